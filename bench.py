@@ -3,12 +3,17 @@
 synthetic S3DIS-like clouds -- 4 clouds x 40960 points per GPU, K=16, 3 mean-field steps.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the K steps and prints the
+headline figure (metric, value, unit, higher_is_better, dtype, ms_per_step) with the run's configuration.  --full adds everything
+measured beside it, including
   "roofline":     the level-0 CRF mean-field forward (similarity + T steps) against the 8 TB/s HBM peak,
                   algorithmic bytes = m * (4 (K-1) + 4 H (2 T + 1))  (SURVEY.md 8(d)), timed with HIP events
-  "cpu_baseline": the CPU oracle (oracle/crf_oracle.py, a port of the reference op sequence) on this host.
+  "cpu_baseline": the CPU oracle (oracle/crf_oracle.py, a port of the reference op sequence) on this host,
+and the fresh-batch / pipelined-loop / reference-loop / other-config legs and the parity report.
+--dump-outputs DIR writes what the last timed step computed (dump_outputs below) before any of that runs.
 """
 import argparse
 import json
@@ -163,6 +168,22 @@ def _print_json_line(obj):
         os.write(_JSON_FD, line.encode())
 
 
+DUMP_BYTES = 60 << 20         # all .npy files of --dump-outputs together, headers included, stay under 64 MB
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every tensor of `arrays` as <path>/<name>.npy in float32.  If they hold more than DUMP_BYTES together, each is cut to
+    its share by a fixed sample of its flattened elements (seed 0, ascending order): the same shapes give the same sample in every run."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        keep = a.size if total <= DUMP_BYTES else max(1, int(a.size * (DUMP_BYTES / total)))
+        if keep < a.size:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
 def main():
     _keep_stdout_for_the_json_line()
     ap = argparse.ArgumentParser()
@@ -173,13 +194,18 @@ def main():
     ap.add_argument('--batch', type=int, default=4, help='clouds per GPU')
     ap.add_argument('--points', type=int, default=40960)
     ap.add_argument('--crf-steps', type=int, default=3)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also measure everything beside the headline figure: fresh-batch replay, pipelined loop, '
+                         'all-reduce, reference loop, parity report, rooflines, other configs, CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help="write what the last timed step computed (loss, logits, flat gradients, updated flat parameters) as DIR/<name>.npy")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='(--full) skip the CPU baseline')
     ap.add_argument('--pipe-gate', default='backward', choices=['off', 'forward', 'backward'],
                     help="the pipelined loop's device-side gate: the collate graph starts when the training step's forward ('forward') / backward ('backward') reaches its coarse levels, or wherever the launches fall ('off')")
     ap.add_argument('--mfma-min-rows', type=int, default=0, help='EXPERIMENT knob (A/B runs only): rows from which the row-streaming Linear forms take over from the tiled ones (ops.state.mfma_min_rows; 0 = the shipped 12288)')
     ap.add_argument('--rehearse', action='store_true', help='rank plumbing only, on the CPU over gloo (no GPU call, no benchmark): see rehearse()')
     ap.add_argument('--other-configs', action='store_true', help='(default since round 5; kept for old command lines)')
-    ap.add_argument('--no-other-configs', action='store_true', help='skip the block that times BASELINE configs 3, 4 (per-GPU share) and 5 on this GPU')
+    ap.add_argument('--no-other-configs', action='store_true', help='(--full) skip the block that times BASELINE configs 3, 4 (per-GPU share) and 5 on this GPU')
     ap.add_argument('--graph', type=int, default=1, help='capture the training step into a hipGraph (1) or run eagerly (0)')
     ap.add_argument('--sort', default='morton', choices=['morton', 'none'],
                     help="point order emitted by the device collate (kernels are order-agnostic)")
@@ -218,10 +244,13 @@ def main():
     #                     [B] SGD(momentum, weight decay) step on views of the bucket.
     # A and B are each captured into a hipGraph (the step issues >1000 small launches; replaying them removes
     # the Python host from the critical path).  The collective stays outside the graphs on purpose.
+    last = {}                                                # the logits of the step run (or captured) last: --dump-outputs
+
     def part_a(d=None):
         d = data if d is None else d
         opt.zero_grad()
         logits = net(d)
+        last['logits'] = logits.detach()                     # (a view: no launch, and no hold on the autograd graph)
         loss = ops.training_loss(logits, d.y, cw, ignore_index=-1)             # trainval.py:101-104, fused kernel
         with ops.deferred_weight_grads(sink=bucket.view_of):     # one batched launch finishes all 74 dW / db reductions, into the bucket
             loss.backward(unit)
@@ -298,6 +327,33 @@ def main():
         rank_ms = {'min': -float(tt[1].item()) / args.steps * 1e3, 'max': dt / args.steps * 1e3}
     ms_per_step = dt / args.steps * 1e3
     value = world * B * N / (dt / args.steps) / 1e6
+    if args.dump_outputs and rank == 0:                  # what the last timed step handed back, before anything below moves it
+        dump_outputs(args.dump_outputs, {'loss': loss, 'logits': last['logits'], 'grads': bucket.flat, 'params': opt.flat})
+
+    line = {
+        'metric': 'M points/sec fwd+bwd, S3DIS 40960-pt cloud, K=16, 3 CRF iters; mIoU parity',
+        'value': value, 'unit': 'M points/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
+        'ms_per_step': ms_per_step, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
+        'dtype': 'f32', 'data': 'synthetic',
+        'config': {'workload': 'BASELINE configs[1]: S3DIS-like synthetic clouds (one point per 4 cm voxel of an '
+                               '8x8x3 m box), %d clouds x %d pts per GPU, K=16, ratios [4,4,4,4,2], '
+                               'PointConvBig(in=6, classes=13, use_crf, steps=%d), train mode: fwd + weighted CE + '
+                               'bwd + flat-bucket grad all-reduce + SGD(momentum) step; tables resident in HBM; point order from '
+                               'the device collate: %s' % (B, N, T, args.sort),
+                   'global_batch': world * B, 'points_per_cloud': N, 'parallelism': 'dp%d (batch-sharded)' % world},
+        'final_loss': float(loss),
+        'launch_mode': graph_note,
+        'rccl_ranks_seen': torch.distributed.get_world_size() if grouped else 1,
+        'dist_backend': torch.distributed.get_backend() if grouped else None,
+        'rank_ms_per_step': rank_ms, 'gpu_max_hw_queues': os.environ.get('GPU_MAX_HW_QUEUES'),
+    }
+    if not args.full:                                    # a plain run: the headline figure only
+        if rank == 0:
+            _print_json_line(line)
+        if grouped:
+            torch.distributed.barrier()
+            torch.distributed.destroy_process_group()
+        return
 
     # ---- per-batch costs that the timed loop (ONE resident batch, cached tables) does not pay, and the proof that the
     # captured step trains on a FRESH batch.  A new batch is collated (kNN etc. on the GPU), copied into the static
@@ -508,10 +564,9 @@ def main():
             torch.cuda.synchronize()
             pipe_ms = None
 
-    # ---- the all-reduce alone (HIP events around 20 calls on the launching stream), and what the group looks like
-    allreduce_us, allreduce_host_us, backend_name = None, None, None
+    # ---- the all-reduce alone (HIP events around 20 calls on the launching stream)
+    allreduce_us, allreduce_host_us = None, None
     if grouped:
-        backend_name = torch.distributed.get_backend()
         for _ in range(5):
             collective()
         torch.cuda.synchronize()
@@ -542,18 +597,8 @@ def main():
             ref_loop = {'error': str(e).splitlines()[0][:200]}
 
     if rank == 0:
-        out = {
-            'metric': 'M points/sec fwd+bwd, S3DIS 40960-pt cloud, K=16, 3 CRF iters; mIoU parity',
-            'value': value, 'unit': 'M points/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-            'ms_per_step': ms_per_step, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-            'dtype': 'f32', 'data': 'synthetic',
-            'config': {'workload': 'BASELINE configs[1]: S3DIS-like synthetic clouds (one point per 4 cm voxel of an '
-                                   '8x8x3 m box), %d clouds x %d pts per GPU, K=16, ratios [4,4,4,4,2], '
-                                   'PointConvBig(in=6, classes=13, use_crf, steps=%d), train mode: fwd + weighted CE + '
-                                   'bwd + flat-bucket grad all-reduce + SGD(momentum) step; tables resident in HBM; point order from '
-                                   'the device collate: %s' % (B, N, T, args.sort),
-                       'global_batch': world * B, 'points_per_cloud': N, 'parallelism': 'dp%d (batch-sharded)' % world},
-            'final_loss': float(loss),
+        out = dict(line)
+        out.update({
             'preprocess_ms_per_batch': fresh['collate_ms_per_batch'],
             'table_refresh_ms_per_batch': fresh['table_refresh_ms_per_batch'],
             'preprocess_plus_refresh_graph_ms_per_batch': fresh['collate_plus_refresh_graph_ms_per_batch'],
@@ -561,17 +606,14 @@ def main():
             'pipelined_ms_per_batch': pipe_ms, 'pipelined_gate': pipe_gate,
             'value_incl_preprocessing': world * B * N / ((pipe_ms or per_batch_ms) * 1e-3) / 1e6,
             'fresh_batch_replay': fresh,
-            'launch_mode': graph_note,
-            'rccl_ranks_seen': torch.distributed.get_world_size() if grouped else 1,
-            'dist_backend': backend_name, 'allreduce_us': allreduce_us, 'allreduce_host_issue_us': allreduce_host_us,
-            'rank_ms_per_step': rank_ms, 'gpu_max_hw_queues': os.environ.get('GPU_MAX_HW_QUEUES'),
+            'allreduce_us': allreduce_us, 'allreduce_host_issue_us': allreduce_host_us,
             'trainval_eager_ms_per_step': None if ref_loop is None else ref_loop.get('eager_ms_per_step'),
             'trainval_captured_ms_per_step': None if ref_loop is None else ref_loop.get('captured_ms_per_step'),
             'trainval_graphed_module_ms_per_step': None if ref_loop is None else ref_loop.get('graphed_module_ms_per_step'),
             'trainval_captured_as_written_ms_per_step': None if ref_loop is None else ref_loop.get('captured_as_written_ms_per_step'),
             'reference_loop': ref_loop,
             'parity': _parity_report(),
-        }
+        })
         out['roofline'] = roofline_meanfield(data, dev, 8, T)
         out['roofline']['measured_copy_GBps'] = copy_ceiling(dev)
         out['roofline_bwd'] = roofline_meanfield_bwd(data, dev, 8, T)

@@ -4,6 +4,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 tag=${1:-r6k}
 part=${2:-all}
 mkdir -p gpurun_out/$tag
+res=${OUT_ROOT:-scratch/out}/$tag; mkdir -p $res      # the bench lines (--full); OUT_ROOT: relative to the repository root
 if [ $part = all ] || [ $part = tests ]; then
 rm -f gpurun_out/$tag/parity_report.json
 CRFCONV_PARITY_RECORD=$GRAFT_REPO_ROOT/gpurun_out/$tag/parity_report.json CRFCONV_TOL_RECORD=$GRAFT_REPO_ROOT/gpurun_out/$tag/tol_recorded.json timeout -k 10 1000 python3 -m pytest tests -m gpu -q > gpurun_out/$tag/tests.log 2>&1
@@ -30,8 +31,8 @@ if [ $part = all ] || [ $part = pmc2 ]; then
 bash scratch/run_pcpmc.sh > gpurun_out/$tag/pcpmc.log 2>&1; echo "pointconv pmc done"; rm -rf gpurun_out/pmc_pc
 fi
 if [ $part = all ] || [ $part = spawn ]; then
-timeout -k 10 400 python3 bench.py --gpus 1 --spawn --steps 30 --no-cpu-baseline --no-other-configs > gpurun_out/$tag/bench_spawn1.json 2> gpurun_out/$tag/bench_spawn1.err; echo "spawn bench rc=$?"
+timeout -k 10 400 python3 bench.py --full --gpus 1 --spawn --steps 30 --no-cpu-baseline --no-other-configs > $res/bench_spawn1.json 2> $res/bench_spawn1.err; echo "spawn bench rc=$?"
 fi
 if [ $part = all ] || [ $part = bench ]; then
-timeout -k 10 900 python3 bench.py > gpurun_out/$tag/bench.json 2> gpurun_out/$tag/bench.err; echo "bench rc=$?"; tail -3 gpurun_out/$tag/bench.err | cut -c1-300
+timeout -k 10 900 python3 bench.py --full > $res/bench.json 2> $res/bench.err; echo "bench rc=$?"; tail -3 $res/bench.err | cut -c1-300
 fi

@@ -161,7 +161,7 @@ def test_bench_pipelined_loop_on_two_ranks(tmp_path):
     env = dict(os.environ, MASTER_ADDR='127.0.0.1', MASTER_PORT='29547', WORLD_SIZE='2', CRFCONV_DIST_BACKEND='gloo',
                OMP_NUM_THREADS='2')
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '1', '--batch', '2',
-           '--points', '8192', '--no-cpu-baseline']
+           '--points', '8192', '--no-cpu-baseline', '--full']
     outs = [open(str(tmp_path / ('out.%d' % r)), 'w') for r in range(2)]
     procs = [subprocess.Popen(cmd, env=dict(env, RANK=str(r), LOCAL_RANK=str(r)), stdout=outs[r], stderr=subprocess.STDOUT, cwd=ROOT)
              for r in range(2)]
@@ -187,7 +187,7 @@ def test_bench_self_launch_one_rank_over_rccl(tmp_path):
                                                             'CRFCONV_DIST_BACKEND')}
     env['OMP_NUM_THREADS'] = '4'
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--spawn', '--steps', '4', '--warmup', '1', '--batch', '2',
-           '--points', '8192', '--no-cpu-baseline']
+           '--points', '8192', '--no-cpu-baseline', '--full']
     with open(str(tmp_path / 'out'), 'w') as fo, open(str(tmp_path / 'err'), 'w') as fe:
         rc = subprocess.run(cmd, env=env, stdout=fo, stderr=fe, cwd=ROOT, timeout=900).returncode
     assert rc == 0, open(str(tmp_path / 'err')).read()[-3000:]
@@ -210,7 +210,7 @@ def test_bench_self_launch_two_ranks_sharing_the_gpu(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
     env.update(CRFCONV_DIST_BACKEND='gloo', OMP_NUM_THREADS='2')
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--batch', '2', '--points', '8192',
-           '--no-cpu-baseline']
+           '--no-cpu-baseline', '--full']
     with open(str(tmp_path / 'out'), 'w') as fo, open(str(tmp_path / 'err'), 'w') as fe:
         rc = subprocess.run(cmd, env=env, stdout=fo, stderr=fe, cwd=ROOT, timeout=900).returncode
     assert rc == 0, open(str(tmp_path / 'err')).read()[-3000:]
@@ -219,6 +219,34 @@ def test_bench_self_launch_two_ranks_sharing_the_gpu(tmp_path):
     rec = json.loads(lines[0])
     assert rec['n_gpus'] == 2 and rec['rccl_ranks_seen'] == 2 and rec['dist_backend'] == 'gloo' and rec['scaling'] == 'weak'
     assert rec['config']['global_batch'] == 4 and rec['value'] > 0 and rec['allreduce_us'] > 0
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: the headline line only (none of the --full legs),
+    `steps` = K, and DIR holds the loss, logits, flat gradients and updated flat parameters of the last timed step in float32.  Two runs
+    with the same arguments start from the same inputs: their dumps agree to float32 rounding (different inputs differ at O(1))."""
+    import json
+    recs, dumps = [], []
+    for run in range(2):
+        out_dir = tmp_path / ('dump%d' % run)
+        cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--batch', '2',
+               '--points', '8192', '--dump-outputs', str(out_dir)]
+        res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, cwd=ROOT, timeout=600)
+        assert res.returncode == 0, res.stderr[-3000:]
+        lines = [l for l in res.stdout.splitlines() if l.startswith('{')]
+        assert len(lines) == 1
+        recs.append(json.loads(lines[0]))
+        dumps.append({k: np.load(str(out_dir / (k + '.npy'))) for k in ('loss', 'logits', 'grads', 'params')})
+    rec, d = recs[0], dumps[0]
+    assert rec['steps'] == 3 and rec['warmup'] == 1 and rec['n_gpus'] == 1 and rec['unit'] == 'M points/s' and rec['dtype'] == 'f32'
+    assert rec['higher_is_better'] is True and rec['ms_per_step'] > 0 and abs(rec['value'] - 2 * 8192 / rec['ms_per_step'] / 1e3) < 1e-6 * rec['value']
+    assert not {'roofline', 'cpu_baseline', 'other_configs', 'reference_loop', 'parity', 'fresh_batch_replay'} & set(rec)
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in d.values())
+    assert d['logits'].shape == (2 * 8192, 13) and d['grads'].shape == d['params'].shape and d['params'].size > 100000
+    assert abs(float(d['loss']) - rec['final_loss']) < 1e-6 and np.abs(d['grads']).max() > 0
+    for k in d:
+        err = np.abs(d[k].astype(np.float64) - dumps[1][k]).max() / max(1.0, np.abs(d[k]).max())
+        assert err < 1e-3, (k, err)
 
 
 GUARD_WORKER = r'''

@@ -17,6 +17,16 @@ from oracle import native as onative
 pytestmark = pytest.mark.gpu
 
 
+@pytest.fixture(autouse=True)
+def _restore_host_threads():
+    """Tests below run the CPU oracle on 16 host threads (torch.set_num_threads); the count goes back after each of them, so that the
+    tests that follow in the same process -- the oracle's golden checks (tests/test_oracle_golden.py: 4 threads) among them -- keep
+    the summation order they were pinned with."""
+    n = torch.get_num_threads()
+    yield
+    torch.set_num_threads(n)
+
+
 @pytest.fixture
 def big_forms_from_4096(monkeypatch):
     """Kernel-level tests of the row-streaming (big-level) forms use 4 100 ... 10 240 rows to stay quick; the shipped switch-over

@@ -179,6 +179,27 @@ def test_step_byte_model_reproduces_the_survey_figures():
     assert abs(bench.step_byte_model(4, 81920, 16, 3, 13)[0] / total - 2.0) < 1e-9
 
 
+def test_bench_dump_outputs_keeps_a_fixed_sample_within_its_budget(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs): arrays under the budget are written whole in float32; over it, each array keeps its share as
+    a seeded sample of its flattened elements in ascending order -- the same sample in every call."""
+    bench = _load_bench()
+    g = torch.Generator().manual_seed(3)
+    arrays = {'a': torch.randn(300, 7, generator=g), 'b': torch.randn(100, generator=g, dtype=torch.float64), 'c': torch.tensor(2.5)}
+    bench.dump_outputs(str(tmp_path / 'whole'), arrays)
+    for k, v in arrays.items():
+        a = np.load(str(tmp_path / 'whole' / (k + '.npy')))
+        assert a.dtype == np.float32 and a.shape == tuple(v.shape) and np.array_equal(a, v.float().numpy())
+    monkeypatch.setattr(bench, 'DUMP_BYTES', 4 * 1000)                # 2201 elements in all -> 1000 kept
+    for run in ('s1', 's2'):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+    files = {k: np.load(str(tmp_path / 's1' / (k + '.npy'))) for k in arrays}
+    assert sum(a.nbytes for a in files.values()) <= 4 * 1000
+    assert files['a'].shape == (954,) and files['b'].shape == (45,) and files['c'].shape == ()
+    assert np.isin(files['a'], arrays['a'].numpy().reshape(-1)).all()
+    for k in arrays:
+        assert np.array_equal(files[k], np.load(str(tmp_path / 's2' / (k + '.npy'))))
+
+
 def test_bench_starts_its_own_ranks_without_a_launcher_environment(monkeypatch):
     """`python bench.py --gpus N` with no WORLD_SIZE in the environment: N child processes with the torchrun variables on 127.0.0.1,
     the parent's exit status = the first failing rank's; under a launcher (WORLD_SIZE set) or at N = 1 without --spawn: nothing."""
