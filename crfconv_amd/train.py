@@ -14,11 +14,24 @@ would then have to synchronise with that stream.
 Round 6: the dense network captures ITSELF (``autograph``).  ``models.PointConvBig`` in training mode hands its forward to a private
 GraphedModel (below) the first time it is called on a device batch, so the reference loop with nothing wrapped -- trainval.py:96-106 as
 written -- runs as two hipGraph replays per step from its second iteration on.  What does not fit runs eagerly, silently and correctly:
-eval mode, ``no_grad``, a batch of other shapes, a forward whose predecessor has not been through ``backward()`` yet (its output is still
-in use: the replay would overwrite it), a model with forward / backward hooks on any submodule, a call during another stream capture.
-``set_autograph(False)`` / ``CRFCONV_AUTOGRAPH=0`` / ``with no_autograph():`` switch it off (every launch issued by the host: 2-3 x the step
-time); ``DistributedDataParallel`` around the model is untested -- switch it off there."""
+eval mode, ``no_grad``, a batch of other shapes or on another device, a forward whose predecessor has not been through ``backward()`` yet
+while anything still reaches that pass's autograd node (a loss is enough -- ``crit(net(b1), y1) + crit(net(b2), y2)``: the replay would
+overwrite the activations its backward needs; a pass whose loss was dropped unused no longer counts), module forward / backward hooks on
+the model or any submodule and torch's global module hooks (checked at every call, also those registered after the capture), parameters
+frozen / thawed since the capture, a call during another stream capture.  Parameters or buffers that are other objects or live at other
+addresses than at the capture (``load_state_dict(..., assign=True)``, optim.FlatSGD re-homing them, ``p.data = ...``) drop the graphs;
+the model captures again at the first training call that no autograd graph of an earlier pass reaches any more (a loop that releases
+its loss before the next forward: at once), eagerly until then; to() / cuda() / float() drop the graphs too.  The logits returned are the caller's own (a copy of the static
+output: kept across steps they keep their values).  What raises (RuntimeError) instead of computing something else: the backward of a
+replayed pass after a later pass has replayed over its activations, or a second backward of one replayed pass (``retain_graph=True`` does
+not keep a replayed pass) -- the model's autograph-off twin gives the eager gradients there.  Still aliased, by design: after
+``backward()`` every parameter's ``.grad`` is a view of a static gradient buffer, moved out to storage of its own before the next replay
+if still held (accumulation over several backward passes works; a reference kept to an old ``.grad`` object across a zero_grad() and
+the next step sees the later values).  ``set_autograph(False)`` / ``CRFCONV_AUTOGRAPH=0`` / ``with no_autograph():`` switch it off (every
+launch issued by the host: 2-3 x the step time); ``DistributedDataParallel`` around the model is untested -- switch it off there."""
+import operator
 import os
+import weakref
 
 import torch
 
@@ -51,11 +64,18 @@ def autograph_wanted(batch):
     return not torch.cuda.is_current_stream_capturing()
 
 
+def _hook_dicts(modules):
+    return [d for m in modules for d in (m._forward_hooks, m._forward_pre_hooks, m._backward_hooks, m._backward_pre_hooks)]
+
+
+def _global_hooks():
+    """torch.nn.modules.module.register_module_forward_hook & co.: they fire for every module, the replayed ones included."""
+    M = torch.nn.modules.module
+    return bool(M._global_forward_hooks or M._global_forward_pre_hooks or M._global_backward_hooks or M._global_backward_pre_hooks)
+
+
 def _has_hooks(model):
-    for m in model.modules():
-        if m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or getattr(m, '_backward_pre_hooks', None):
-            return True
-    return False
+    return _global_hooks() or any(_hook_dicts(model.modules()))
 
 
 def autograph_forward(model, batch):
@@ -66,6 +86,8 @@ def autograph_forward(model, batch):
             return None
         runner = GraphedModel(model, guard_pending=True)
         object.__setattr__(model, '_autograph', runner)      # (not a submodule of the model: the model is the runner's)
+    elif runner.hooked():
+        return None                                          # a hook registered since the capture: the model's own forward calls it
     elif runner.training is not model.training:
         runner.training = model.training                     # (the runner is outside the model's tree: train() / eval() do not reach it)
     return runner(batch)
@@ -144,20 +166,37 @@ class CapturedStep:
 
 
 class _GraphedPass(torch.autograd.Function):
-    """model(batch) as one forward replay; the gradient of whatever the caller computed from its output as one backward replay."""
+    """model(batch) as one forward replay; the gradient of whatever the caller computed from its output as one backward replay.
+
+    The replays work on ONE set of static buffers: every forward replay overwrites the activations the previous pass saved, and its
+    backward replay consumes them (a memory pool shared by both graphs: the backward reuses freed activations for its temporaries).
+    `gm._gen` counts both; a pass may run its backward only while the buffers still hold ITS state (ctx.gen == gm._gen) -- a stale or
+    repeated backward raises instead of replaying over another pass's activations."""
 
     @staticmethod
     def forward(ctx, gm, *params):
         gm.fwd_graph.replay()
-        ctx.gm = gm
-        gm._pending = True                 # this output lives in the static buffer until its backward has run (autograph's guard)
+        gm._gen += 1
+        ctx.gm, ctx.gen = gm, gm._gen
+        gm._passes.add(ctx)
+        if gm.guard_pending:
+            # pending until its backward has run or its autograd node is gone (autograph's guard).  The node, not the output: a loss
+            # keeps the node alive without keeping the output (cross_entropy saves its own intermediates)
+            gm._pending = weakref.ref(ctx)
+            return gm.static_out.clone()       # the caller owns its logits: the next replay overwrites static_out
         return gm.static_out.detach()
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
         gm = ctx.gm
-        gm._pending = False
+        if ctx.gen != gm._gen:
+            raise RuntimeError('crfconv_amd.train: backward through a replayed training pass whose saved activations are gone -- a later '
+                               'forward replay overwrote them, or this pass has been through backward() already (retain_graph=True '
+                               'does not keep a replayed pass).  Run the backward before the next training call of the model, or run '
+                               'this pass eagerly (train.no_autograph()).')
+        gm._gen += 1
+        gm._pending = None
         gm._keep_accumulated_grads()
         gm.static_gout.copy_(g)
         gm.bwd_graph.replay()
@@ -165,6 +204,20 @@ class _GraphedPass(torch.autograd.Function):
         # takes a gradient nobody else holds AS .grad -- handed the objects of gm.static_grads themselves it copies every one of them
         # (about 300 small copy launches per step for PointConvBig, 0.5 ms of the step)
         return (None,) + tuple(None if sg is None else sg.detach() for sg in gm.static_grads)
+
+
+class _EagerPass(torch.autograd.Function):
+    """Identity node behind an output the runner computed eagerly: while it lives (a loss reaches it), so may the parameters' gradient
+    accumulators of that pass -- GraphedModel does not capture again then (see forward)."""
+
+    @staticmethod
+    def forward(ctx, gm, out):
+        gm._passes.add(ctx)
+        return out.view_as(out)
+
+    @staticmethod
+    def backward(ctx, g):
+        return None, g
 
 
 class GraphedModel(torch.nn.Module):
@@ -178,19 +231,26 @@ class GraphedModel(torch.nn.Module):
     between -- about 300 library launches per step leave the host as two.  The first training call captures (after `warmup` eager
     passes on a side stream whose effect on BatchNorm statistics and dropout counters is undone); later batches of the SAME shapes
     are copied into the captured batch's buffers (MultiScaleData.load_: one copy launch + the table refreshes).  A batch of other
-    shapes, eval mode and no_grad calls run the wrapped model eagerly.  Parameter gradients come back through autograd (hooks,
+    shapes, eval mode, no_grad calls, module hooks (any submodule, torch's global ones) and parameters frozen / thawed since the capture
+    run the wrapped model eagerly; parameters or buffers re-homed since the capture (other objects or addresses) capture again, once no
+    earlier pass's autograd graph is alive (eagerly until then: that graph holds the parameters' gradient accumulators, bound to another stream).  The
+    backward of a pass that a later training call has replayed over raises (RuntimeError): without the self-capturing models' pending
+    guard (below), ``crit(net(b1)) + crit(net(b2))`` is such a pass.  Parameter gradients come back through autograd (hooks,
     accumulation over several backward passes see ordinary gradients -- tested; a hook-based wrapper such as DistributedDataParallel
     should too, untested); the output -- and, after ``backward()``, every parameter's
     ``.grad`` -- aliases a static buffer that the next call overwrites, as with torch.cuda.make_graphed_callables (gradients still held as ``.grad``
     at the next call are moved out first: _keep_accumulated_grads)."""
 
     def __init__(self, model, warmup=2, defer_weight_grads=True, guard_pending=False):
-        """guard_pending (the self-capturing models' setting): a training call whose predecessor's output has not been through
-        ``backward()`` runs the model eagerly instead of replaying over it."""
+        """guard_pending (the self-capturing models' setting): a training call whose predecessor has not been through ``backward()``
+        while its autograd node is still reachable runs the model eagerly instead of replaying over it, and the output is a copy of the
+        static one (the caller's to keep)."""
         super().__init__()
         self.model = model
         self.warmup, self.defer_weight_grads = int(warmup), bool(defer_weight_grads)
-        self.guard_pending, self._pending, self._last_out = bool(guard_pending), False, None
+        self.guard_pending, self._pending, self._gen = bool(guard_pending), None, 0
+        self._passes = weakref.WeakSet()                         # autograd nodes of this runner's passes that are still alive
+        self.captures = 0
         self.fwd_graph = self.bwd_graph = None
         self.static = self.static_out = self.static_gout = None
         self.params, self.static_grads, self._sig = [], [], None
@@ -223,7 +283,7 @@ class GraphedModel(torch.nn.Module):
         sig = []
 
         def visit(t):
-            sig.append((tuple(t.shape), t.dtype))
+            sig.append((tuple(t.shape), t.dtype, t.device))
             return t
         batch._apply(visit)
         return tuple(sig)
@@ -237,13 +297,23 @@ class GraphedModel(torch.nn.Module):
             self.static_out.backward(self.static_gout)
 
     def _capture(self, batch):
-        with no_autograph():                                    # (the wrapped model's forward is issued launch by launch inside this capture)
-            self._capture_eagerly_issued(batch)
+        self.captures += 1
+        # no garbage collection inside the capture: a dead runner of another model (model <-> runner is a reference cycle) owns graphs,
+        # and destroying a graph in the middle of another capture aborts the process -- the dead ones go here, before it
+        import gc
+        gc.collect()
+        was = gc.isenabled()
+        gc.disable()
+        try:
+            with no_autograph():                                # (the wrapped model's forward is issued launch by launch inside this capture)
+                self._capture_eagerly_issued(batch)
+        finally:
+            if was:
+                gc.enable()
 
     def _capture_eagerly_issued(self, batch):
         model = self.model
         self.params = [p for p in model.parameters() if p.requires_grad]
-        self._frozen = tuple(p.requires_grad for p in model.parameters())
         self.static = batch._apply(torch.clone)
         self._sig = self._signature(batch)
         user_grads = [p.grad for p in self.params]
@@ -277,6 +347,41 @@ class GraphedModel(torch.nn.Module):
         self.static_out = self.static_out.detach()
         for p, g in zip(self.params, user_grads):
             p.grad = g
+        self._snapshot()                                        # (after the warm-up: the first training forward re-homes the step counters)
+
+    # What the graphs were captured against, kept as flat lists so that the per-call check costs tens of microseconds, not the
+    # hundreds of a walk over model.modules() / model.parameters(): every module's hook dictionaries, every module's parameter /
+    # buffer / submodule slots (an object put in a slot -- load_state_dict(assign=True), a replaced submodule -- changes an id), the
+    # device address of every parameter and buffer (``p.data = ...``, e.g. optim.FlatSGD re-homing the parameters) and requires_grad.
+    def _snapshot(self):
+        modules = list(self.model.modules())
+        self._hooks = _hook_dicts(modules)
+        slots = [(d, k, v) for m in modules for d in (m._parameters, m._buffers, m._modules) for k, v in d.items()]
+        self._slot_dicts, self._slot_keys, self._slot_objs = [s[0] for s in slots], [s[1] for s in slots], [s[2] for s in slots]
+        self._tensors = list(self.model.parameters()) + list(self.model.buffers())
+        self._ptrs = list(map(torch.Tensor.data_ptr, self._tensors))
+        self._all_params = list(self.model.parameters())
+        self._grad_flags = [p.requires_grad for p in self._all_params]
+
+    def hooked(self):
+        """A module forward / backward hook on the wrapped model or any submodule, or a global one: the replay would skip it."""
+        if self.fwd_graph is None:
+            return _has_hooks(self.model)
+        return _global_hooks() or any(self._hooks)
+
+    def _moved(self):
+        """Parameters or buffers are other objects or live at other addresses than at the capture: the graphs would read stale storage."""
+        try:
+            same = all(map(operator.is_, map(operator.getitem, self._slot_dicts, self._slot_keys), self._slot_objs))
+        except KeyError:                                        # (a slot deleted)
+            same = False
+        return not same or list(map(torch.Tensor.data_ptr, self._tensors)) != self._ptrs
+
+    def _drop_graphs(self):
+        self._gen += 1                                          # (a pass of the old graphs has nothing left to run its backward on)
+        self.fwd_graph = self.bwd_graph = None
+        self.static = self.static_out = self.static_gout = None
+        self.params, self.static_grads, self._sig = [], [], None
 
     def _keep_accumulated_grads(self):
         """A caller who accumulates over several backward passes (no zero_grad() in between) holds last pass's static buffers as
@@ -289,27 +394,33 @@ class GraphedModel(torch.nn.Module):
 
     def _eager(self, batch):
         with no_autograph():
-            return self.model(batch)
+            out = self.model(batch)
+        return _EagerPass.apply(self, out) if torch.is_tensor(out) and out.requires_grad else out
 
     def forward(self, batch):
         if not (self.training and torch.is_grad_enabled()):
             return self._eager(batch)
-        if self.guard_pending and self._pending:
-            if self._last_out is not None and self._last_out() is None:
-                self._pending = False                           # ... unless nobody holds it any more (a step that skipped its backward)
+        if not self.guard_pending and self.hooked():            # (autograph_forward has checked: the model's own forward runs them)
+            return self._eager(batch)
+        if self.guard_pending and self._pending is not None:
+            if self._pending() is None:
+                self._pending = None                            # ... unless its autograd node is gone (a step that skipped its backward)
             else:
-                return self._eager(batch)                       # the previous output is still in use: nothing may be replayed over it
+                return self._eager(batch)                       # the previous pass still awaits its backward: nothing may replay over it
+        if self.fwd_graph is not None and self._moved():
+            self._drop_graphs()                                 # a pending pass of the old graphs raises at its backward (_GraphedPass)
         if self.fwd_graph is None:
+            if self._passes:
+                # a live autograd graph of an earlier pass holds the parameters' gradient accumulators, bound to the stream they were
+                # created on: the captured backward would have to join that stream (the capture fails, or worse) -- eagerly until
+                # every earlier pass has been dropped (the next call of a loop that releases its loss before it)
+                return self._eager(batch)
             self._capture(batch)
         elif batch is not self.static and self._signature(batch) != self._sig:
             return self._eager(batch)
-        elif self.guard_pending and self._frozen != tuple(p.requires_grad for p in self.model.parameters()):
+        elif [p.requires_grad for p in self._all_params] != self._grad_flags:
             return self._eager(batch)                           # parameters frozen / thawed since the capture
         self._keep_accumulated_grads()
         if batch is not self.static:
             self.static.load_(batch, defer_check=True)          # (no host synchronisation: a bad table raises at the next call)
-        out = _GraphedPass.apply(self, *self.params)
-        if self.guard_pending:
-            import weakref
-            self._last_out = weakref.ref(out)
-        return out
+        return _GraphedPass.apply(self, *self.params)

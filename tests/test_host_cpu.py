@@ -341,3 +341,76 @@ def test_graphed_model_state_dict_is_symmetric_as_a_submodule():
     assert 'net.lin.weight' in sd and not any('.model.' in k for k in sd)
     b.load_state_dict(sd, strict=True)
     assert torch.equal(b.net.model.lin.weight, a.net.model.lin.weight) and torch.equal(b.net.model.bn.running_var, a.net.model.bn.running_var)
+
+
+def test_graphed_model_signature_tells_devices_apart():
+    """GraphedModel._signature keys a batch by shape, dtype AND device: a batch of the captured shapes on another device must not be
+    load_()-ed into the captured one."""
+    import torch
+    from crfconv_amd.data import Data
+    from crfconv_amd.train import GraphedModel
+
+    def batch(dev, fill=0.0):
+        return Data(x=torch.full((2, 5, 6), fill, device=dev), y=torch.zeros(2, 5, dtype=torch.long, device=dev),
+                    multiscale=[Data(pos=torch.zeros(2, 5, 3, device=dev))])
+    sig = GraphedModel._signature
+    assert sig(batch('cpu')) == sig(batch('cpu', 1.0))
+    assert sig(batch('cpu')) != sig(batch('meta'))
+    assert sig(batch('cpu')) != sig(Data(x=torch.zeros(2, 5, 6), y=torch.zeros(2, 5, dtype=torch.int32),
+                                         multiscale=[Data(pos=torch.zeros(2, 5, 3))]))
+
+
+def test_graphed_model_per_call_checks_see_hooks_and_moved_tensors_after_capture():
+    """The per-call checks of GraphedModel.forward over its capture-time snapshot (no GPU needed: the snapshot is all they read):
+    hooks registered after the capture -- on any submodule, of every kind, and torch's global module hooks -- and parameters / buffers
+    / submodules that are other objects or live at other addresses (p.data = ..., load_state_dict(assign=True), optim.FlatSGD's
+    re-homing) are noticed; an in-place load_state_dict is not a move."""
+    import torch
+    from crfconv_amd.train import GraphedModel
+
+    class Inner(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.lin, self.bn = torch.nn.Linear(3, 4), torch.nn.BatchNorm1d(4)
+            self.head = torch.nn.Sequential(torch.nn.Linear(4, 4), torch.nn.ReLU())
+
+    inner = Inner()
+    g = GraphedModel(inner, guard_pending=True)
+
+    def snapshot():
+        g._snapshot()
+        g.fwd_graph = object()                                # (as after a capture: the checks read the snapshot)
+        assert not g.hooked() and not g._moved()
+    snapshot()
+    M = torch.nn.modules.module
+    for register in (lambda f: inner.head[0].register_forward_hook(lambda m, i, o: None),
+                     lambda f: inner.bn.register_forward_pre_hook(lambda m, i: None),
+                     lambda f: inner.lin.register_full_backward_hook(lambda m, gi, go: None),
+                     lambda f: inner.register_full_backward_pre_hook(lambda m, go: None),
+                     lambda f: M.register_module_forward_hook(lambda m, i, o: None),
+                     lambda f: M.register_module_forward_pre_hook(lambda m, i: None),
+                     lambda f: M.register_module_full_backward_hook(lambda m, gi, go: None)):
+        h = register(None)
+        assert g.hooked()
+        h.remove()
+        assert not g.hooked()
+    sd = {k: v.clone() + 1 for k, v in inner.state_dict().items()}
+    inner.load_state_dict(sd)                                 # values copied in place: the graphs stay valid
+    assert not g._moved()
+    inner.head[0].weight.data = inner.head[0].weight.data.clone()
+    assert g._moved()
+    snapshot()
+    inner.bn.running_mean.data = inner.bn.running_mean.clone()
+    assert g._moved()
+    snapshot()
+    inner.load_state_dict({k: v.clone() for k, v in inner.state_dict().items()}, assign=True)
+    assert g._moved()
+    snapshot()
+    inner.load_state_dict(inner.state_dict(), assign=True)    # other Parameter objects over the same storage: still a move
+    assert g._moved()
+    snapshot()
+    inner.head[1] = torch.nn.ReLU()
+    assert g._moved()
+    snapshot()
+    del inner.head[1]
+    assert g._moved()
