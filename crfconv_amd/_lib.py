@@ -191,8 +191,17 @@ SIGNATURES = {
     'crfconv_argmin_f64': (_i, [_vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     'crfconv_possibility_crop_workspace': (_sz, [_i64, _i64]),
     'crfconv_possibility_crop': (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'crfconv_augment_workspace': (_sz, [_i64, _i64]),
+    'crfconv_augment': (_i, [_vp, _vp, _i64, _i64, _i, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
+
+
+class AugmentSpec(ctypes.Structure):
+    """crf_augment_spec of include/crfconv_amd.h."""
+    _fields_ = [('rotate_axis', ctypes.c_int32), ('deg_lo', ctypes.c_float), ('deg_hi', ctypes.c_float), ('scale', ctypes.c_int32),
+                ('scale_lo', ctypes.c_float), ('scale_span', ctypes.c_float), ('flip_axes', ctypes.c_int32), ('noise', ctypes.c_int32),
+                ('sigma', ctypes.c_float), ('clip', ctypes.c_float), ('drop', ctypes.c_int32), ('drop_p', ctypes.c_float)]
 
 
 class ReduceJob(ctypes.Structure):

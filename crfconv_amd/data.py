@@ -368,8 +368,13 @@ class CollateGraph:
         train_graph.replay()
     """
 
-    def __init__(self, target, kernel_size=(16, 16, 16, 16, 16), ratio=(4, 4, 4, 4, 2), generator=None, device_draw=True, slot=0, gate=None):
+    def __init__(self, target, kernel_size=(16, 16, 16, 16, 16), ratio=(4, 4, 4, 4, 2), generator=None, device_draw=True, slot=0, gate=None,
+                 augment=None):
         self.target, self.kernel_size, self.ratio, self.generator = target, tuple(kernel_size), tuple(ratio), generator
+        # augment: a transforms.Compose (the reference's train_transform, trainval.py:26-36) applied to the new clouds ahead of the Morton
+        # sort and the kNN -- inside the graph with device_draw, eagerly in front of it otherwise.  Keyed on this graph's seed and batch
+        # counter (the kernel adds its own domain constant): no extra generator draw, and state_dict() resumes the augmented sequence too.
+        self.augment = augment
         self.device_draw = bool(device_draw)
         self.gate = gate                         # 4 int64 device words (crfconv_gate_wait): the graph's first launch waits for a mark of the training stream
         # The subset seed is a DRAW on the caller's generator (it advances the generator's state): graphs built one after the
@@ -402,6 +407,8 @@ class CollateGraph:
         self.graph = None
         self._uploaded = None                    # event after the last upload from the pinned buffers
         self.counter = torch.zeros(1, dtype=torch.int64, device=dev)      # batches collated so far (device_draw: keys the subsets)
+        if augment is not None and self.x is not None and self.x.shape[-1] not in (3, 6):
+            raise ValueError('CollateGraph(augment=...): x must be [pos] or [pos, rgb] (3 or 6 channels), got %d' % self.x.shape[-1])
 
     def state_dict(self):
         """What a checkpoint needs to continue this graph's subset sequence: the seed and the batch counter (device word)."""
@@ -433,6 +440,8 @@ class CollateGraph:
             from . import _lib
             from .graph import ptr, stream_ptr
             _lib.call('crfconv_add_i64', ptr(self.counter), 1, 1, stream_ptr())       # counter += 1 (a library launch: no framework kernel in the graph)
+            if self.augment is not None:
+                self.augment.apply_batch(self.pos, self.x, self.seed, self.counter)
             random_subsets_device(self.sizes, [c.numel() for c in self.choices], self.seed, self.counter, self.choices, ranks=self.ranks)
             morton_order(self.pos, out=self.order)
         return multiscale_compute(self.pos, x=self.x, y=self.y, kernel_size=self.kernel_size, ratio=self.ratio,
@@ -442,13 +451,21 @@ class CollateGraph:
     def _work(self):
         self.target.load_(self._work_collate())
 
-    def _inputs(self, pos, x, y):
+    def _copy_inputs(self, pos, x, y):
         self.pos.copy_(pos)
         if self.x is not None:
             self.x.copy_(x)
         if self.y is not None:
             self.y.copy_(y)
+
+    def _inputs(self, pos, x, y):
+        self._copy_inputs(pos, x, y)
         if not self.device_draw:
+            if self.augment is not None:          # eagerly, on the batch counter advanced here (the graph advances it with device_draw)
+                from . import _lib
+                from .graph import ptr, stream_ptr
+                _lib.call('crfconv_add_i64', ptr(self.counter), 1, 1, stream_ptr())
+                self.augment.apply_batch(self.pos, self.x, self.seed, self.counter)
             self._draw()                          # host torch.randperm + pinned upload; the argsort eagerly in front of the graph
             morton_order(self.pos, out=self.order)
 
@@ -466,6 +483,8 @@ class CollateGraph:
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):
                 self._work()
+            if self.augment is not None and self.device_draw:
+                self._copy_inputs(pos, x, y)                  # the warm-up augmented the staged clouds in place
         self.graph.replay()
         return self.target
 
@@ -491,6 +510,8 @@ class CollateGraph:
             self.graph_load = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph_load, pool=self.graph_collate.pool()):
                 self.target.load_(self._staged)
+            if self.augment is not None and self.device_draw:
+                self._copy_inputs(pos, x, y)                  # the warm-up augmented the staged clouds in place
         self.graph_collate.replay()
 
     def load(self):
@@ -519,14 +540,15 @@ class CollatePipeline:
     GATE_MAX_WAIT_US = 3000       # a gated collate goes ahead after this long without a mark (crfconv_gate_wait)
 
     def __init__(self, batches, kernel_size=(16, 16, 16, 16, 16), ratio=(4, 4, 4, 4, 2), generator=None, device_draw=True,
-                 priority=None, gate=False):
+                 priority=None, gate=False, augment=None):
         """gate: the collate graphs START with a bounded device-side wait for a mark of the training stream (``self.mark()``,
         called inside the captured training step where its coarse levels begin -- e.g. PointConvBig.phase_hook): the side stream's
         kernels then fall into the part of the step whose launches leave most of the chip idle instead of beside its fine-level
         kernels (``mark_on('coarse_backward')``: 4.36 -> 4.25 ms per batch at 4 x 40 960 points; the forward's window or the collate as
         two gated graphs, one per window: 4.33 / 4.27).  Off until ``enable_gate(True)``; a collate that sees no mark within
         GATE_MAX_WAIT_US goes ahead, and after three such waits in a row the gate switches itself off (a marking stream that shares
-        the side stream's hardware queue can never run beside the wait)."""
+        the side stream's hardware queue can never run beside the wait).  augment: a transforms.Compose every slot's graph applies
+        to its new clouds (CollateGraph(augment=))."""
         import os
         import warnings
         if (torch.distributed.is_available() and torch.distributed.is_initialized()
@@ -537,7 +559,7 @@ class CollatePipeline:
                           'crfconv_amd before torch initialises the GPU, or export GPU_MAX_HW_QUEUES=8')
         self.batches = list(batches)
         self.gate = torch.zeros(4, dtype=torch.int64, device=self.batches[0].multiscale[0].pos.device) if gate else None
-        self.graphs = [CollateGraph(b, kernel_size, ratio, generator, device_draw=device_draw, slot=k, gate=self.gate)
+        self.graphs = [CollateGraph(b, kernel_size, ratio, generator, device_draw=device_draw, slot=k, gate=self.gate, augment=augment)
                        for k, b in enumerate(self.batches)]
         # the side stream at the LOWEST priority the device offers by default: the collate fills the CUs the training step
         # leaves idle (its many small launches) instead of taking turns with it

@@ -891,6 +891,35 @@ int crfconv_possibility_crop(const float* points, int64_t n, int64_t k, const in
                              float* out_xyz, double* out_center, void* workspace, size_t workspace_bytes,
                              crf_stream_t stream);
 
+/* The reference's training augmentation (trainval.py:26-36), csrc/augment.hip, in place on B crops pos [B, N, 3] float32 and, when
+ * x is not NULL, x [B, N, C] (C = 3: [pos], C = 6: [pos, rgb]), in this order, every step optional:
+ *   rotate   (rotate_axis in {0, 1, 2}; -1 = off) theta ~ U(deg_lo, deg_hi) degrees, pos <- pos @ M with PyG's matrix about the axis
+ *   scale    (scale = 1) pos_i <- pos_i * s_i, s_i ~ U(scale_lo, scale_lo + scale_span), three independent factors
+ *   flip     (bit i of flip_axes) with probability 1/2: pos_i <- max(pos_i) - pos_i, max over the crop after rotate and scale
+ *   noise    (noise = 1) pos <- pos + clamp(sigma N(0, 1), -clip, clip) per point and axis
+ *   drop     (drop = 1) with probability drop_p: x[..., 3:6] <- 0
+ *   x[..., 0:3] <- the augmented pos.
+ * The draws are a function of (seed, *counter, cloud): *counter is a DEVICE word the caller advances, so a captured graph draws new
+ * parameters at every replay.  params_in [B, 8] (or NULL) replaces the per-cloud draws, noise_in [B, N, 3] (or NULL) the noise
+ * before its clamp.  params_out [B, 8] (or NULL) <- (cos, sin, sx, sy, sz, flip mask, keep, c_max of the lowest flipped axis or 0)
+ * as applied.  workspace: crfconv_augment_workspace(B, N) bytes, 16-byte aligned, needed only when flip_axes != 0 (two launches
+ * then; one otherwise). */
+typedef struct crf_augment_spec {
+    int32_t rotate_axis;
+    float deg_lo, deg_hi;
+    int32_t scale;
+    float scale_lo, scale_span;
+    int32_t flip_axes;
+    int32_t noise;
+    float sigma, clip;
+    int32_t drop;
+    float drop_p;
+} crf_augment_spec;
+size_t crfconv_augment_workspace(int64_t B, int64_t N);
+int crfconv_augment(float* pos, float* x, int64_t B, int64_t N, int C, const crf_augment_spec* spec, uint64_t seed,
+                    const int64_t* counter, const float* params_in, const float* noise_in, float* params_out, void* workspace,
+                    size_t workspace_bytes, crf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
