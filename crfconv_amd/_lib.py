@@ -193,6 +193,9 @@ SIGNATURES = {
     'crfconv_possibility_crop': (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'crfconv_augment_workspace': (_sz, [_i64, _i64]),
     'crfconv_augment': (_i, [_vp, _vp, _i64, _i64, _i, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'crfconv_possibility_crop_batch_workspace': (_sz, [_i64, _i64, _i64]),
+    'crfconv_possibility_crop_batch': (_i, [_vp, _i, _i64, _vp, _vp, _i64, _i64, _u64, _vp, _d, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp,
+                                            _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 

@@ -369,7 +369,16 @@ class CollateGraph:
     """
 
     def __init__(self, target, kernel_size=(16, 16, 16, 16, 16), ratio=(4, 4, 4, 4, 2), generator=None, device_draw=True, slot=0, gate=None,
-                 augment=None):
+                 augment=None, sampler=None):
+        # sampler: a sampling.PossibilitySampler the graph draws its OWN input from -- run() / collate() then take no clouds: after the
+        # counter increment and before the augmentation the graph calls sampler.get_batch(B, out=<staging pos / x / y>, seed=self.seed,
+        # counter=self.counter), so sample -> augment -> collate -> load_ is one replay with nothing handed in from the host.  point_idx /
+        # cloud_idx of the crops reach the target (when it has such tensors) in the row order of y.  Several graphs may share one
+        # sampler (the slots of a CollatePipeline): each replay draws from the possibilities the replays before it left, i.e. the crops
+        # follow SUBMISSION order on the device -- the caller orders the replays (one side stream, or events).
+        if sampler is not None and not device_draw:
+            raise ValueError('CollateGraph(sampler=...) draws inside the graph: device_draw=False is not supported with a sampler')
+        self.sampler = sampler
         self.target, self.kernel_size, self.ratio, self.generator = target, tuple(kernel_size), tuple(ratio), generator
         # augment: a transforms.Compose (the reference's train_transform, trainval.py:26-36) applied to the new clouds ahead of the Morton
         # sort and the kNN -- inside the graph with device_draw, eagerly in front of it otherwise.  Keyed on this graph's seed and batch
@@ -407,6 +416,17 @@ class CollateGraph:
         self.graph = None
         self._uploaded = None                    # event after the last upload from the pinned buffers
         self.counter = torch.zeros(1, dtype=torch.int64, device=dev)      # batches collated so far (device_draw: keys the subsets)
+        self.point_idx = self.cloud_idx = None
+        if sampler is not None:
+            B, N = ms[0].pos.shape[:2]
+            if N != sampler.num_points:
+                raise ValueError('CollateGraph(sampler=...): the target holds %d points per cloud, the sampler draws %d' % (N, sampler.num_points))
+            if self.y is not None and self.y.dtype != torch.int64:
+                raise ValueError('CollateGraph(sampler=...): target.y must be int64')
+            if torch.is_tensor(getattr(target, 'point_idx', None)):
+                self.point_idx = torch.empty((B, N), dtype=torch.int64, device=dev)
+            if torch.is_tensor(getattr(target, 'cloud_idx', None)):
+                self.cloud_idx = torch.empty((B, 1), dtype=torch.int64, device=dev)
         if augment is not None and self.x is not None and self.x.shape[-1] not in (3, 6):
             raise ValueError('CollateGraph(augment=...): x must be [pos] or [pos, rgb] (3 or 6 channels), got %d' % self.x.shape[-1])
 
@@ -440,11 +460,15 @@ class CollateGraph:
             from . import _lib
             from .graph import ptr, stream_ptr
             _lib.call('crfconv_add_i64', ptr(self.counter), 1, 1, stream_ptr())       # counter += 1 (a library launch: no framework kernel in the graph)
+            if self.sampler is not None:
+                self.sampler.get_batch(self.pos.shape[0], out=Data(pos=self.pos, x=self.x, y=self.y, point_idx=self.point_idx,
+                                                                   cloud_idx=self.cloud_idx), seed=self.seed, counter=self.counter)
             if self.augment is not None:
                 self.augment.apply_batch(self.pos, self.x, self.seed, self.counter)
             random_subsets_device(self.sizes, [c.numel() for c in self.choices], self.seed, self.counter, self.choices, ranks=self.ranks)
             morton_order(self.pos, out=self.order)
-        return multiscale_compute(self.pos, x=self.x, y=self.y, kernel_size=self.kernel_size, ratio=self.ratio,
+        return multiscale_compute(self.pos, x=self.x, y=self.y, point_idx=self.point_idx, cloud_idx=self.cloud_idx,
+                                  kernel_size=self.kernel_size, ratio=self.ratio,
                                   num_scales=len(self.sizes), choices=self.choices, sort='morton', order=self.order,
                                   ranks=self.ranks if self.device_draw else None)
 
@@ -459,6 +483,12 @@ class CollateGraph:
             self.y.copy_(y)
 
     def _inputs(self, pos, x, y):
+        if self.sampler is not None:
+            if pos is not None or x is not None or y is not None:
+                raise ValueError('CollateGraph(sampler=...) draws its own clouds: run() / collate() take none')
+            return
+        if pos is None:
+            raise ValueError('CollateGraph.run / collate: pos is needed (no sampler)')
         self._copy_inputs(pos, x, y)
         if not self.device_draw:
             if self.augment is not None:          # eagerly, on the batch counter advanced here (the graph advances it with device_draw)
@@ -469,21 +499,24 @@ class CollateGraph:
             self._draw()                          # host torch.randperm + pinned upload; the argsort eagerly in front of the graph
             morton_order(self.pos, out=self.order)
 
-    def run(self, pos, x=None, y=None):
+    def run(self, pos=None, x=None, y=None):
         self._inputs(pos, x, y)
         if self.graph is None:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
                 count = self.counter.clone()
+                drawn = None if self.sampler is None else self.sampler.snapshot()
                 self._work()                                  # warm-up outside the capture (allocator, lazy tables)
                 self.counter.copy_(count)                     # ... which must not consume a batch number (resume: load_state_dict)
+                if drawn is not None:
+                    self.sampler.restore(drawn)               # ... nor crops: possibilities and per-cloud minima are put back
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):
                 self._work()
-            if self.augment is not None and self.device_draw:
+            if self.augment is not None and self.device_draw and self.sampler is None:
                 self._copy_inputs(pos, x, y)                  # the warm-up augmented the staged clouds in place
         self.graph.replay()
         return self.target
@@ -492,7 +525,7 @@ class CollateGraph:
     # NEXT batch (collate(): kNN etc. into this object's own staging tensors) may run on a side stream while the step of the current batch
     # still reads `target`; load() -- the copy into `target` and the in-place refresh of its tables, a fraction of the work -- then runs
     # on the training stream between two steps.  collate() of batch i + 2 must wait for load() of batch i + 1 (it overwrites the staging).
-    def collate(self, pos, x=None, y=None):
+    def collate(self, pos=None, x=None, y=None):
         self._inputs(pos, x, y)
         if getattr(self, 'graph_collate', None) is None:
             cur = torch.cuda.current_stream()
@@ -500,8 +533,11 @@ class CollateGraph:
             side.wait_stream(cur)
             with torch.cuda.stream(side):
                 count = self.counter.clone()
+                drawn = None if self.sampler is None else self.sampler.snapshot()
                 self.target.load_(self._work_collate())       # warm-up of BOTH halves outside the captures
                 self.counter.copy_(count)
+                if drawn is not None:
+                    self.sampler.restore(drawn)
             cur.wait_stream(side)
             torch.cuda.synchronize()
             self.graph_collate = torch.cuda.CUDAGraph()
@@ -510,7 +546,7 @@ class CollateGraph:
             self.graph_load = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph_load, pool=self.graph_collate.pool()):
                 self.target.load_(self._staged)
-            if self.augment is not None and self.device_draw:
+            if self.augment is not None and self.device_draw and self.sampler is None:
                 self._copy_inputs(pos, x, y)                  # the warm-up augmented the staged clouds in place
         self.graph_collate.replay()
 
@@ -540,8 +576,9 @@ class CollatePipeline:
     GATE_MAX_WAIT_US = 3000       # a gated collate goes ahead after this long without a mark (crfconv_gate_wait)
 
     def __init__(self, batches, kernel_size=(16, 16, 16, 16, 16), ratio=(4, 4, 4, 4, 2), generator=None, device_draw=True,
-                 priority=None, gate=False, augment=None):
-        """gate: the collate graphs START with a bounded device-side wait for a mark of the training stream (``self.mark()``,
+                 priority=None, gate=False, augment=None, sampler=None):
+        """sampler: a sampling.PossibilitySampler every slot's graph draws its own clouds from (CollateGraph(sampler=)); submit(slot)
+        then takes no clouds, and the batches follow SUBMISSION order (all slots replay on the one side stream).  gate: the collate graphs START with a bounded device-side wait for a mark of the training stream (``self.mark()``,
         called inside the captured training step where its coarse levels begin -- e.g. PointConvBig.phase_hook): the side stream's
         kernels then fall into the part of the step whose launches leave most of the chip idle instead of beside its fine-level
         kernels (``mark_on('coarse_backward')``: 4.36 -> 4.25 ms per batch at 4 x 40 960 points; the forward's window or the collate as
@@ -559,7 +596,8 @@ class CollatePipeline:
                           'crfconv_amd before torch initialises the GPU, or export GPU_MAX_HW_QUEUES=8')
         self.batches = list(batches)
         self.gate = torch.zeros(4, dtype=torch.int64, device=self.batches[0].multiscale[0].pos.device) if gate else None
-        self.graphs = [CollateGraph(b, kernel_size, ratio, generator, device_draw=device_draw, slot=k, gate=self.gate, augment=augment)
+        self.graphs = [CollateGraph(b, kernel_size, ratio, generator, device_draw=device_draw, slot=k, gate=self.gate, augment=augment,
+                                    sampler=sampler)
                        for k, b in enumerate(self.batches)]
         # the side stream at the LOWEST priority the device offers by default: the collate fills the CUs the training step
         # leaves idle (its many small launches) instead of taking turns with it
@@ -629,7 +667,7 @@ class CollatePipeline:
         for g, s in zip(self.graphs, sd['graphs']):
             g.load_state_dict(s)
 
-    def submit(self, slot, pos, x=None, y=None, wait_current=True):
+    def submit(self, slot, pos=None, x=None, y=None, wait_current=True):
         """Queue the collate of `pos` / `x` / `y` into slot `slot` on the side stream.  wait_current=False: the inputs are
         known to be complete already (e.g. produced long ago, or on another stream the caller has synchronised with), so the
         side stream only waits for the slot's release -- call it AFTER launching the current training step and the host part

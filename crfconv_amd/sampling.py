@@ -21,6 +21,21 @@ def _ws(nbytes, device):
     return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
 
 
+_M64 = 0xFFFFFFFFFFFFFFFF
+_SMP_DOMAIN = 0x8CB92BA72F3D8DD7            # csrc/sampler.hip SMP_DOMAIN
+_SMP_PERM_SLOT = 8
+
+
+def _smp_hash(seed, counter, b, slots):
+    """csrc/sampler.hip smp_hash(seed, counter, b, slot) for an array of slots: uint64."""
+    base = (((int(seed) & _M64) ^ _SMP_DOMAIN) + 0x9E3779B97F4A7C15 * (int(counter) + 1) + int(b) * 0xC2B2AE3D27D4EB4F) & _M64
+    with np.errstate(over='ignore'):
+        z = np.uint64(base) + np.asarray(slots).astype(np.uint64) * np.uint64(0xD1B54A32D192ED03)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return z ^ (z >> np.uint64(31))
+
+
 class PossibilitySampler:
     """points: list of float32 [n_c, 3] CUDA tensors (the sub-sampled clouds); rgb / labels: matching lists or None.
 
@@ -63,6 +78,9 @@ class PossibilitySampler:
         for c in range(len(self.points)):
             self._refresh_min(c)
         self._crop_ws = {}
+        self._batch = None                                  # get_batch's device tables, built at its first call
+        self._seed = None                                   # get_batch's own seed: ONE draw on the generator, at first need
+        self._counter = torch.zeros(1, dtype=torch.int64, device=self.device)      # get_batch calls on the own counter so far
 
     def _refresh_min(self, c):
         p = self.possibility[c]
@@ -107,6 +125,157 @@ class PossibilitySampler:
         out.center = center
         out.cloud = c                                        # the same as a host int (VoteAccumulator.update takes it without a device read)
         return out
+
+    # ---- B crops per call, every decision on the device (csrc/sampler.hip)
+    @property
+    def seed(self):
+        """Seed of get_batch's draws when the caller passes none: one draw on ``generator`` (on data._private_generator() without
+        one: the global generator never advances), taken at first need so that get_random's sequence is untouched."""
+        if self._seed is None:
+            from .data import _private_generator
+            g = self.generator if self.generator is not None else _private_generator()
+            self._seed = int(torch.randint(0, 2 ** 62, (1,), generator=g, dtype=torch.int64, device=g.device).item())
+        return self._seed
+
+    def _batch_tables(self):
+        if self._batch is not None:
+            return self._batch
+        k = self.num_points
+        for c, p in enumerate(self.points):
+            if p.shape[0] < k:
+                raise ValueError('PossibilitySampler.get_batch: cloud %d holds %d points, fewer than num_points = %d (the batch '
+                                 'form has fixed shapes)' % (c, p.shape[0], k))
+        rgb = None if self.rgb is None else [to_device(torch.as_tensor(r), self.device).float().contiguous() for r in self.rgb]
+        labels = None if self.labels is None else [lab.long().contiguous() for lab in self.labels]
+        rows = []
+        for c, p in enumerate(self.points):
+            rows.append([p.data_ptr(), self.possibility[c].data_ptr(),
+                         0 if self.point_weight is None else self.point_weight[c].data_ptr(),
+                         0 if labels is None else labels[c].data_ptr(), 0 if rgb is None else rgb[c].data_ptr(), p.shape[0]])
+        table = to_device(torch.tensor(rows, dtype=torch.int64), self.device)      # crf_cloud_desc [n_clouds]: six 8-byte words each
+        self._batch = {'table': table, 'rgb': rgb, 'labels': labels, 'n_max': max(p.shape[0] for p in self.points), 'ws': {},
+                       'keep': [t.data_ptr() for t in self.possibility]}
+        return self._batch
+
+    @staticmethod
+    def draws(seed, counter, B, k=0, noise_scale=1.0):
+        """Host twin (numpy) of what get_batch draws at (seed, counter value the call reads): dict of u [B, 3, 2] (the 53-bit uniforms in
+        (0, 1]), normal [B, 3] (Box-Muller, float64), noise [B, 3] = normal * noise_scale, and perm [B, k] int64 (stable arg-sort
+        of the row hashes).  The uniforms and the permutations are the device's exactly; the normals to a few ulp."""
+        u = np.empty((B, 3, 2))
+        perm = np.empty((B, int(k)), np.int64)
+        for b in range(B):
+            h = _smp_hash(seed, counter, b, np.arange(6))
+            u[b] = (((h >> np.uint64(11)) + np.uint64(1)).astype(np.float64) * 2.0 ** -53).reshape(3, 2)
+            perm[b] = np.argsort(_smp_hash(seed, counter, b, _SMP_PERM_SLOT + np.arange(int(k), dtype=np.uint64)), kind='stable')
+        normal = np.sqrt(-2.0 * np.log(u[..., 0])) * np.cos(2.0 * np.pi * u[..., 1])
+        return {'u': u, 'normal': normal, 'noise': normal * float(noise_scale), 'perm': perm}
+
+    def get_batch(self, B, out=None, noise=None, perm=None, seed=None, counter=None, return_draws=False):
+        """B crops as ONE library call (47 launches per crop, no host read, capturable in a hipGraph): what B consecutive
+        ``get_random`` calls give -- crop b + 1 sees the possibilities crop b updated, the cloud is chosen per crop on the
+        device -- stacked into ``Data(pos [B, k, 3], x [B, k, C] or None, y [B, k], point_idx [B, k], cloud_idx [B, 1],
+        center [B, 3])``, bit for bit for the same jitter and shuffle.
+
+        out: a Data whose tensors (pos, and optionally x / y / point_idx / cloud_idx / center) receive the batch -- static outputs
+        for a captured graph; x has 3 ([pos]) or 6 ([pos, rgb]) channels.  Without `out`, x = [pos, rgb] when the sampler has colours.
+        noise float64 [B, 3] / perm int64 [B, k] (``False`` = identity) override the draws.  The draws are keyed on
+        (seed, counter): by default the sampler's own ``seed`` and device counter, which the call advances by one BEFORE drawing;
+        an explicit `counter` (one-element int64 device tensor) is read as it is and advanced by its owner (a CollateGraph).
+        The seed is a launch scalar: a captured call keeps the seed it was captured with.  return_draws: also returns
+        (noise [B, 3], perm [B, k]) as used, on the device.  Every cloud must hold at least num_points points."""
+        tb = self._batch_tables()
+        if tb['keep'] != [t.data_ptr() for t in self.possibility]:
+            raise _lib.CrfConvError('PossibilitySampler: the possibility tensors were replaced after the first get_batch '
+                                    '(load_state_dict copies into them)')
+        B, k, dev = int(B), self.num_points, self.device
+        if B <= 0:
+            raise ValueError('get_batch: B = %d' % B)
+
+        def given(name, shape, dtype):
+            t = None if out is None else getattr(out, name, None)
+            if t is None:
+                return None
+            if not (t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape):
+                raise ValueError('get_batch(out=): %s must be a contiguous %s device tensor of shape %s' % (name, dtype, shape))
+            return t
+        x = None if out is None else getattr(out, 'x', None)
+        if x is not None:
+            if x.dim() != 3 or x.shape[-1] not in (3, 6):
+                raise ValueError('get_batch(out=): x must be [B, k, 3] or [B, k, 6]')
+            if x.shape[-1] == 6 and tb['rgb'] is None:
+                raise ValueError('get_batch(out=): x has six channels but the sampler holds no colours')
+            x = given('x', (B, k, x.shape[-1]), torch.float32)
+        elif out is None and tb['rgb'] is not None:
+            x = torch.empty((B, k, 6), dtype=torch.float32, device=dev)
+        pos = given('pos', (B, k, 3), torch.float32)
+        if pos is None:
+            pos = torch.empty((B, k, 3), dtype=torch.float32, device=dev)
+        res = {'pos': pos, 'x': x}
+        for name, shape, dtype in (('y', (B, k), torch.int64), ('point_idx', (B, k), torch.int64), ('cloud_idx', (B, 1), torch.int64),
+                                   ('center', (B, 3), torch.float64)):
+            t = given(name, shape, dtype)
+            res[name] = t if t is not None else torch.empty(shape, dtype=dtype, device=dev)
+        if noise is not None:
+            noise = to_device(torch.as_tensor(noise, dtype=torch.float64).contiguous(), dev)
+            if tuple(noise.shape) != (B, 3):
+                raise ValueError('get_batch: noise must be [B, 3]')
+        identity = perm is False
+        if perm is not None and not identity:
+            perm = to_device(torch.as_tensor(perm, dtype=torch.int64).contiguous(), dev)
+            if tuple(perm.shape) != (B, k):
+                raise ValueError('get_batch: perm must be [B, k]')
+        else:
+            perm = None
+        if counter is None:
+            counter = self._counter
+            _lib.call('crfconv_add_i64', ptr(counter), 1, 1, stream_ptr())
+        elif not (torch.is_tensor(counter) and counter.is_cuda and counter.dtype == torch.int64 and counter.numel() >= 1):
+            raise ValueError('get_batch: counter must be an int64 device tensor')
+        seed = self.seed if seed is None else int(seed)
+        noise_out = perm_out = None
+        if return_draws:
+            noise_out = torch.empty((B, 3), dtype=torch.float64, device=dev)
+            perm_out = torch.arange(k, dtype=torch.int64, device=dev).repeat(B, 1) if identity \
+                else torch.empty((B, k), dtype=torch.int64, device=dev)
+        if B not in tb['ws']:
+            tb['ws'][B] = _ws(_lib.load().crfconv_possibility_crop_batch_workspace(tb['n_max'], k, B), dev)
+        ws = tb['ws'][B]
+        _lib.call('crfconv_possibility_crop_batch', ptr(tb['table']), len(self.points), tb['n_max'], ptr(self._minv), ptr(self._mini),
+                  k, B, seed & _M64, ptr(counter), self.noise_scale, ptr(noise), ptr(perm), 1 if identity else 0, ptr(pos), ptr(x),
+                  0 if x is None else x.shape[-1], ptr(res['y']), ptr(res['point_idx']), ptr(res['cloud_idx']), ptr(res['center']),
+                  ptr(noise_out), None if identity else ptr(perm_out), ptr(ws), ws.numel(), stream_ptr())
+        for t in list(res.values()) + list(self.possibility) + [self._minv, self._mini]:      # written by library kernels
+            if t is not None:
+                torch.autograd.graph.increment_version(t)
+        data = Data(pos=pos, x=x, y=res['y'], point_idx=res['point_idx'], cloud_idx=res['cloud_idx'])
+        data.center = res['center']
+        return (data, noise_out, perm_out) if return_draws else data
+
+    def snapshot(self):
+        """Device copies of everything a get_batch call changes (possibilities, per-cloud minima, the own counter)."""
+        return ([p.clone() for p in self.possibility], self._minv.clone(), self._mini.clone(), self._counter.clone())
+
+    def restore(self, snap):
+        """Puts a ``snapshot()`` back, in place (a graph's warm-up pass must not consume crops)."""
+        for p, q in zip(self.possibility, snap[0]):
+            p.copy_(q)
+        self._minv.copy_(snap[1])
+        self._mini.copy_(snap[2])
+        self._counter.copy_(snap[3])
+
+    def state_dict(self):
+        """Seed, counter and possibility tables: what a checkpoint needs to continue the crop sequence."""
+        return {'seed': int(self.seed), 'counter': int(self._counter.item()), 'possibility': [p.cpu().clone() for p in self.possibility]}
+
+    def load_state_dict(self, sd):
+        if len(sd['possibility']) != len(self.possibility):
+            raise ValueError('PossibilitySampler.load_state_dict: %d clouds in the checkpoint, %d here' % (len(sd['possibility']), len(self.possibility)))
+        self._seed = int(sd['seed'])
+        self._counter.fill_(int(sd['counter']))
+        for c, (p, q) in enumerate(zip(self.possibility, sd['possibility'])):
+            p.copy_(torch.as_tensor(q, dtype=torch.float64))            # in place: the device table points at these tensors
+            self._refresh_min(c)
 
 
 class VoteAccumulator:

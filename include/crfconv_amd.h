@@ -920,6 +920,37 @@ int crfconv_augment(float* pos, float* x, int64_t B, int64_t N, int C, const crf
                     const int64_t* counter, const float* params_in, const float* noise_in, float* params_out, void* workspace,
                     size_t workspace_bytes, crf_stream_t stream);
 
+/* B possibility crops in one call, every decision on the device (csrc/sampler.hip; B consecutive draws of
+ * semantic3d_dataset.py:423-460): for b = 0 .. B-1 in stream order
+ *   cloud  = arg-min of min_value[0 .. n_clouds) (first index on ties), seed point = min_index[cloud]
+ *   jitter = noise_in[b] (float64 [B, 3]) or noise_scale x three float64 Box-Muller normals of 53-bit uniforms in (0, 1] of a
+ *            splitmix64 hash of (seed, *counter, b, slot); centre = float64(points[seed point]) + jitter
+ *   crop   = the k points with the smallest (float64 squared distance, point id), found by a radix select + a sort of k pairs
+ *   the possibility update, distances and centred coordinates of crfconv_possibility_crop, bit for bit
+ *   min_value / min_index [cloud] <- the cloud's new minimum possibility
+ * Row t of crop b shows crop element perm_b[t]: perm_in int64 [B, k], or the identity (identity_perm != 0), or the stable arg-sort
+ * over t of the hashes of slot 8 + t.  *counter is a DEVICE word the call reads (never writes): advance it between calls and a
+ * captured graph draws new crops at every replay.  counter may be NULL when nothing is drawn.
+ * clouds: DEVICE array of n_clouds descriptors; every cloud must hold at least k points (the caller checks; n_max = the largest n).
+ * Outputs (all but out_pos may be NULL): out_pos float32 [B, k, 3] (x, y centred, z raw); out_x float32 [B, k, x_channels],
+ * x_channels 3 = [pos] or 6 = [pos, rgb] (zeros without rgb); out_y int64 [B, k] (zeros without labels); out_point_idx int64
+ * [B, k]; out_cloud_idx int64 [B]; out_center float64 [B, 3]; noise_out float64 [B, 3] / perm_out int64 [B, k]: the draws used.
+ * No host synchronisation, no scratch memory: capturable in a hipGraph.  47 launches per crop + 39 per call for the shuffles. */
+typedef struct crf_cloud_desc {
+    const float* points;          /* [n, 3] */
+    double* possibility;          /* [n] */
+    const double* point_weight;   /* [n] or NULL (weight 1: the test split) */
+    const int64_t* labels;        /* [n] or NULL */
+    const float* rgb;             /* [n, 3] or NULL */
+    int64_t n;
+} crf_cloud_desc;
+size_t crfconv_possibility_crop_batch_workspace(int64_t n_max, int64_t k, int64_t B);
+int crfconv_possibility_crop_batch(const crf_cloud_desc* clouds, int n_clouds, int64_t n_max, double* min_value, int64_t* min_index,
+                                   int64_t k, int64_t B, uint64_t seed, const int64_t* counter, double noise_scale,
+                                   const double* noise_in, const int64_t* perm_in, int identity_perm, float* out_pos, float* out_x,
+                                   int x_channels, int64_t* out_y, int64_t* out_point_idx, int64_t* out_cloud_idx, double* out_center,
+                                   double* noise_out, int64_t* perm_out, void* workspace, size_t workspace_bytes, crf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
