@@ -57,6 +57,24 @@ __global__ __launch_bounds__(EV_BLOCK) void confusion_kernel(const int64_t* __re
     }
 }
 
+// one row of the update: dst <- smooth * dst + (1 - smooth) * prob, prob = probs_row or soft-max of logits_row
+__device__ __forceinline__ void vote_row(float* __restrict__ dst, const float* __restrict__ probs_row, const float* __restrict__ logits_row,
+                                         int C, float smooth, float one_minus) {
+    if (logits_row) {
+        const float* row = logits_row;
+        float mx = row[0];
+        for (int c = 1; c < C; ++c) mx = fmaxf(mx, row[c]);
+        float se = 0.f;
+        for (int c = 0; c < C; ++c) se += expf(row[c] - mx);
+        const float inv = 1.0f / se;
+        for (int c = 0; c < C; ++c)
+            dst[c] = add_rn(mul_rn(smooth, dst[c]), mul_rn(one_minus, expf(row[c] - mx) * inv));
+    } else {
+        const float* row = probs_row;
+        for (int c = 0; c < C; ++c) dst[c] = add_rn(mul_rn(smooth, dst[c]), mul_rn(one_minus, row[c]));
+    }
+}
+
 // test_probs[p_idx[r]] = smooth * test_probs[p_idx[r]] + (1 - smooth) * prob[r]   (float32, products and sum each
 // rounded once -- numpy evaluates the expression of trainval.py:188 array-op by array-op, so no fused multiply-add).
 // prob = probs[r] or soft-max of logits[r].  Rows of one call must be distinct points (a crop is a kNN result).
@@ -70,20 +88,39 @@ __global__ __launch_bounds__(EV_BLOCK) void vote_kernel(const float* __restrict_
     const int64_t p = point_idx[r];
     if (p < 0 || p >= n_cloud) { atomicAdd(bad, 1); return; }
     if (visits != nullptr) visits[p] += 1;               // (rows of one call are distinct points: no two threads share p)
-    float* dst = test_probs + p * C;
-    if (logits) {
-        const float* row = logits + r * C;
-        float mx = row[0];
-        for (int c = 1; c < C; ++c) mx = fmaxf(mx, row[c]);
-        float se = 0.f;
-        for (int c = 0; c < C; ++c) se += expf(row[c] - mx);
-        const float inv = 1.0f / se;
-        for (int c = 0; c < C; ++c)
-            dst[c] = add_rn(mul_rn(smooth, dst[c]), mul_rn(one_minus, expf(row[c] - mx) * inv));
-    } else {
-        const float* row = probs + r * C;
-        for (int c = 0; c < C; ++c) dst[c] = add_rn(mul_rn(smooth, dst[c]), mul_rn(one_minus, row[c]));
-    }
+    vote_row(test_probs + p * C, probs ? probs + r * C : nullptr, logits ? logits + r * C : nullptr, C, smooth, one_minus);
+}
+
+// The same for rows that may name a point more than once (a padded S3DIS crop, s3dis_dataset.py:375-377), with numpy's meaning of
+// a[idx] = s * a[idx] + (1 - s) * p (trainval.py:256-262): every right-hand side is formed from the OLD row and of several rows naming
+// one point the LAST is stored.  Three passes over the rows, deterministic: (1) integer atomic max of the row number into last[p]
+// (-1 everywhere between calls), (2) only row last[p] updates point p and its visit count, (3) last[p] <- -1 again.
+__global__ __launch_bounds__(EV_BLOCK) void vote_last_row_kernel(const int64_t* __restrict__ point_idx, int64_t n_rows, int64_t n_cloud,
+                                                                 int32_t* __restrict__ last, int32_t* __restrict__ bad) {
+    const int64_t r = (int64_t)blockIdx.x * EV_BLOCK + threadIdx.x;
+    if (r >= n_rows) return;
+    const int64_t p = point_idx[r];
+    if (p < 0 || p >= n_cloud) { atomicAdd(bad, 1); return; }
+    atomicMax(&last[p], (int32_t)r);
+}
+__global__ __launch_bounds__(EV_BLOCK) void vote_repeated_kernel(const float* __restrict__ probs, const float* __restrict__ logits,
+                                                                 const int64_t* __restrict__ point_idx, int64_t n_rows, int C,
+                                                                 float smooth, float one_minus, float* __restrict__ test_probs,
+                                                                 int64_t n_cloud, const int32_t* __restrict__ last,
+                                                                 int32_t* __restrict__ visits) {
+    const int64_t r = (int64_t)blockIdx.x * EV_BLOCK + threadIdx.x;
+    if (r >= n_rows) return;
+    const int64_t p = point_idx[r];
+    if (p < 0 || p >= n_cloud || last[p] != (int32_t)r) return;
+    if (visits != nullptr) visits[p] += 1;               // one row per point passes the test above
+    vote_row(test_probs + p * C, probs ? probs + r * C : nullptr, logits ? logits + r * C : nullptr, C, smooth, one_minus);
+}
+__global__ __launch_bounds__(EV_BLOCK) void vote_last_row_clear_kernel(const int64_t* __restrict__ point_idx, int64_t n_rows,
+                                                                       int64_t n_cloud, int32_t* __restrict__ last) {
+    const int64_t r = (int64_t)blockIdx.x * EV_BLOCK + threadIdx.x;
+    if (r >= n_rows) return;
+    const int64_t p = point_idx[r];
+    if (p >= 0 && p < n_cloud) last[p] = -1;             // (rows naming one point store the same value)
 }
 
 // preds[i] = argmax_c test_probs[proj_idx[i], c] + label_offset   (trainval.py:200-203)
@@ -304,6 +341,26 @@ static int vote_accumulate_impl(const float* probs, const float* logits, const i
     const float one_minus = (float)(1.0 - smooth);
     hipLaunchKernelGGL(vote_kernel, dim3((unsigned)cdiv(n_rows, EV_BLOCK)), dim3(EV_BLOCK), 0, as_stream(stream), probs,
                        logits, point_idx, n_rows, C, (float)smooth, one_minus, test_probs, n_cloud, bad_count, visits);
+    CRF_LAUNCH_CHECK();
+    return CRF_OK;
+}
+
+extern "C" int crfconv_vote_update_repeated(const float* probs, const float* logits, const int64_t* point_idx, int64_t n_rows, int C,
+                                            double smooth, float* test_probs, int64_t n_cloud, int32_t* bad_count, int32_t* visits,
+                                            int32_t* last_row, crf_stream_t stream) {
+    CRF_REQUIRE((probs || logits) && point_idx && test_probs && bad_count && last_row, CRF_ERR_ARG, "null pointer");
+    CRF_REQUIRE(C >= 1 && n_cloud > 0 && n_rows < ((int64_t)1 << 31), CRF_ERR_ARG, "C=%d n_cloud=%lld n_rows=%lld invalid", C,
+                (long long)n_cloud, (long long)n_rows);
+    if (n_rows <= 0) return CRF_OK;
+    const float one_minus = (float)(1.0 - smooth);          // as vote_accumulate_impl
+    const dim3 grid((unsigned)cdiv(n_rows, EV_BLOCK)), blk(EV_BLOCK);
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(vote_last_row_kernel, grid, blk, 0, st, point_idx, n_rows, n_cloud, last_row, bad_count);
+    CRF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(vote_repeated_kernel, grid, blk, 0, st, probs, logits, point_idx, n_rows, C, (float)smooth, one_minus, test_probs,
+                       n_cloud, (const int32_t*)last_row, visits);
+    CRF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(vote_last_row_clear_kernel, grid, blk, 0, st, point_idx, n_rows, n_cloud, last_row);
     CRF_LAUNCH_CHECK();
     return CRF_OK;
 }

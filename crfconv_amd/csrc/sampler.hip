@@ -27,6 +27,9 @@
 //   once per call: the B shuffles.  perm_b = stable arg-sort over t of smp_hash(seed, counter, b, 8 + t): ONE sort of the B k hashes
 //   (values b k + t) followed by one stable pass on b -- the crops do not enter, so this is not repeated per crop.
 //
+//   S3DIS form (datasets/s3dis_dataset.py:343-379, crfconv_possibility_crop_batch_s3dis): the same select and sort for kc = min(n, k)
+//   rows -- a device value; rows kc .. k of the sort's input are all-ones sentinels -- with its own distance / update kernels and the
+//   padding of a short crop to k rows (further down).
 // Everything is integer counting or singly rounded arithmetic in a fixed order: deterministic, no floating-point atomics.
 #include <cmath>
 
@@ -60,6 +63,7 @@ struct SbCrop {                   // one crop's device-side decisions; lives in 
     double center[3];
     long long n;
     int cloud, pad;
+    long long kc;                 // rows of this crop: k, or min(n, k) in the S3DIS form (a small room is taken whole)
 };
 struct SbMin {
     double v;
@@ -84,6 +88,7 @@ __device__ __forceinline__ unsigned long long sb_key(const float* __restrict__ p
     return (unsigned long long)__double_as_longlong(d);
 }
 
+template <bool S3DIS>
 __global__ __launch_bounds__(SB_NT) void sb_choose_kernel(const crf_cloud_desc* __restrict__ clouds, int n_clouds,
                                                           const double* __restrict__ minv, const int64_t* __restrict__ mini,
                                                           unsigned long long seed, const int64_t* __restrict__ counter, int b, long long k,
@@ -119,7 +124,9 @@ __global__ __launch_bounds__(SB_NT) void sb_choose_kernel(const crf_cloud_desc* 
     if (lane == 0) {
         st->cloud = c;
         st->n = cd.n;
-        st->sel[0] = SbSel{0ull, k};
+        const long long kc = S3DIS && cd.n < k ? cd.n : k;            // s3dis_dataset.py:352-355
+        st->kc = kc;
+        st->sel[0] = SbSel{0ull, kc};
         if (out_cloud != nullptr) out_cloud[b] = c;
     }
 }
@@ -222,12 +229,21 @@ __global__ __launch_bounds__(SB_NT) void sb_count_kernel(const crf_cloud_desc* _
     }
 }
 
+template <bool S3DIS>
 __global__ __launch_bounds__(SB_NT) void sb_scatter_kernel(const crf_cloud_desc* __restrict__ clouds, const SbCrop* __restrict__ st,
                                                            const int32_t* __restrict__ cnt, long long nb, long long k,
                                                            unsigned long long* __restrict__ keys_out, uint32_t* __restrict__ vals_out) {
     __shared__ long long s_b[SB_NT / WAVE][2];
     __shared__ int s_c[SB_NT / WAVE][2];
     const long long n = st->n, lo = (long long)blockIdx.x * SB_TILE;
+    if constexpr (S3DIS) {                                             // rows kc .. k of the sort's input: sentinels that sort last
+        const long long kc = st->kc;
+        for (long long i = kc + (long long)blockIdx.x * SB_NT + threadIdx.x; i < k; i += (long long)gridDim.x * SB_NT) {
+            keys_out[i] = ~0ull;
+            vals_out[i] = 0xFFFFFFFFu;
+        }
+        k = kc;
+    }
     if (lo >= n) return;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const unsigned long long kth = st->sel[8].prefix;
@@ -400,12 +416,166 @@ __global__ __launch_bounds__(SB_NT) void sb_perm_final_kernel(const uint32_t* __
     if (perm_out != nullptr) perm_out[i] = v;
 }
 
+// ---- the S3DIS form (datasets/s3dis_dataset.py:343-379): all three axes centred, float32 distances of the float32 centred
+// coordinates, weight 1, a room smaller than k taken whole (kc = n rows) and padded to k rows by `choice`.
+constexpr unsigned long long SMP_CHOICE_SLOT = 1ull << 32;             // slot (j + 1) 2^32 + t: padding key of element t of block j
+
+// np.sum(np.square(query_xyz.astype(np.float32)), axis=1) (:363): x x + y y + z z in float32, every operation rounded once
+__global__ __launch_bounds__(SB_NT) void sb_dist_s3dis_kernel(const crf_cloud_desc* __restrict__ clouds, const SbCrop* __restrict__ st,
+                                                              const uint32_t* __restrict__ sel, long long k, float* __restrict__ dist,
+                                                              float* __restrict__ pmax) {
+    __shared__ float s_red[SB_NT / WAVE];
+    const long long t = (long long)blockIdx.x * SB_NT + threadIdx.x;
+    const float* __restrict__ points = clouds[st->cloud].points;
+    float d = 0.f;
+    if (t < k) {
+        const long long i = sel[t];
+        if (t < st->kc && i < st->n) {
+            const float px = (float)((double)points[3 * i] - st->center[0]), py = (float)((double)points[3 * i + 1] - st->center[1]),
+                        pz = (float)((double)points[3 * i + 2] - st->center[2]);
+            d = add_rn(add_rn(mul_rn(px, px), mul_rn(py, py)), mul_rn(pz, pz));
+        }
+        dist[t] = d;
+    }
+    float mx = d;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, WAVE));
+    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < SB_NT / WAVE; ++w) mx = fmaxf(mx, s_red[w]);
+        pmax[blockIdx.x] = mx;
+    }
+}
+
+// possibility[query_idx] += (1 - d / d_max)^2 over the kc DISTINCT rows of the crop (:364-365), then row t of the batch = row
+// choice[t] of the shuffled crop = selected element perm[choice[t]] (:357, :375-377).  kc == k: choice is the identity.
+__global__ __launch_bounds__(SB_NT) void sb_update_s3dis_kernel(const crf_cloud_desc* __restrict__ clouds, const SbCrop* __restrict__ st,
+                                                                const uint32_t* __restrict__ sel, const int64_t* __restrict__ perm,
+                                                                const int64_t* __restrict__ perm_compact,
+                                                                const int64_t* __restrict__ choice, long long k,
+                                                                const float* __restrict__ dist, const float* __restrict__ pmax, int nblk,
+                                                                float* __restrict__ out_pos, float* __restrict__ out_x, int xc,
+                                                                int64_t* __restrict__ out_y, int64_t* __restrict__ out_idx) {
+    const long long t = (long long)blockIdx.x * SB_NT + threadIdx.x;
+    if (t >= k) return;
+    const crf_cloud_desc cd = clouds[st->cloud];
+    const long long kc = st->kc;
+    if (t < kc) {
+        float dmax = pmax[0];
+        for (int b = 1; b < nblk; ++b) dmax = fmaxf(dmax, pmax[b]);
+        const long long j = sel[t];
+        if (j < cd.n) {
+            const float u = sub_rn(1.0f, __fdiv_rn(dist[t], dmax));
+            cd.possibility[j] += (double)mul_rn(u, u);              // the kc selected rows are distinct points
+        }
+    }
+    long long s = t;
+    if (kc < k) {
+        if (choice == nullptr) return;
+        s = choice[t];
+    }
+    if (s < 0 || s >= kc) return;
+    if (kc < k && perm_compact != nullptr) perm = perm_compact;     // the device's own shuffle, restricted to kc rows
+    const long long src = perm ? perm[s] : s;
+    if (src < 0 || src >= kc) return;
+    const long long i = sel[src];
+    if (i >= cd.n) return;
+    const float px = (float)((double)cd.points[3 * i + 0] - st->center[0]);
+    const float py = (float)((double)cd.points[3 * i + 1] - st->center[1]);
+    const float pz = (float)((double)cd.points[3 * i + 2] - st->center[2]);
+    out_pos[3 * t + 0] = px;
+    out_pos[3 * t + 1] = py;
+    out_pos[3 * t + 2] = pz;
+    if (out_x != nullptr) {
+        float* xr = out_x + (size_t)t * xc;
+        xr[0] = px; xr[1] = py; xr[2] = pz;
+        if (xc == 6) {
+            xr[3] = cd.rgb ? cd.rgb[3 * i + 0] : 0.f;
+            xr[4] = cd.rgb ? cd.rgb[3 * i + 1] : 0.f;
+            xr[5] = cd.rgb ? cd.rgb[3 * i + 2] : 0.f;
+        }
+    }
+    if (out_y != nullptr) out_y[t] = cd.labels ? cd.labels[i] : 0;
+    if (out_idx != nullptr) out_idx[t] = i;
+}
+
+// The shuffle of a crop of kc < k rows: the stable ranking of the first kc hashes of row b = the entries below kc of the row's full
+// arg-sort, in their order.  One workgroup, order-preserving compaction; perm_out (or NULL) <- the kc entries, then -1.
+__global__ __launch_bounds__(SB_NT) void sb_perm_compact_kernel(const SbCrop* __restrict__ st, const int64_t* __restrict__ full, long long k,
+                                                                int64_t* __restrict__ compact, int64_t* __restrict__ perm_out) {
+    __shared__ int s_c[SB_NT / WAVE];
+    const long long kc = st->kc;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    if (kc >= k) {
+        if (perm_out != nullptr)
+            for (long long i = t; i < k; i += SB_NT) perm_out[i] = full[i];
+        return;
+    }
+    long long base = 0;
+    for (long long lo = 0; lo < k; lo += SB_NT) {
+        const long long i = lo + t;
+        const long long v = i < k ? full[i] : k;
+        const bool keep = v < kc;
+        const unsigned long long m = __ballot(keep);
+        if (lane == 0) s_c[wave] = __popcll(m);
+        __syncthreads();
+        long long slot = base;
+        int total = 0;
+#pragma unroll
+        for (int w = 0; w < SB_NT / WAVE; ++w) {
+            if (w < wave) slot += s_c[w];
+            total += s_c[w];
+        }
+        if (keep) {
+            slot += __popcll(m & ((1ull << lane) - 1ull));
+            compact[slot] = v;
+            if (perm_out != nullptr) perm_out[slot] = v;
+        }
+        base += total;
+        __syncthreads();
+    }
+    if (perm_out != nullptr)
+        for (long long i = kc + t; i < k; i += SB_NT) perm_out[i] = -1;
+}
+
+// Padding of a crop of kc < k rows (FixedPoints(k, replace=False, allow_duplicates=True), :375-377): ceil(k / kc) independent
+// permutations of range(kc) laid end to end, the first k entries.  Permutation j = stable arg-sort over t of the upper 32 bits of
+// smp_hash(seed, counter, b, (j + 1) 2^32 + t): ONE sort of at most k + kc - 1 < 2 k pairs keyed (j, hash); grid of 2 k elements.
+__global__ __launch_bounds__(SB_NT) void sb_choice_keys_kernel(const SbCrop* __restrict__ st, unsigned long long seed,
+                                                               const int64_t* __restrict__ counter, int b, long long k,
+                                                               unsigned long long* __restrict__ keys, uint32_t* __restrict__ vals) {
+    const long long e = (long long)blockIdx.x * SB_NT + threadIdx.x;
+    if (e >= 2 * k) return;
+    const long long kc = st->kc;
+    unsigned long long key = ~0ull;
+    if (kc < k && kc > 0) {
+        const long long nblocks = (k + kc - 1) / kc;
+        if (e < nblocks * kc) {
+            const unsigned long long j = (unsigned long long)(e / kc), t = (unsigned long long)(e % kc);
+            key = (j << 32) | (smp_hash(seed, (unsigned long long)*counter, (unsigned long long)b, (j + 1ull) * SMP_CHOICE_SLOT + t) >> 32);
+        }
+    }
+    keys[e] = key;
+    vals[e] = (uint32_t)e;
+}
+__global__ __launch_bounds__(SB_NT) void sb_choice_final_kernel(const SbCrop* __restrict__ st, const uint32_t* __restrict__ vals, long long k,
+                                                                int64_t* __restrict__ choice, int64_t* __restrict__ choice_out) {
+    const long long t = (long long)blockIdx.x * SB_NT + threadIdx.x;
+    if (t >= k) return;
+    const long long kc = st->kc;
+    const int64_t v = kc < k && kc > 0 && vals != nullptr ? (int64_t)vals[t] - (t / kc) * kc : t;      // sorted slot t lies in block t / kc
+    choice[t] = v;
+    if (choice_out != nullptr) choice_out[t] = v;
+}
+
 static size_t sb_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct SbLayout {
     size_t crop, hist, cnt, keys_a, keys_b, vals_a, vals_b, dist, pmax, pv, pi, sort, pkeys_a, pkeys_b, pvals_a, pvals_b, perm, psort, total;
+    size_t compact, choice, ckeys_a, ckeys_b, cvals_a, cvals_b, csort;      // the S3DIS form only
 };
-static SbLayout sb_layout(int64_t n_max, int64_t k, int64_t B) {
+static SbLayout sb_layout(int64_t n_max, int64_t k, int64_t B, bool s3dis = false) {
     SbLayout l;
     size_t o = 0;
     auto take = [&o](size_t bytes) { const size_t at = o; o += sb_align(bytes); return at; };
@@ -428,6 +598,16 @@ static SbLayout sb_layout(int64_t n_max, int64_t k, int64_t B) {
     l.pvals_b = take(4 * bk);
     l.perm = take(8 * bk);
     l.psort = take(rsort_workspace(B * k));
+    l.compact = l.choice = l.ckeys_a = l.ckeys_b = l.cvals_a = l.cvals_b = l.csort = 0;
+    if (s3dis) {
+        l.compact = take(8 * kk);
+        l.choice = take(8 * kk);
+        l.ckeys_a = take(16 * kk);
+        l.ckeys_b = take(16 * kk);
+        l.cvals_a = take(8 * kk);
+        l.cvals_b = take(8 * kk);
+        l.csort = take(rsort_workspace(2 * k));
+    }
     l.total = o + 256;                                                 // (room to align the caller's pointer)
     return l;
 }
@@ -436,30 +616,28 @@ static SbLayout sb_layout(int64_t n_max, int64_t k, int64_t B) {
 
 using namespace crf;
 
-extern "C" size_t crfconv_possibility_crop_batch_workspace(int64_t n_max, int64_t k, int64_t B) {
-    if (n_max <= 0 || k <= 0 || B <= 0 || k > n_max) return 0;
-    return sb_layout(n_max, k, B).total;
-}
-
-extern "C" int crfconv_possibility_crop_batch(const crf_cloud_desc* clouds, int n_clouds, int64_t n_max, double* min_value,
-                                              int64_t* min_index, int64_t k, int64_t B, uint64_t seed, const int64_t* counter,
-                                              double noise_scale, const double* noise_in, const int64_t* perm_in, int identity_perm,
-                                              float* out_pos, float* out_x, int x_channels, int64_t* out_y, int64_t* out_point_idx,
-                                              int64_t* out_cloud_idx, double* out_center, double* noise_out, int64_t* perm_out,
-                                              void* workspace, size_t workspace_bytes, crf_stream_t stream) {
+// Both forms.  s3dis: kc = min(n, k) rows per crop on the device, padded through choice; n_min (the smallest cloud, a property of the
+// table the host knows) >= k means no crop is ever padded and the padding's sort is not enqueued.
+static int sb_run(bool s3dis, const crf_cloud_desc* clouds, int n_clouds, int64_t n_max, int64_t n_min, double* min_value,
+                  int64_t* min_index, int64_t k, int64_t B, uint64_t seed, const int64_t* counter, double noise_scale,
+                  const double* noise_in, const int64_t* perm_in, int identity_perm, const int64_t* choice_in, float* out_pos, float* out_x,
+                  int x_channels, int64_t* out_y, int64_t* out_point_idx, int64_t* out_cloud_idx, double* out_center, double* noise_out,
+                  int64_t* perm_out, int64_t* choice_out, void* workspace, size_t workspace_bytes, crf_stream_t stream) {
     CRF_REQUIRE(clouds && min_value && min_index && out_pos && workspace, CRF_ERR_ARG, "null pointer");
     CRF_REQUIRE(n_clouds > 0, CRF_ERR_ARG, "n_clouds=%d", n_clouds);
-    CRF_REQUIRE(k > 0 && k <= n_max && n_max < ((int64_t)1 << 31), CRF_ERR_ARG, "n_max=%lld k=%lld invalid", (long long)n_max,
-                (long long)k);
-    CRF_REQUIRE(B > 0 && B <= 65536 && B * k < ((int64_t)1 << 31), CRF_ERR_ARG, "B=%lld k=%lld invalid", (long long)B, (long long)k);
+    CRF_REQUIRE(k > 0 && (s3dis || k <= n_max) && n_max > 0 && n_max < ((int64_t)1 << 31), CRF_ERR_ARG, "n_max=%lld k=%lld invalid",
+                (long long)n_max, (long long)k);
+    CRF_REQUIRE(!s3dis || (n_min > 0 && n_min <= n_max), CRF_ERR_ARG, "n_min=%lld n_max=%lld invalid", (long long)n_min, (long long)n_max);
+    CRF_REQUIRE(B > 0 && B <= 65536 && B * k < ((int64_t)1 << 31) && (!s3dis || k < ((int64_t)1 << 30)), CRF_ERR_ARG, "B=%lld k=%lld invalid", (long long)B, (long long)k);
     CRF_REQUIRE(out_x == nullptr || x_channels == 3 || x_channels == 6, CRF_ERR_ARG, "x_channels=%d: 3 or 6", x_channels);
-    CRF_REQUIRE(counter != nullptr || (noise_in != nullptr && (perm_in != nullptr || identity_perm)), CRF_ERR_ARG,
-                "a counter is needed unless noise_in and the shuffle are given");
+    const bool padded = s3dis && n_min < k;
+    CRF_REQUIRE(counter != nullptr || (noise_in != nullptr && (perm_in != nullptr || identity_perm) && (!padded || choice_in != nullptr)),
+                CRF_ERR_ARG, "a counter is needed unless noise_in, the shuffle and (with a cloud below k) the padding are given");
     CRF_REQUIRE(!(perm_in != nullptr && identity_perm), CRF_ERR_ARG, "perm_in and identity_perm exclude each other");
-    CRF_REQUIRE(workspace_bytes >= crfconv_possibility_crop_batch_workspace(n_max, k, B), CRF_ERR_WORKSPACE,
-                "possibility_crop_batch workspace %zu < %zu", workspace_bytes, crfconv_possibility_crop_batch_workspace(n_max, k, B));
+    const size_t need = sb_layout(n_max, k, B, s3dis).total;
+    CRF_REQUIRE(workspace_bytes >= need, CRF_ERR_WORKSPACE, "possibility_crop_batch workspace %zu < %zu", workspace_bytes, need);
     hipStream_t st = as_stream(stream);
-    const SbLayout l = sb_layout(n_max, k, B);
+    const SbLayout l = sb_layout(n_max, k, B, s3dis);
     char* ws = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
     auto at = [ws](size_t off) { return ws + off; };
     auto* crop = reinterpret_cast<SbCrop*>(at(l.crop));
@@ -502,7 +680,9 @@ extern "C" int crfconv_possibility_crop_batch(const crf_cloud_desc* clouds, int 
         } else if (where) {
             pvals_a = pvals_b;
         }
-        hipLaunchKernelGGL(sb_perm_final_kernel, pgrid, blk, 0, st, pvals_a, (long long)k, (long long)total, perm_ws, perm_out);
+        // (S3DIS form: the rows of perm_out are written per crop, cut to the crop's own row count)
+        hipLaunchKernelGGL(sb_perm_final_kernel, pgrid, blk, 0, st, pvals_a, (long long)k, (long long)total, perm_ws,
+                           s3dis ? (int64_t*)nullptr : perm_out);
         CRF_LAUNCH_CHECK();
         perm = perm_ws;
     } else if (perm_out != nullptr && perm_in != nullptr) {
@@ -514,8 +694,70 @@ extern "C" int crfconv_possibility_crop_batch(const crf_cloud_desc* clouds, int 
     int64_t ablocks = cdiv(n_max, SB_NT);
     if (ablocks > SB_ARGMIN_BLOCKS) ablocks = SB_ARGMIN_BLOCKS;
     const dim3 sgrid((unsigned)nb), kgrid((unsigned)nblk);
+    auto* compact = reinterpret_cast<int64_t*>(at(l.compact));
+    auto* choice_ws = reinterpret_cast<int64_t*>(at(l.choice));
+    const bool own_perm = perm == perm_ws;
+    int choice_bits = 32;                                              // sort key of the padding: (block j, upper hash half); j < k
+    while (choice_bits < 64 && (k >> (choice_bits - 32)) != 0) choice_bits += 8;
+    if (s3dis && choice_in != nullptr && choice_out != nullptr)
+        CRF_HIP(hipMemcpyAsync(choice_out, choice_in, sizeof(int64_t) * (size_t)total, hipMemcpyDeviceToDevice, st));
     for (int64_t b = 0; b < B; ++b) {
-        hipLaunchKernelGGL(sb_choose_kernel, dim3(1), blk, 0, st, clouds, n_clouds, (const double*)min_value, (const int64_t*)min_index,
+        if (s3dis) {
+            hipLaunchKernelGGL(sb_choose_kernel<true>, dim3(1), blk, 0, st, clouds, n_clouds, (const double*)min_value,
+                               (const int64_t*)min_index, (unsigned long long)seed, counter, (int)b, (long long)k, noise_scale, noise_in,
+                               crop, hist, noise_out, out_center, out_cloud_idx);
+            CRF_LAUNCH_CHECK();
+            for (int p = 0; p < 8; ++p) {
+                hipLaunchKernelGGL(sb_hist_kernel, sgrid, blk, 0, st, clouds, crop, hist, p);
+                CRF_LAUNCH_CHECK();
+            }
+            hipLaunchKernelGGL(sb_count_kernel, sgrid, blk, 0, st, clouds, crop, (const int32_t*)hist, cnt, (long long)nb);
+            CRF_LAUNCH_CHECK();
+            hipLaunchKernelGGL(sb_scatter_kernel<true>, sgrid, blk, 0, st, clouds, (const SbCrop*)crop, (const int32_t*)cnt, (long long)nb,
+                               (long long)k, keys_a, vals_a);
+            CRF_LAUNCH_CHECK();
+            const uint32_t* sel = rsort_pairs_u64(keys_a, vals_a, keys_b, vals_b, k, 0, 64, at(l.sort), st) ? vals_b : vals_a;
+            CRF_LAUNCH_CHECK();
+            if (own_perm && (padded || perm_out != nullptr)) {
+                hipLaunchKernelGGL(sb_perm_compact_kernel, dim3(1), blk, 0, st, (const SbCrop*)crop, perm + b * k, (long long)k, compact,
+                                   perm_out ? perm_out + b * k : (int64_t*)nullptr);
+                CRF_LAUNCH_CHECK();
+            }
+            const int64_t* choice = choice_in ? choice_in + b * k : (const int64_t*)nullptr;
+            if (choice_in == nullptr && (padded || choice_out != nullptr)) {
+                const uint32_t* cv = nullptr;
+                if (padded) {
+                    auto* cka = reinterpret_cast<unsigned long long*>(at(l.ckeys_a));
+                    auto* ckb = reinterpret_cast<unsigned long long*>(at(l.ckeys_b));
+                    auto* cva = reinterpret_cast<uint32_t*>(at(l.cvals_a));
+                    auto* cvb = reinterpret_cast<uint32_t*>(at(l.cvals_b));
+                    hipLaunchKernelGGL(sb_choice_keys_kernel, dim3((unsigned)cdiv(2 * k, SB_NT)), blk, 0, st, (const SbCrop*)crop,
+                                       (unsigned long long)seed, counter, (int)b, (long long)k, cka, cva);
+                    CRF_LAUNCH_CHECK();
+                    cv = rsort_pairs_u64(cka, cva, ckb, cvb, 2 * k, 0, choice_bits, at(l.csort), st) ? cvb : cva;
+                    CRF_LAUNCH_CHECK();
+                }
+                hipLaunchKernelGGL(sb_choice_final_kernel, kgrid, blk, 0, st, (const SbCrop*)crop, cv, (long long)k, choice_ws,
+                                   choice_out ? choice_out + b * k : (int64_t*)nullptr);
+                CRF_LAUNCH_CHECK();
+                choice = choice_ws;
+            }
+            hipLaunchKernelGGL(sb_dist_s3dis_kernel, kgrid, blk, 0, st, clouds, (const SbCrop*)crop, sel, (long long)k, dist, pmax);
+            CRF_LAUNCH_CHECK();
+            hipLaunchKernelGGL(sb_update_s3dis_kernel, kgrid, blk, 0, st, clouds, (const SbCrop*)crop, sel,
+                               perm ? perm + b * k : (const int64_t*)nullptr, own_perm && padded ? (const int64_t*)compact : (const int64_t*)nullptr,
+                               choice, (long long)k, (const float*)dist, (const float*)pmax, nblk, out_pos + (size_t)b * k * 3,
+                               out_x ? out_x + (size_t)b * k * x_channels : (float*)nullptr, x_channels,
+                               out_y ? out_y + b * k : (int64_t*)nullptr, out_point_idx ? out_point_idx + b * k : (int64_t*)nullptr);
+            CRF_LAUNCH_CHECK();
+            hipLaunchKernelGGL(sb_argmin_partial_kernel, dim3((unsigned)ablocks), blk, 0, st, clouds, (const SbCrop*)crop, pv, pi);
+            CRF_LAUNCH_CHECK();
+            hipLaunchKernelGGL(sb_argmin_final_kernel, dim3(1), blk, 0, st, (const SbCrop*)crop, (const double*)pv, (const int64_t*)pi,
+                               (int)ablocks, min_value, min_index);
+            CRF_LAUNCH_CHECK();
+            continue;
+        }
+        hipLaunchKernelGGL(sb_choose_kernel<false>, dim3(1), blk, 0, st, clouds, n_clouds, (const double*)min_value, (const int64_t*)min_index,
                            (unsigned long long)seed, counter, (int)b, (long long)k, noise_scale, noise_in, crop, hist, noise_out,
                            out_center, out_cloud_idx);
         CRF_LAUNCH_CHECK();
@@ -525,7 +767,7 @@ extern "C" int crfconv_possibility_crop_batch(const crf_cloud_desc* clouds, int 
         }
         hipLaunchKernelGGL(sb_count_kernel, sgrid, blk, 0, st, clouds, crop, (const int32_t*)hist, cnt, (long long)nb);
         CRF_LAUNCH_CHECK();
-        hipLaunchKernelGGL(sb_scatter_kernel, sgrid, blk, 0, st, clouds, (const SbCrop*)crop, (const int32_t*)cnt, (long long)nb,
+        hipLaunchKernelGGL(sb_scatter_kernel<false>, sgrid, blk, 0, st, clouds, (const SbCrop*)crop, (const int32_t*)cnt, (long long)nb,
                            (long long)k, keys_a, vals_a);
         CRF_LAUNCH_CHECK();
         const uint32_t* sel = rsort_pairs_u64(keys_a, vals_a, keys_b, vals_b, k, 0, 64, at(l.sort), st) ? vals_b : vals_a;
@@ -544,4 +786,37 @@ extern "C" int crfconv_possibility_crop_batch(const crf_cloud_desc* clouds, int 
         CRF_LAUNCH_CHECK();
     }
     return CRF_OK;
+}
+
+extern "C" size_t crfconv_possibility_crop_batch_workspace(int64_t n_max, int64_t k, int64_t B) {
+    if (n_max <= 0 || k <= 0 || B <= 0 || k > n_max) return 0;
+    return sb_layout(n_max, k, B).total;
+}
+
+extern "C" int crfconv_possibility_crop_batch(const crf_cloud_desc* clouds, int n_clouds, int64_t n_max, double* min_value,
+                                              int64_t* min_index, int64_t k, int64_t B, uint64_t seed, const int64_t* counter,
+                                              double noise_scale, const double* noise_in, const int64_t* perm_in, int identity_perm,
+                                              float* out_pos, float* out_x, int x_channels, int64_t* out_y, int64_t* out_point_idx,
+                                              int64_t* out_cloud_idx, double* out_center, double* noise_out, int64_t* perm_out,
+                                              void* workspace, size_t workspace_bytes, crf_stream_t stream) {
+    return sb_run(false, clouds, n_clouds, n_max, n_max, min_value, min_index, k, B, seed, counter, noise_scale, noise_in, perm_in,
+                  identity_perm, nullptr, out_pos, out_x, x_channels, out_y, out_point_idx, out_cloud_idx, out_center, noise_out, perm_out,
+                  nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t crfconv_possibility_crop_batch_s3dis_workspace(int64_t n_max, int64_t k, int64_t B) {
+    if (n_max <= 0 || k <= 0 || B <= 0) return 0;
+    return sb_layout(n_max, k, B, true).total;
+}
+
+extern "C" int crfconv_possibility_crop_batch_s3dis(const crf_cloud_desc* clouds, int n_clouds, int64_t n_max, int64_t n_min,
+                                                    double* min_value, int64_t* min_index, int64_t k, int64_t B, uint64_t seed,
+                                                    const int64_t* counter, double noise_scale, const double* noise_in,
+                                                    const int64_t* perm_in, int identity_perm, const int64_t* choice_in, float* out_pos,
+                                                    float* out_x, int x_channels, int64_t* out_y, int64_t* out_point_idx,
+                                                    int64_t* out_cloud_idx, double* out_center, double* noise_out, int64_t* perm_out,
+                                                    int64_t* choice_out, void* workspace, size_t workspace_bytes, crf_stream_t stream) {
+    return sb_run(true, clouds, n_clouds, n_max, n_min, min_value, min_index, k, B, seed, counter, noise_scale, noise_in, perm_in,
+                  identity_perm, choice_in, out_pos, out_x, x_channels, out_y, out_point_idx, out_cloud_idx, out_center, noise_out, perm_out,
+                  choice_out, workspace, workspace_bytes, stream);
 }

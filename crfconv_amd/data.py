@@ -376,6 +376,9 @@ class CollateGraph:
         # cloud_idx of the crops reach the target (when it has such tensors) in the row order of y.  Several graphs may share one
         # sampler (the slots of a CollatePipeline): each replay draws from the possibilities the replays before it left, i.e. the crops
         # follow SUBMISSION order on the device -- the caller orders the replays (one side stream, or events).
+        # An S3DIS-form sampler (form='s3dis') is taken as it is, rooms below num_points included: its crops always hold num_points rows.
+        # A padded crop holds coincident points; the kNN's tie rule is deterministic, column 0 of a neighbour row is the point or one
+        # of its twins, and the reference behaves the same way (its _remove_self_loop drops column 0 whichever twin that is).
         if sampler is not None and not device_draw:
             raise ValueError('CollateGraph(sampler=...) draws inside the graph: device_draw=False is not supported with a sampler')
         self.sampler = sampler

@@ -24,6 +24,7 @@ def _ws(nbytes, device):
 _M64 = 0xFFFFFFFFFFFFFFFF
 _SMP_DOMAIN = 0x8CB92BA72F3D8DD7            # csrc/sampler.hip SMP_DOMAIN
 _SMP_PERM_SLOT = 8
+_SMP_CHOICE_SLOT = 1 << 32                  # csrc/sampler.hip SMP_CHOICE_SLOT: slot (j + 1) 2^32 + t
 
 
 def _smp_hash(seed, counter, b, slots):
@@ -41,11 +42,24 @@ class PossibilitySampler:
 
     ``class_weight`` float64 [n_classes] and ``label_to_idx`` (dict raw label -> class id) give the per-point update
     weight of the train / val splits (:443-445); ``split='test'`` uses weight 1 and zero labels (:439-441).
-    Possibilities start as ``randn * 1e-3`` (:267) from ``generator``, or from ``possibility`` if given."""
+    Possibilities start as ``randn * 1e-3`` (:267) from ``generator``, or from ``possibility`` if given.
+
+    ``form='s3dis'`` is the sampler of datasets/s3dis_dataset.py:343-379 instead: the crop is centred on all three axes, the update's
+    distances are those of the float32 centred coordinates, there is no class weight and no label map (both are rejected; labels pass
+    through unchanged, whatever the split), and a room of fewer than ``num_points`` points is taken whole and padded to ``num_points``
+    rows with as few repeats as possible (:375-377, torch_geometric's ``FixedPoints(num_points, replace=False,
+    allow_duplicates=True)``): ``get_random`` and ``get_batch`` always return ``num_points`` rows."""
 
     def __init__(self, points, rgb=None, labels=None, num_points=65536, class_weight=None, label_to_idx=None,
-                 split='train', generator=None, possibility=None, noise_scale=3.5 / 10):
+                 split='train', generator=None, possibility=None, noise_scale=3.5 / 10, form='semantic3d'):
+        if form not in ('semantic3d', 's3dis'):
+            raise ValueError("PossibilitySampler: form must be 'semantic3d' or 's3dis', not %r" % (form,))
+        if form == 's3dis' and class_weight is not None:
+            raise ValueError("PossibilitySampler(form='s3dis'): the S3DIS sampler has no class_weight (s3dis_dataset.py:364)")
+        if form == 's3dis' and label_to_idx is not None:
+            raise ValueError("PossibilitySampler(form='s3dis'): the S3DIS sampler has no label_to_idx (s3dis_dataset.py:360)")
         require_gpu(*points)
+        self.form = form
         self.points = [p.float().contiguous() for p in points]
         self.device = self.points[0].device
         self.rgb = rgb
@@ -55,7 +69,10 @@ class PossibilitySampler:
         self.generator = generator
         self.labels = None
         self.point_weight = None
-        if split != 'test' and labels is not None:
+        if form == 's3dis':
+            if labels is not None:
+                self.labels = [lab.to(self.device).long().contiguous() for lab in labels]
+        elif split != 'test' and labels is not None:
             self.labels, self.point_weight = [], []
             cw = torch.as_tensor(np.asarray(class_weight, dtype=np.float64)).to(self.device)
             for lab in labels:
@@ -91,10 +108,18 @@ class PossibilitySampler:
     def min_possibility(self):
         return self._minv.cpu().numpy()
 
-    def get_random(self, noise=None, perm=None):
+    def get_random(self, noise=None, perm=None, choice=None):
         """One crop.  ``noise`` float64 [3] and ``perm`` int64 [k] override the Gaussian jitter and the shuffle (tests
         feed the reference's draws); otherwise they come from ``self.generator``.  Returns ``Data(pos, rgb, y,
-        point_idx, cloud_idx)`` with the reference's field meanings (:453-458), all on the device."""
+        point_idx, cloud_idx)`` with the reference's field meanings (:453-458), all on the device.
+
+        form='s3dis': ``Data(x = [pos, rgb], pos, y, point_idx, cloud_idx)`` of exactly ``num_points`` rows (s3dis_dataset.py:368-379);
+        ``perm`` holds a permutation of ``range(k_c)``, k_c = min(n_c, num_points), in its first k_c entries and ``choice`` int64
+        [num_points] the padding of a small room (row t = row choice[t] of the shuffled crop; unused when k_c == num_points)."""
+        if self.form == 's3dis':
+            return self._get_random_s3dis(noise, perm, choice)
+        if choice is not None:
+            raise ValueError("get_random(choice=) belongs to form='s3dis'")
         # :424 -- which cloud: the loop's only host decision (a device -> host read; none with a single cloud)
         c = 0 if len(self.points) == 1 else int(torch.argmin(self._minv).item())
         pts = self.points[c]
@@ -126,6 +151,39 @@ class PossibilitySampler:
         out.cloud = c                                        # the same as a host int (VoteAccumulator.update takes it without a device read)
         return out
 
+    @staticmethod
+    def _padding(kc, k, randperm):
+        """FixedPoints(k, replace=False, allow_duplicates=True) for kc < k rows: ceil(k / kc) permutations end to end, cut to k."""
+        return torch.cat([randperm(kc) for _ in range(-(-k // kc))])[:k]
+
+    def _get_random_s3dis(self, noise, perm, choice):
+        """One S3DIS-form crop = the batch call with B = 1 (the same kernels, so get_batch(B) is B of these by construction of the
+        stream order); the draws come from ``self.generator`` in the reference's order: jitter, shuffle, then the padding."""
+        c = 0 if len(self.points) == 1 else int(torch.argmin(self._minv).item())
+        k = self.num_points
+        kc = min(k, self.points[c].shape[0])
+        if noise is None:
+            noise = torch.randn(3, dtype=torch.float64, generator=self.generator) * self.noise_scale
+        noise = torch.as_tensor(noise, dtype=torch.float64).reshape(1, 3)
+        if perm is None:
+            perm = torch.randperm(kc, generator=self.generator)
+        if perm is not False:
+            perm = torch.as_tensor(perm, dtype=torch.int64).reshape(-1).cpu()
+            if perm.numel() < kc:
+                raise ValueError('get_random: perm holds %d entries, the crop %d rows' % (perm.numel(), kc))
+            perm = torch.cat([perm[:kc], torch.full((k - kc,), -1, dtype=torch.int64)]).reshape(1, k)
+        if kc < k:
+            if choice is None:
+                choice = self._padding(kc, k, lambda n: torch.randperm(n, generator=self.generator))
+            choice = torch.as_tensor(choice, dtype=torch.int64).reshape(1, k)
+        else:
+            choice = None
+        d = self.get_batch(1, noise=noise, perm=perm, choice=choice, counter=self._counter)      # (nothing is drawn: the counter stays)
+        out = Data(x=None if d.x is None else d.x[0], pos=d.pos[0], y=d.y[0], point_idx=d.point_idx[0], cloud_idx=d.cloud_idx[0])
+        out.center = d.center[0]
+        out.cloud = c
+        return out
+
     # ---- B crops per call, every decision on the device (csrc/sampler.hip)
     @property
     def seed(self):
@@ -142,7 +200,7 @@ class PossibilitySampler:
             return self._batch
         k = self.num_points
         for c, p in enumerate(self.points):
-            if p.shape[0] < k:
+            if p.shape[0] < k and self.form != 's3dis':
                 raise ValueError('PossibilitySampler.get_batch: cloud %d holds %d points, fewer than num_points = %d (the batch '
                                  'form has fixed shapes)' % (c, p.shape[0], k))
         rgb = None if self.rgb is None else [to_device(torch.as_tensor(r), self.device).float().contiguous() for r in self.rgb]
@@ -153,25 +211,48 @@ class PossibilitySampler:
                          0 if self.point_weight is None else self.point_weight[c].data_ptr(),
                          0 if labels is None else labels[c].data_ptr(), 0 if rgb is None else rgb[c].data_ptr(), p.shape[0]])
         table = to_device(torch.tensor(rows, dtype=torch.int64), self.device)      # crf_cloud_desc [n_clouds]: six 8-byte words each
-        self._batch = {'table': table, 'rgb': rgb, 'labels': labels, 'n_max': max(p.shape[0] for p in self.points), 'ws': {},
+        self._batch = {'table': table, 'rgb': rgb, 'labels': labels, 'n_max': max(p.shape[0] for p in self.points),
+                       'n_min': min(p.shape[0] for p in self.points), 'ws': {},
                        'keep': [t.data_ptr() for t in self.possibility]}
         return self._batch
 
     @staticmethod
-    def draws(seed, counter, B, k=0, noise_scale=1.0):
+    def draws(seed, counter, B, k=0, noise_scale=1.0, kc=None):
         """Host twin (numpy) of what get_batch draws at (seed, counter value the call reads): dict of u [B, 3, 2] (the 53-bit uniforms in
         (0, 1]), normal [B, 3] (Box-Muller, float64), noise [B, 3] = normal * noise_scale, and perm [B, k] int64 (stable arg-sort
-        of the row hashes).  The uniforms and the permutations are the device's exactly; the normals to a few ulp."""
+        of the row hashes).  The uniforms and the permutations are the device's exactly; the normals to a few ulp.
+
+        kc (form='s3dis'): the row count k_c = min(n_c, k) of every crop, B of them.  perm[b] then ranks the first k_c hashes only (its
+        tail is -1) and the dict gains choice [B, k] int64, the padding: the identity for k_c == k, else the first k entries of
+        ceil(k / k_c) permutations of range(k_c) laid end to end, permutation j the stable arg-sort over t of the upper 32 bits of the
+        hash of slot (j + 1) 2^32 + t."""
+        k = int(k)
         u = np.empty((B, 3, 2))
-        perm = np.empty((B, int(k)), np.int64)
+        perm = np.full((B, k), -1, np.int64)
+        choice = None if kc is None else np.empty((B, k), np.int64)
+        if kc is not None and len(kc) != B:
+            raise ValueError('draws: kc holds %d row counts for B = %d crops' % (len(kc), B))
         for b in range(B):
             h = _smp_hash(seed, counter, b, np.arange(6))
             u[b] = (((h >> np.uint64(11)) + np.uint64(1)).astype(np.float64) * 2.0 ** -53).reshape(3, 2)
-            perm[b] = np.argsort(_smp_hash(seed, counter, b, _SMP_PERM_SLOT + np.arange(int(k), dtype=np.uint64)), kind='stable')
+            n = k if kc is None else int(kc[b])
+            if not 0 < n <= k and k > 0:
+                raise ValueError('draws: kc[%d] = %d outside 1 .. k = %d' % (b, n, k))
+            perm[b, :n] = np.argsort(_smp_hash(seed, counter, b, _SMP_PERM_SLOT + np.arange(n, dtype=np.uint64)), kind='stable')
+            if kc is not None:
+                if n == k:
+                    choice[b] = np.arange(k)
+                else:
+                    blocks = [np.argsort(_smp_hash(seed, counter, b, (j + 1) * _SMP_CHOICE_SLOT + np.arange(n, dtype=np.uint64)) >> np.uint64(32),
+                                         kind='stable') for j in range(-(-k // n))]
+                    choice[b] = np.concatenate(blocks)[:k]
         normal = np.sqrt(-2.0 * np.log(u[..., 0])) * np.cos(2.0 * np.pi * u[..., 1])
-        return {'u': u, 'normal': normal, 'noise': normal * float(noise_scale), 'perm': perm}
+        out = {'u': u, 'normal': normal, 'noise': normal * float(noise_scale), 'perm': perm}
+        if kc is not None:
+            out['choice'] = choice
+        return out
 
-    def get_batch(self, B, out=None, noise=None, perm=None, seed=None, counter=None, return_draws=False):
+    def get_batch(self, B, out=None, noise=None, perm=None, seed=None, counter=None, return_draws=False, choice=None):
         """B crops as ONE library call (47 launches per crop, no host read, capturable in a hipGraph): what B consecutive
         ``get_random`` calls give -- crop b + 1 sees the possibilities crop b updated, the cloud is chosen per crop on the
         device -- stacked into ``Data(pos [B, k, 3], x [B, k, C] or None, y [B, k], point_idx [B, k], cloud_idx [B, 1],
@@ -183,7 +264,16 @@ class PossibilitySampler:
         (seed, counter): by default the sampler's own ``seed`` and device counter, which the call advances by one BEFORE drawing;
         an explicit `counter` (one-element int64 device tensor) is read as it is and advanced by its owner (a CollateGraph).
         The seed is a launch scalar: a captured call keeps the seed it was captured with.  return_draws: also returns
-        (noise [B, 3], perm [B, k]) as used, on the device.  Every cloud must hold at least num_points points."""
+        (noise [B, 3], perm [B, k]) as used, on the device.  Every cloud must hold at least num_points points.
+
+        form='s3dis': small clouds are welcome (a room below num_points is taken whole and padded, decided per crop on the device; the
+        launch shapes do not depend on which cloud is drawn).  Only the first k_c = min(n_c, k) entries of a `perm` row are read;
+        `choice` int64 [B, k] overrides the padding (read for crops with k_c < k only; without it and without a counter-keyed draw
+        of its own the call refuses clouds below k).  return_draws gives (data, noise, perm, choice): perm rows end in -1 beyond k_c,
+        choice rows are the identity for k_c == k."""
+        s3dis = self.form == 's3dis'
+        if choice is not None and not s3dis:
+            raise ValueError("get_batch(choice=) belongs to form='s3dis'")
         tb = self._batch_tables()
         if tb['keep'] != [t.data_ptr() for t in self.possibility]:
             raise _lib.CrfConvError('PossibilitySampler: the possibility tensors were replaced after the first get_batch '
@@ -227,6 +317,10 @@ class PossibilitySampler:
                 raise ValueError('get_batch: perm must be [B, k]')
         else:
             perm = None
+        if choice is not None:
+            choice = to_device(torch.as_tensor(choice, dtype=torch.int64).contiguous(), dev)
+            if tuple(choice.shape) != (B, k):
+                raise ValueError('get_batch: choice must be [B, k]')
         if counter is None:
             counter = self._counter
             _lib.call('crfconv_add_i64', ptr(counter), 1, 1, stream_ptr())
@@ -238,18 +332,29 @@ class PossibilitySampler:
             noise_out = torch.empty((B, 3), dtype=torch.float64, device=dev)
             perm_out = torch.arange(k, dtype=torch.int64, device=dev).repeat(B, 1) if identity \
                 else torch.empty((B, k), dtype=torch.int64, device=dev)
+        choice_out = torch.empty((B, k), dtype=torch.int64, device=dev) if return_draws and s3dis else None
         if B not in tb['ws']:
-            tb['ws'][B] = _ws(_lib.load().crfconv_possibility_crop_batch_workspace(tb['n_max'], k, B), dev)
+            query = _lib.load().crfconv_possibility_crop_batch_s3dis_workspace if s3dis else _lib.load().crfconv_possibility_crop_batch_workspace
+            tb['ws'][B] = _ws(query(tb['n_max'], k, B), dev)
         ws = tb['ws'][B]
-        _lib.call('crfconv_possibility_crop_batch', ptr(tb['table']), len(self.points), tb['n_max'], ptr(self._minv), ptr(self._mini),
-                  k, B, seed & _M64, ptr(counter), self.noise_scale, ptr(noise), ptr(perm), 1 if identity else 0, ptr(pos), ptr(x),
-                  0 if x is None else x.shape[-1], ptr(res['y']), ptr(res['point_idx']), ptr(res['cloud_idx']), ptr(res['center']),
-                  ptr(noise_out), None if identity else ptr(perm_out), ptr(ws), ws.numel(), stream_ptr())
+        if s3dis:
+            _lib.call('crfconv_possibility_crop_batch_s3dis', ptr(tb['table']), len(self.points), tb['n_max'], tb['n_min'], ptr(self._minv),
+                      ptr(self._mini), k, B, seed & _M64, ptr(counter), self.noise_scale, ptr(noise), ptr(perm), 1 if identity else 0,
+                      ptr(choice), ptr(pos), ptr(x), 0 if x is None else x.shape[-1], ptr(res['y']), ptr(res['point_idx']),
+                      ptr(res['cloud_idx']), ptr(res['center']), ptr(noise_out), None if identity else ptr(perm_out), ptr(choice_out),
+                      ptr(ws), ws.numel(), stream_ptr())
+        else:
+            _lib.call('crfconv_possibility_crop_batch', ptr(tb['table']), len(self.points), tb['n_max'], ptr(self._minv), ptr(self._mini),
+                      k, B, seed & _M64, ptr(counter), self.noise_scale, ptr(noise), ptr(perm), 1 if identity else 0, ptr(pos), ptr(x),
+                      0 if x is None else x.shape[-1], ptr(res['y']), ptr(res['point_idx']), ptr(res['cloud_idx']), ptr(res['center']),
+                      ptr(noise_out), None if identity else ptr(perm_out), ptr(ws), ws.numel(), stream_ptr())
         for t in list(res.values()) + list(self.possibility) + [self._minv, self._mini]:      # written by library kernels
             if t is not None:
                 torch.autograd.graph.increment_version(t)
         data = Data(pos=pos, x=x, y=res['y'], point_idx=res['point_idx'], cloud_idx=res['cloud_idx'])
         data.center = res['center']
+        if return_draws and s3dis:
+            return data, noise_out, perm_out, choice_out
         return (data, noise_out, perm_out) if return_draws else data
 
     def snapshot(self):
@@ -282,18 +387,30 @@ class VoteAccumulator:
     """``test_probs`` of trainval.py:58 (one float32 [n_c, n_classes] table per cloud, zeros) with the update of
     :186-189 and the projection of :198-203."""
 
-    def __init__(self, cloud_sizes, num_classes, smooth=0.98, device='cuda', track_visits=False):
+    def __init__(self, cloud_sizes, num_classes, smooth=0.98, device='cuda', track_visits=False, allow_repeats=False):
         """track_visits: count the updates of every point (int32 tables beside the votes) -- what ``merge`` needs when the crops of a
-        scene are spread over several accumulators (ranks)."""
+        scene are spread over several accumulators (ranks).
+        allow_repeats: the rows of an update may name a point more than once (the padded crops of an S3DIS-form sampler; smooth = 0.95
+        is the S3DIS value, trainval.py:220): one int32 table per cloud picks the row that is stored (``update(repeated=)``)."""
         self.num_classes = int(num_classes)
         self.smooth = float(smooth)
         self.test_probs = [torch.zeros((int(n), self.num_classes), dtype=torch.float32, device=device) for n in cloud_sizes]
         self.visits = [torch.zeros(int(n), dtype=torch.int32, device=device) for n in cloud_sizes] if track_visits else None
         self._bad = torch.zeros(1, dtype=torch.int32, device=device)
+        self._last = [torch.full((int(n),), -1, dtype=torch.int32, device=device) for n in cloud_sizes] if allow_repeats else None
 
-    def update(self, point_idx, cloud_idx, probs=None, logits=None):
+    def update(self, point_idx, cloud_idx, probs=None, logits=None, repeated=None):
         """point_idx int64 [B, N]; cloud_idx int64 [B] or [B, 1]; probs or logits float32 [B * N, C] (the network's
-        output layout).  Samples are applied in batch order, as the reference's ``for b in range(batch_size)``."""
+        output layout).  Samples are applied in batch order, as the reference's ``for b in range(batch_size)``.
+
+        repeated: the rows of a sample may name one point several times; the update then has numpy's meaning of
+        ``test_probs[c][p_idx] = s * test_probs[c][p_idx] + (1 - s) * probs`` (trainval.py:256-262): every right-hand side is formed
+        from the old row, the last row naming a point is stored, a visit is counted once per point.  None = as the accumulator was built
+        (``allow_repeats``); False keeps the kernel for distinct rows, which races on repeats."""
+        if repeated is None:
+            repeated = self._last is not None
+        if repeated and self._last is None:
+            raise _lib.CrfConvError('VoteAccumulator.update(repeated=True) needs allow_repeats=True at construction')
         src = probs if probs is not None else logits
         require_gpu(point_idx, src)
         B, N = point_idx.shape
@@ -303,7 +420,12 @@ class VoteAccumulator:
         clouds = cloud_idx.reshape(B, -1)[:, 0].tolist() if torch.is_tensor(cloud_idx) else ([int(cloud_idx)] if isinstance(cloud_idx, int) else [int(c) for c in cloud_idx])
         for b in range(B):
             tp = self.test_probs[int(clouds[b])]
-            if self.visits is None:
+            if repeated:
+                _lib.call('crfconv_vote_update_repeated', ptr(src[b]) if probs is not None else None,
+                          ptr(src[b]) if probs is None else None, ptr(point_idx[b]), N, self.num_classes, self.smooth,
+                          ptr(tp), tp.shape[0], ptr(self._bad), None if self.visits is None else ptr(self.visits[int(clouds[b])]),
+                          ptr(self._last[int(clouds[b])]), stream_ptr())
+            elif self.visits is None:
                 _lib.call('crfconv_vote_accumulate', ptr(src[b]) if probs is not None else None,
                           ptr(src[b]) if probs is None else None, ptr(point_idx[b]), N, self.num_classes, self.smooth,
                           ptr(tp), tp.shape[0], ptr(self._bad), stream_ptr())
@@ -408,7 +530,10 @@ def vote_scene(sampler, net, votes, n_crops, kernel_size=(16, 16, 16, 16, 16), r
     graph_cache: a dict the captured graphs are kept in across calls (same net, same crop shapes: further scenes pay no capture).
     timings: a dict that receives the summed milliseconds per stage (host clock around device-synchronised stages: a diagnostic mode --
     it serialises host and device).  on_crop(data, logits, point_idx): called per crop with the collated batch (static buffers when graphed:
-    clone what is to be kept), the logits and the crop's point ids in the batch's row order (tests)."""
+    clone what is to be kept), the logits and the crop's point ids in the batch's row order (tests).
+
+    An S3DIS-form sampler (``form='s3dis'``) yields crops of exactly num_points rows with x = [pos, rgb] built; the crop of a small room
+    names some points twice, so ``votes`` must have been built with ``allow_repeats=True`` and every update is a repeated-index one."""
     import time
     from .data import multiscale_compute
     dev = sampler.device
@@ -422,6 +547,7 @@ def vote_scene(sampler, net, votes, n_crops, kernel_size=(16, 16, 16, 16, 16), r
         torch.cuda.synchronize()
         timings[name] = timings.get(name, 0.0) + (time.perf_counter() - t0) * 1e3
         return out
+    repeated = True if getattr(sampler, 'form', 'semantic3d') == 's3dis' else None
     was_training = net.training
     net.eval()
     graphs = graph_cache if graph_cache is not None else {}
@@ -431,8 +557,11 @@ def vote_scene(sampler, net, votes, n_crops, kernel_size=(16, 16, 16, 16, 16), r
             if i % world != rank:
                 continue
             pos = crop.pos.unsqueeze(0)
-            rgb = crop.rgb if crop.rgb is not None else torch.zeros_like(crop.pos)
-            x = torch.cat([crop.pos, rgb], -1).unsqueeze(0)
+            if repeated:                                                  # (s3dis form: x = [pos, rgb] comes with the crop)
+                x = (crop.x if crop.x is not None else torch.cat([crop.pos, torch.zeros_like(crop.pos)], -1)).unsqueeze(0)
+            else:
+                rgb = crop.rgb if crop.rgb is not None else torch.zeros_like(crop.pos)
+                x = torch.cat([crop.pos, rgb], -1).unsqueeze(0)
             shape = tuple(pos.shape)
             if graphed and shape in graphs:
                 logits, order = stage('collate+network (replays)', lambda: graphs[shape].run(pos, x))
@@ -446,12 +575,12 @@ def vote_scene(sampler, net, votes, n_crops, kernel_size=(16, 16, 16, 16, 16), r
                 # the collate reordered the crop along its Morton curve: point_idx travelled with it (multiscale_compute permutes x, y, point_idx alike)
                 point_idx = data.point_idx
                 if graphed:
-                    votes.update(point_idx, crop.cloud, logits=logits)
+                    votes.update(point_idx, crop.cloud, logits=logits, repeated=repeated)
                     if on_crop is not None:
                         on_crop(data, logits, point_idx)
                     graphs[shape] = _GraphedCrops(net, data, kernel_size, ratio, generator)
                     continue
-            stage('vote', lambda: votes.update(point_idx, crop.cloud, logits=logits))
+            stage('vote', lambda: votes.update(point_idx, crop.cloud, logits=logits, repeated=repeated))
             if on_crop is not None:
                 on_crop(data, logits, point_idx)
     finally:

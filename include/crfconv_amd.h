@@ -951,6 +951,36 @@ int crfconv_possibility_crop_batch(const crf_cloud_desc* clouds, int n_clouds, i
                                    int x_channels, int64_t* out_y, int64_t* out_point_idx, int64_t* out_cloud_idx, double* out_center,
                                    double* noise_out, int64_t* perm_out, void* workspace, size_t workspace_bytes, crf_stream_t stream);
 
+/* The S3DIS form of the same call (datasets/s3dis_dataset.py:343-379), operation for operation.  Per crop, decided on the device:
+ *   kc     = min(n of the chosen cloud, k): a room smaller than k is taken whole
+ *   pos    = float32(float64(point) - centre) on ALL three axes; d = x x + y y + z z of those float32 values in float32 (each operation
+ *            rounded once); possibility[q] += float64((1 - d / max d)^2) over the kc distinct rows; no class weight, labels as stored
+ *   row t of crop b shows row choice_b[t] of the shuffled crop, i.e. selected element perm_b[choice_b[t]]
+ *   perm_b   = perm_in (only the first kc entries of row b are read: a permutation of range(kc)), the identity, or the stable ranking of
+ *              the first kc hashes of slot 8 + t (for kc == k the permutation of crfconv_possibility_crop_batch)
+ *   choice_b = the identity when kc == k; else choice_in, or the first k entries of ceil(k / kc) permutations of range(kc) laid end to
+ *              end, permutation j = stable arg-sort over t of the UPPER 32 bits of the hash of slot (j + 1) 2^32 + t
+ *              (torch_geometric's FixedPoints(k, replace=False, allow_duplicates=True)): pos, x, y, point_idx are padded.
+ * n_min = the smallest cloud of the table: with n_min >= k no crop is padded and the padding's sort is not enqueued.  k may exceed
+ * n_max.  perm_out int64 [B, k]: the kc entries used, then -1; choice_out int64 [B, k].  The launch shapes depend on (n_max, n_min,
+ * k, B) only.  Workspace: crfconv_possibility_crop_batch_s3dis_workspace(n_max, k, B). */
+size_t crfconv_possibility_crop_batch_s3dis_workspace(int64_t n_max, int64_t k, int64_t B);
+int crfconv_possibility_crop_batch_s3dis(const crf_cloud_desc* clouds, int n_clouds, int64_t n_max, int64_t n_min, double* min_value,
+                                         int64_t* min_index, int64_t k, int64_t B, uint64_t seed, const int64_t* counter,
+                                         double noise_scale, const double* noise_in, const int64_t* perm_in, int identity_perm,
+                                         const int64_t* choice_in, float* out_pos, float* out_x, int x_channels, int64_t* out_y,
+                                         int64_t* out_point_idx, int64_t* out_cloud_idx, double* out_center, double* noise_out,
+                                         int64_t* perm_out, int64_t* choice_out, void* workspace, size_t workspace_bytes,
+                                         crf_stream_t stream);
+
+/* crfconv_vote_accumulate(_counted) for rows that may name one point several times (a padded S3DIS crop), with numpy's meaning of
+ * a[idx] = s * a[idx] + (1 - s) * p: every right-hand side is formed from the old row, of several rows naming one point the LAST is
+ * stored, visits (may be NULL) rises by one per point and call.  last_row int32 [n_cloud]: the caller's table, -1 everywhere before
+ * the first call and again after every call.  n_rows < 2^31.  Deterministic (an integer atomic max picks the row). */
+int crfconv_vote_update_repeated(const float* probs, const float* logits, const int64_t* point_idx, int64_t n_rows, int C, double smooth,
+                                 float* test_probs, int64_t n_cloud, int32_t* bad_count, int32_t* visits, int32_t* last_row,
+                                 crf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
