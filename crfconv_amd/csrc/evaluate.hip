@@ -7,8 +7,7 @@
 //   * possibility sampler of datasets/semantic3d_dataset.py:423-460 (_get_random): seed = arg-min possibility,
 //     crop = the num_points nearest points of the (jittered) seed, possibility += (1 - d / d_max)^2 * weight.
 // Integer / byte work and streaming reductions: HBM-bound, no LDS tiling beyond block-local histograms.
-#include "common.hpp"
-
+#include "crop_common.hpp"
 #include "radix_sort.hpp"
 
 namespace crf {
@@ -136,34 +135,10 @@ __global__ __launch_bounds__(EV_BLOCK) void project_kernel(const float* __restri
 }
 
 // ------------------------------------------------------------------------------------------ possibility sampler
-// arg-min with the first index on ties (np.argmin), two passes: per-block candidates, then one block.
-struct MinIdx {
-    double v;
-    int64_t i;
-};
-__device__ __forceinline__ MinIdx min_first(MinIdx a, MinIdx b) {
-    return (b.v < a.v || (b.v == a.v && b.i < a.i)) ? b : a;
-}
-__device__ __forceinline__ MinIdx block_min_first(MinIdx m) {
-    __shared__ double s_v[EV_BLOCK / WAVE];
-    __shared__ int64_t s_i[EV_BLOCK / WAVE];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        MinIdx other;
-        other.v = __shfl_xor(m.v, o, WAVE);
-        other.i = __shfl_xor(m.i, o, WAVE);
-        m = min_first(m, other);
-    }
-    if ((threadIdx.x & 63) == 0) { s_v[threadIdx.x >> 6] = m.v; s_i[threadIdx.x >> 6] = m.i; }
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int w = 1; w < EV_BLOCK / WAVE; ++w) m = min_first(m, MinIdx{s_v[w], s_i[w]});
-    return m;       // valid on thread 0
-}
-
+// arg-min with the first index on ties (np.argmin; crop_common.hpp), two passes: per-block candidates, then one block.
 __global__ __launch_bounds__(EV_BLOCK) void argmin_partial_kernel(const double* __restrict__ v, int64_t n,
                                                                   double* __restrict__ pv, int64_t* __restrict__ pi) {
-    MinIdx m{1.0 / 0.0, INT64_MAX};
+    MinIdx m = min_none();
     for (int64_t i = (int64_t)blockIdx.x * EV_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * EV_BLOCK)
         m = min_first(m, MinIdx{v[i], i});
     m = block_min_first(m);
@@ -173,7 +148,7 @@ __global__ __launch_bounds__(EV_BLOCK) void argmin_partial_kernel(const double* 
 __global__ __launch_bounds__(EV_BLOCK) void argmin_final_kernel(const double* __restrict__ pv,
                                                                 const int64_t* __restrict__ pi, int nblk,
                                                                 double* __restrict__ out_v, int64_t* __restrict__ out_i) {
-    MinIdx m{1.0 / 0.0, INT64_MAX};
+    MinIdx m = min_none();
     for (int b = threadIdx.x; b < nblk; b += EV_BLOCK) m = min_first(m, MinIdx{pv[b], pi[b]});
     m = block_min_first(m);
     if (threadIdx.x == 0) { *out_v = m.v; *out_i = m.i; }
@@ -185,51 +160,29 @@ __global__ void pick_point_kernel(const float* __restrict__ points, const int64_
     if (threadIdx.x < 3) center[threadIdx.x] = (double)points[*pick * 3 + threadIdx.x] + (noise ? noise[threadIdx.x] : 0.0);
 }
 
-// sort key of point i = bit pattern of the float64 squared distance to the seed (sklearn's KDTree holds the points
-// as float64 and ranks by the reduced distance sum (x - c)^2); non-negative doubles order like their bit patterns.
+// The single-crop entry: the key of EVERY point for a full stable sort of the cloud -- the independent twin of sampler.hip's select --
+// then the distances, the update and the row write of crop_common.hpp in the Semantic3D form.
 __global__ __launch_bounds__(EV_BLOCK) void crop_keys_kernel(const float* __restrict__ points, int64_t n,
                                                              const double* __restrict__ center,
                                                              unsigned long long* __restrict__ keys,
                                                              unsigned int* __restrict__ ids) {
     const int64_t i = (int64_t)blockIdx.x * EV_BLOCK + threadIdx.x;
     if (i >= n) return;
-    const double dx = (double)points[3 * i] - center[0], dy = (double)points[3 * i + 1] - center[1],
-                 dz = (double)points[3 * i + 2] - center[2];
-    const double d = dadd_rn(dadd_rn(dmul_rn(dx, dx), dmul_rn(dy, dy)), dmul_rn(dz, dz));
-    keys[i] = (unsigned long long)__double_as_longlong(d);
+    keys[i] = crop_key(points, i, center[0], center[1], center[2]);
     ids[i] = (unsigned int)i;
 }
 
-// float32 distances of the crop as the reference forms them for the possibility update
-// (np.sum(np.square(points[q] - pick).astype(np.float32), axis=1), :448): squares in float64, rounded to float32,
-// added left to right in float32; plus the block-wise maximum.
 __global__ __launch_bounds__(EV_BLOCK) void crop_dist_kernel(const float* __restrict__ points,
                                                              const unsigned int* __restrict__ sel, int64_t k,
                                                              const double* __restrict__ center,
                                                              float* __restrict__ dist, float* __restrict__ pmax) {
-    __shared__ float s_red[EV_BLOCK / WAVE];
     const int64_t t = (int64_t)blockIdx.x * EV_BLOCK + threadIdx.x;
     float d = 0.f;
-    if (t < k) {
-        const int64_t i = sel[t];
-        const double dx = (double)points[3 * i] - center[0], dy = (double)points[3 * i + 1] - center[1],
-                     dz = (double)points[3 * i + 2] - center[2];
-        d = add_rn(add_rn((float)dmul_rn(dx, dx), (float)dmul_rn(dy, dy)), (float)dmul_rn(dz, dz));
-        dist[t] = d;
-    }
-    float mx = d;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, WAVE));
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < EV_BLOCK / WAVE; ++w) mx = fmaxf(mx, s_red[w]);
-        pmax[blockIdx.x] = mx;
-    }
+    if (t < k) dist[t] = d = crop_row_dist<false>(points, sel[t], center);
+    block_max_to(d, pmax);
 }
 
-// possibility[q] += (1 - d / d_max)^2 * weight[label_to_idx(labels[q])]     (:449-450), and the crop's outputs:
-// point_idx (int64), xyz centred on the seed in x and y (:436-437, float64 subtraction rounded to float32).
+// possibility[q] += (1 - d / d_max)^2 * weight[label_to_idx(labels[q])]     (:449-450), and the crop's outputs
 __global__ __launch_bounds__(EV_BLOCK) void crop_update_kernel(const float* __restrict__ points,
                                                                const unsigned int* __restrict__ sel,
                                                                const int64_t* __restrict__ perm, int64_t k,
@@ -242,26 +195,39 @@ __global__ __launch_bounds__(EV_BLOCK) void crop_update_kernel(const float* __re
                                                                float* __restrict__ out_xyz) {
     const int64_t t = (int64_t)blockIdx.x * EV_BLOCK + threadIdx.x;
     if (t >= k) return;
-    float dmax = pmax[0];
-    for (int b = 1; b < nblk; ++b) dmax = fmaxf(dmax, pmax[b]);
     const int64_t src = perm ? perm[t] : t;            // output row t shows selected element perm[t] (the shuffle)
     const int64_t i = sel[src];
-    const float u = sub_rn(1.0f, __fdiv_rn(dist[src], dmax));
-    const float sq = mul_rn(u, u);
+    const float sq = crop_gain(dist[src], crop_dmax(pmax, nblk));
     // the weights are float64 for train / val (class_weight array) and the python int 1 for test (float32 result)
-    const double delta = point_weight ? dmul_rn((double)sq, point_weight[i]) : (double)sq;
-    possibility[i] += delta;                            // rows of a crop are distinct points
-    out_idx[t] = i;
-    out_xyz[3 * t + 0] = (float)((double)points[3 * i + 0] - center[0]);
-    out_xyz[3 * t + 1] = (float)((double)points[3 * i + 1] - center[1]);
-    out_xyz[3 * t + 2] = points[3 * i + 2];
+    possibility[i] += point_weight ? dmul_rn((double)sq, point_weight[i]) : (double)sq;      // rows of a crop are distinct points
+    crop_write_row<false>(points, nullptr, nullptr, i, center, t, out_xyz, nullptr, 0, nullptr, out_idx);
 }
 
-static size_t ev_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
-static size_t crop_sort_temp(int64_t n) { return rsort_workspace(n); }      // this library's radix sort (radix_sort.hpp)
-
+static_assert(EV_BLOCK == CROP_NT, "the crop helpers reduce over 256 threads");
 constexpr int ARGMIN_BLOCKS = 1024;
+
+struct CropWs {                   // workspace of the single-crop entry
+    unsigned long long *keys_in, *keys_out;
+    unsigned int *ids_in, *ids_out;
+    float *dist, *pmax;
+    double* center;
+    char* sort;
+    size_t bytes;
+};
+static CropWs crop_carve(void* workspace, int64_t n, int64_t k) {
+    Carve c(workspace);
+    CropWs w;
+    w.keys_in = c.take<unsigned long long>((size_t)n);
+    w.keys_out = c.take<unsigned long long>((size_t)n);
+    w.ids_in = c.take<unsigned int>((size_t)n);
+    w.ids_out = c.take<unsigned int>((size_t)n);
+    w.dist = c.take<float>((size_t)k);
+    w.pmax = c.take<float>((size_t)cdiv(k, EV_BLOCK));
+    w.center = c.take<double>(3);
+    w.sort = c.take<char>(rsort_workspace(n));      // this library's radix sort (radix_sort.hpp)
+    w.bytes = c.bytes();
+    return w;
+}
 
 }  // namespace crf
 
@@ -377,7 +343,7 @@ extern "C" int crfconv_vote_project(const float* test_probs, const int64_t* proj
     return CRF_OK;
 }
 
-extern "C" size_t crfconv_argmin_workspace(void) { return ev_align(ARGMIN_BLOCKS * 8) * 2; }
+extern "C" size_t crfconv_argmin_workspace(void) { return ARGMIN_BLOCKS * (sizeof(double) + sizeof(int64_t)); }
 
 extern "C" int crfconv_argmin_f64(const double* values, int64_t n, double* out_value, int64_t* out_index,
                                   void* workspace, size_t workspace_bytes, crf_stream_t stream) {
@@ -385,7 +351,7 @@ extern "C" int crfconv_argmin_f64(const double* values, int64_t n, double* out_v
     CRF_REQUIRE(n > 0, CRF_ERR_ARG, "empty array");
     CRF_REQUIRE(workspace_bytes >= crfconv_argmin_workspace(), CRF_ERR_WORKSPACE, "argmin workspace too small");
     double* pv = reinterpret_cast<double*>(workspace);
-    int64_t* pi = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(workspace) + ev_align(ARGMIN_BLOCKS * 8));
+    int64_t* pi = reinterpret_cast<int64_t*>(pv + ARGMIN_BLOCKS);
     int64_t blocks = cdiv(n, EV_BLOCK);
     if (blocks > ARGMIN_BLOCKS) blocks = ARGMIN_BLOCKS;
     hipLaunchKernelGGL(argmin_partial_kernel, dim3((unsigned)blocks), dim3(EV_BLOCK), 0, as_stream(stream), values, n, pv, pi);
@@ -398,9 +364,7 @@ extern "C" int crfconv_argmin_f64(const double* values, int64_t n, double* out_v
 
 extern "C" size_t crfconv_possibility_crop_workspace(int64_t n, int64_t k) {
     if (n <= 0 || k <= 0) return 0;
-    // [keys_in n u64][keys_out n u64][ids_in n u32][ids_out n u32][dist k f32][pmax blocks f32][center 3 f64][sort temp]
-    return 2 * ev_align(8 * (size_t)n) + 2 * ev_align(4 * (size_t)n) + ev_align(4 * (size_t)k) +
-           ev_align(4 * (size_t)cdiv(k, EV_BLOCK)) + 256 + ev_align(crop_sort_temp(n)) + 256;
+    return crop_carve(nullptr, n, k).bytes;
 }
 
 extern "C" int crfconv_possibility_crop(const float* points, int64_t n, int64_t k, const int64_t* pick_index,
@@ -410,34 +374,25 @@ extern "C" int crfconv_possibility_crop(const float* points, int64_t n, int64_t 
     CRF_REQUIRE(points && pick_index && possibility && out_idx && out_xyz && workspace, CRF_ERR_ARG, "null pointer");
     CRF_REQUIRE(n > 0 && k > 0 && k <= n && n < ((int64_t)1 << 32), CRF_ERR_ARG, "n=%lld k=%lld invalid", (long long)n,
                 (long long)k);
-    CRF_REQUIRE(workspace_bytes >= crfconv_possibility_crop_workspace(n, k), CRF_ERR_WORKSPACE,
-                "possibility_crop workspace %zu < %zu", workspace_bytes, crfconv_possibility_crop_workspace(n, k));
+    const CropWs w = crop_carve(workspace, n, k);
+    CRF_REQUIRE(workspace_bytes >= w.bytes, CRF_ERR_WORKSPACE, "possibility_crop workspace %zu < %zu", workspace_bytes, w.bytes);
     hipStream_t st = as_stream(stream);
-    char* ws = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-    auto* keys_in = reinterpret_cast<unsigned long long*>(ws);   ws += ev_align(8 * (size_t)n);
-    auto* keys_out = reinterpret_cast<unsigned long long*>(ws);  ws += ev_align(8 * (size_t)n);
-    auto* ids_in = reinterpret_cast<unsigned int*>(ws);          ws += ev_align(4 * (size_t)n);
-    auto* ids_out = reinterpret_cast<unsigned int*>(ws);         ws += ev_align(4 * (size_t)n);
-    auto* dist = reinterpret_cast<float*>(ws);                   ws += ev_align(4 * (size_t)k);
     const int nblk = (int)cdiv(k, EV_BLOCK);
-    auto* pmax = reinterpret_cast<float*>(ws);                   ws += ev_align(4 * (size_t)nblk);
-    auto* center = reinterpret_cast<double*>(ws);                ws += 256;
-    size_t temp_bytes = crop_sort_temp(n);
-
-    hipLaunchKernelGGL(pick_point_kernel, dim3(1), dim3(64), 0, st, points, pick_index, noise, center);
+    hipLaunchKernelGGL(pick_point_kernel, dim3(1), dim3(64), 0, st, points, pick_index, noise, w.center);
     CRF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(crop_keys_kernel, dim3((unsigned)cdiv(n, EV_BLOCK)), dim3(EV_BLOCK), 0, st, points, n, center,
-                       keys_in, ids_in);
+    hipLaunchKernelGGL(crop_keys_kernel, dim3((unsigned)cdiv(n, EV_BLOCK)), dim3(EV_BLOCK), 0, st, points, n, (const double*)w.center,
+                       w.keys_in, w.ids_in);
     CRF_LAUNCH_CHECK();
-    // stable LSD radix sort: equal distances keep ascending point order (the KD-tree's order on ties is unspecified)
-    (void)temp_bytes;
-    if (rsort_pairs_u64(keys_in, ids_in, keys_out, ids_out, n, 0, 64, ws, st) == 0) ids_out = ids_in;      // float64 keys: all eight digits
+    // stable LSD radix sort over all eight digits of the float64 keys: equal distances keep ascending point order (the KD-tree's order
+    // on ties is unspecified)
+    const unsigned int* sel = rsort_pairs_u64(w.keys_in, w.ids_in, w.keys_out, w.ids_out, n, 0, 64, w.sort, st) ? w.ids_out : w.ids_in;
     CRF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(crop_dist_kernel, dim3((unsigned)nblk), dim3(EV_BLOCK), 0, st, points, ids_out, k, center, dist, pmax);
+    hipLaunchKernelGGL(crop_dist_kernel, dim3((unsigned)nblk), dim3(EV_BLOCK), 0, st, points, sel, k, (const double*)w.center, w.dist,
+                       w.pmax);
     CRF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(crop_update_kernel, dim3((unsigned)nblk), dim3(EV_BLOCK), 0, st, points, ids_out, perm, k, center,
-                       dist, pmax, nblk, point_weight, possibility, out_idx, out_xyz);
+    hipLaunchKernelGGL(crop_update_kernel, dim3((unsigned)nblk), dim3(EV_BLOCK), 0, st, points, sel, perm, k, (const double*)w.center,
+                       (const float*)w.dist, (const float*)w.pmax, nblk, point_weight, possibility, out_idx, out_xyz);
     CRF_LAUNCH_CHECK();
-    if (out_center) CRF_HIP(hipMemcpyAsync(out_center, center, 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
+    if (out_center) CRF_HIP(hipMemcpyAsync(out_center, w.center, 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
     return CRF_OK;
 }

@@ -1,15 +1,16 @@
 // B possibility crops per call, decided and written on the device (datasets/semantic3d_dataset.py:423-460, `_get_random`, as B
 // consecutive __getitem__ calls; crfconv_amd.sampling.PossibilitySampler.get_batch).  No host read anywhere, no scratch memory:
 // the whole call can sit in a captured hipGraph (data.CollateGraph(sampler=)).  Bit for bit what B calls of
-// crfconv_possibility_crop (evaluate.hip) give for the same jitter and shuffle, without sorting the cloud:
+// crfconv_possibility_crop (evaluate.hip) give for the same jitter and shuffle, without sorting the cloud.  The key, the distances,
+// the gain, the row write and the arg-min are those of crop_common.hpp, which that entry uses too.
 //
-//   per crop b, in stream order (crop b + 1 sees the possibilities crop b left):
+//   ONE sequence per crop b for both forms (sb_run), in stream order (crop b + 1 sees the possibilities crop b left):
 //     sb_choose_kernel   1 workgroup: cloud = arg-min of the per-cloud minima (first index on ties), seed point = that cloud's
 //                        arg-min, jitter (Box-Muller in float64 on 53-bit uniforms of smp_hash, or noise_in), centre; clears the
 //                        select's histograms.  The cloud is read through a DEVICE table of descriptors (crf_cloud_desc), the grids
 //                        below are sized for the largest cloud and leave early beyond the chosen one.
-//     sb_hist_kernel x 8 MSB-first radix SELECT on the 64-bit key (bit pattern of the float64 squared distance, recomputed from the
-//                        12-byte point in every pass): pass p counts digit p of the keys that match the p digits found so far
+//     sb_hist_kernel x 8 MSB-first radix SELECT on the 64-bit key (crop_key: bit pattern of the float64 squared distance, recomputed
+//                        from the 12-byte point in every pass): pass p counts digit p of the keys that match the p digits found so far
 //                        (per-wavefront LDS bins; a wavefront whose matching lanes agree on the digit -- the rule in the exponent
 //                        passes -- adds one popcount; <= 256 global integer atomics per workgroup).  Every workgroup resolves the
 //                        PREVIOUS pass itself (256-bin scan: the digit holding rank `want`, and the rank inside it), so there is
@@ -20,25 +21,30 @@
 //                        below the k-th in point order into [0, L), then the first k - L points with the k-th key in point order.
 //     rsort_pairs_u64    the library's stable radix sort over those k pairs only: (key, point id) order, i.e. what the full stable
 //                        sort of evaluate.hip yields; ties at the ball's boundary go to the lower point id.
-//     sb_dist_kernel / sb_update_kernel   float32 distances, d_max, possibility += (1 - d / d_max)^2 weight -- the arithmetic of
-//                        crop_dist_kernel / crop_update_kernel operation for operation -- and row b of the batch: pos (x, y
-//                        centred), x = [pos, rgb], y, point_idx, through the shuffle.
+//     (S3DIS form only)  the padding of a short crop, see below: sb_perm_compact_kernel, sb_choice_keys_kernel + its sort,
+//                        sb_choice_final_kernel -- each enqueued only when the table or the caller's outputs can need it.
+//     sb_dist_kernel / sb_update_kernel   float32 distances, d_max, possibility += (1 - d / d_max)^2 weight, and row b of the batch:
+//                        pos, x = [pos, rgb], y, point_idx, through the shuffle.
 //     sb_argmin_partial_kernel / sb_argmin_final_kernel   the chosen cloud's new minimum possibility (:451).
 //   once per call: the B shuffles.  perm_b = stable arg-sort over t of smp_hash(seed, counter, b, 8 + t): ONE sort of the B k hashes
 //   (values b k + t) followed by one stable pass on b -- the crops do not enter, so this is not repeated per crop.
+//   Launches, where a pass of the radix sort is 4 (histogram, two for the scan, scatter: k = 40 960 .. 65 536): 47 per crop --
+//   1 choose + 8 + 1 count + 1 scatter + 8 x 4 + distance + update + 2 arg-min -- + 39 per call for the device's own shuffles
+//   (keys, 8 x 4, crop keys, 1 x 4 for B <= 256, final); the S3DIS form adds per crop only what its table can need.
 //
-//   S3DIS form (datasets/s3dis_dataset.py:343-379, crfconv_possibility_crop_batch_s3dis): the same select and sort for kc = min(n, k)
-//   rows -- a device value; rows kc .. k of the sort's input are all-ones sentinels -- with its own distance / update kernels and the
-//   padding of a short crop to k rows (further down).
+//   Where the forms differ (template argument S3DIS of the choose, scatter, distance and update kernels;
+//   datasets/s3dis_dataset.py:343-379, crfconv_possibility_crop_batch_s3dis): the S3DIS form selects kc = min(n, k) rows -- a device
+//   value; rows kc .. k of the sort's input are all-ones sentinels --, centres all three axes, takes the distances of the float32
+//   centred coordinates, has no point weight, and pads a crop of kc < k rows to k rows through `choice`.
 // Everything is integer counting or singly rounded arithmetic in a fixed order: deterministic, no floating-point atomics.
 #include <cmath>
 
-#include "common.hpp"
+#include "crop_common.hpp"
 #include "radix_sort.hpp"
 
 namespace crf {
 
-constexpr int SB_NT = 256, SB_IPT = 16, SB_TILE = SB_NT * SB_IPT;      // threads per workgroup; points per thread / per tile
+constexpr int SB_NT = CROP_NT, SB_IPT = 16, SB_TILE = SB_NT * SB_IPT;  // threads per workgroup; points per thread / per tile
 constexpr int SB_ARGMIN_BLOCKS = 1024;
 constexpr unsigned long long SMP_DOMAIN = 0x8CB92BA72F3D8DD7ull;       // separates these draws from the subsets' / dropout's / augmentation's
 constexpr int SMP_PERM_SLOT = 8;                                       // slots 0 .. 5: the jitter's uniforms; 8 + t: shuffle key of row t
@@ -65,28 +71,6 @@ struct SbCrop {                   // one crop's device-side decisions; lives in 
     int cloud, pad;
     long long kc;                 // rows of this crop: k, or min(n, k) in the S3DIS form (a small room is taken whole)
 };
-struct SbMin {
-    double v;
-    long long i;
-};
-__device__ __forceinline__ SbMin sb_min_first(SbMin a, SbMin b) { return (b.v < a.v || (b.v == a.v && b.i < a.i)) ? b : a; }
-__device__ __forceinline__ SbMin sb_wave_min(SbMin m) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        SbMin other;
-        other.v = __shfl_xor(m.v, o, WAVE);
-        other.i = __shfl_xor(m.i, o, WAVE);
-        m = sb_min_first(m, other);
-    }
-    return m;
-}
-
-// the key of crop_keys_kernel (evaluate.hip): x then y then z, every operation singly rounded
-__device__ __forceinline__ unsigned long long sb_key(const float* __restrict__ pts, long long i, double cx, double cy, double cz) {
-    const double dx = (double)pts[3 * i] - cx, dy = (double)pts[3 * i + 1] - cy, dz = (double)pts[3 * i + 2] - cz;
-    const double d = dadd_rn(dadd_rn(dmul_rn(dx, dx), dmul_rn(dy, dy)), dmul_rn(dz, dz));
-    return (unsigned long long)__double_as_longlong(d);
-}
 
 template <bool S3DIS>
 __global__ __launch_bounds__(SB_NT) void sb_choose_kernel(const crf_cloud_desc* __restrict__ clouds, int n_clouds,
@@ -99,9 +83,9 @@ __global__ __launch_bounds__(SB_NT) void sb_choose_kernel(const crf_cloud_desc* 
     for (int p = 0; p < 8; ++p) hist[p * 256 + threadIdx.x] = 0;
     if (threadIdx.x >= WAVE) return;
     const int lane = threadIdx.x;
-    SbMin m{1.0 / 0.0, INT64_MAX};
-    for (int c = lane; c < n_clouds; c += WAVE) m = sb_min_first(m, SbMin{minv[c], (long long)c});
-    m = sb_wave_min(m);
+    MinIdx m = min_none();
+    for (int c = lane; c < n_clouds; c += WAVE) m = min_first(m, MinIdx{minv[c], (long long)c});
+    m = wave_min_first(m);
     const int c = m.i < (long long)n_clouds ? (int)m.i : 0;          // (all minima NaN: cloud 0)
     const crf_cloud_desc cd = clouds[c];
     long long pick = mini[c];
@@ -178,7 +162,7 @@ __global__ __launch_bounds__(SB_NT) void sb_hist_kernel(const crf_cloud_desc* __
         bool match = i < n;
         unsigned d = 0;
         if (match) {
-            const unsigned long long key = sb_key(pts, i, cx, cy, cz);
+            const unsigned long long key = crop_key(pts, i, cx, cy, cz);
             if (p > 0) match = (key >> (shift + 8)) == want_hi;
             d = (unsigned)((key >> shift) & 255ull);
         }
@@ -213,7 +197,7 @@ __global__ __launch_bounds__(SB_NT) void sb_count_kernel(const crf_cloud_desc* _
     for (int r = 0; r < SB_IPT; ++r) {
         const long long i = lo + (long long)r * SB_NT + t;
         if (i < n) {
-            const unsigned long long key = sb_key(pts, i, cx, cy, cz);
+            const unsigned long long key = crop_key(pts, i, cx, cy, cz);
             less += key < s.prefix ? 1 : 0;
             eq += key == s.prefix ? 1 : 0;
         }
@@ -234,7 +218,7 @@ __global__ __launch_bounds__(SB_NT) void sb_scatter_kernel(const crf_cloud_desc*
                                                            const int32_t* __restrict__ cnt, long long nb, long long k,
                                                            unsigned long long* __restrict__ keys_out, uint32_t* __restrict__ vals_out) {
     __shared__ long long s_b[SB_NT / WAVE][2];
-    __shared__ int s_c[SB_NT / WAVE][2];
+    __shared__ int s_l[SB_NT / WAVE], s_e[SB_NT / WAVE];
     const long long n = st->n, lo = (long long)blockIdx.x * SB_TILE;
     if constexpr (S3DIS) {                                             // rows kc .. k of the sort's input: sentinels that sort last
         const long long kc = st->kc;
@@ -261,29 +245,19 @@ __global__ __launch_bounds__(SB_NT) void sb_scatter_kernel(const crf_cloud_desc*
     if (bl >= L && be >= want) return;                                  // uniform: nothing of this tile is taken
     const float* __restrict__ pts = clouds[st->cloud].points;
     const double cx = st->center[0], cy = st->center[1], cz = st->center[2];
-    const unsigned long long lt = (1ull << lane) - 1ull;
     for (int r = 0; r < SB_IPT; ++r) {
         const long long i = lo + (long long)r * SB_NT + t;
         unsigned long long key = ~0ull;
-        if (i < n) key = sb_key(pts, i, cx, cy, cz);
+        if (i < n) key = crop_key(pts, i, cx, cy, cz);
         const bool less = i < n && key < kth, eq = i < n && key == kth;
-        const unsigned long long ml = __ballot(less), me = __ballot(eq);
-        if (lane == 0) { s_c[wave][0] = __popcll(ml); s_c[wave][1] = __popcll(me); }
+        const unsigned long long ml = compact_count(less, s_l), me = compact_count(eq, s_e);
         __syncthreads();
-        long long sl = bl, se = be;
-        int tl = 0, te = 0;
-#pragma unroll
-        for (int w = 0; w < SB_NT / WAVE; ++w) {
-            if (w < wave) { sl += s_c[w][0]; se += s_c[w][1]; }
-            tl += s_c[w][0];
-            te += s_c[w][1];
-        }
+        int tl, te;
+        const long long sl = compact_slot(ml, s_l, bl, tl), se = compact_slot(me, s_e, be, te);
         if (less) {
-            const long long slot = sl + __popcll(ml & lt);
-            if (slot < L) { keys_out[slot] = key; vals_out[slot] = (uint32_t)i; }
+            if (sl < L) { keys_out[sl] = key; vals_out[sl] = (uint32_t)i; }
         } else if (eq) {
-            const long long e = se + __popcll(me & lt);
-            if (e < want) { keys_out[L + e] = key; vals_out[L + e] = (uint32_t)i; }
+            if (se < want) { keys_out[L + se] = key; vals_out[L + se] = (uint32_t)i; }
         }
         bl += tl;
         be += te;
@@ -291,105 +265,79 @@ __global__ __launch_bounds__(SB_NT) void sb_scatter_kernel(const crf_cloud_desc*
     }
 }
 
-// crop_dist_kernel of evaluate.hip, the cloud taken from the crop's descriptor
+// dist[t] = the update's float32 distance of selected row t (crop_row_dist) and the workgroup maxima; S3DIS: rows kc .. k hold 0
+template <bool S3DIS>
 __global__ __launch_bounds__(SB_NT) void sb_dist_kernel(const crf_cloud_desc* __restrict__ clouds, const SbCrop* __restrict__ st,
                                                         const uint32_t* __restrict__ sel, long long k, float* __restrict__ dist,
                                                         float* __restrict__ pmax) {
-    __shared__ float s_red[SB_NT / WAVE];
     const long long t = (long long)blockIdx.x * SB_NT + threadIdx.x;
     const float* __restrict__ points = clouds[st->cloud].points;
     float d = 0.f;
     if (t < k) {
         const long long i = sel[t];
-        if (i < st->n) {
-            const double dx = (double)points[3 * i] - st->center[0], dy = (double)points[3 * i + 1] - st->center[1],
-                         dz = (double)points[3 * i + 2] - st->center[2];
-            d = add_rn(add_rn((float)dmul_rn(dx, dx), (float)dmul_rn(dy, dy)), (float)dmul_rn(dz, dz));
-        }
+        if ((!S3DIS || t < st->kc) && i < st->n) d = crop_row_dist<S3DIS>(points, i, st->center);
         dist[t] = d;
     }
-    float mx = d;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, WAVE));
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < SB_NT / WAVE; ++w) mx = fmaxf(mx, s_red[w]);
-        pmax[blockIdx.x] = mx;
-    }
+    block_max_to(d, pmax);
 }
 
-// crop_update_kernel of evaluate.hip + the gathers of labels and colours, into row b of the batch
+// possibility += (1 - d / d_max)^2 [weight] over the crop's DISTINCT rows and row t of the batch through the shuffle.
+//   Semantic3D: row t shows selected element perm[t], and that element's possibility is updated by the same thread.
+//   S3DIS (s3dis_dataset.py:364-365, :357, :375-377): thread t < kc updates selected element t, weight 1; row t of the batch = row
+//   choice[t] of the shuffled crop = selected element perm[choice[t]], perm the device's own shuffle restricted to kc rows
+//   (perm_compact) when the crop is short.  kc == k: choice is the identity and is not read.
+template <bool S3DIS>
 __global__ __launch_bounds__(SB_NT) void sb_update_kernel(const crf_cloud_desc* __restrict__ clouds, const SbCrop* __restrict__ st,
-                                                          const uint32_t* __restrict__ sel, const int64_t* __restrict__ perm, long long k,
-                                                          const float* __restrict__ dist, const float* __restrict__ pmax, int nblk,
-                                                          float* __restrict__ out_pos, float* __restrict__ out_x, int xc,
+                                                          const uint32_t* __restrict__ sel, const int64_t* __restrict__ perm,
+                                                          const int64_t* __restrict__ perm_compact, const int64_t* __restrict__ choice,
+                                                          long long k, const float* __restrict__ dist, const float* __restrict__ pmax,
+                                                          int nblk, float* __restrict__ out_pos, float* __restrict__ out_x, int xc,
                                                           int64_t* __restrict__ out_y, int64_t* __restrict__ out_idx) {
     const long long t = (long long)blockIdx.x * SB_NT + threadIdx.x;
     if (t >= k) return;
     const crf_cloud_desc cd = clouds[st->cloud];
-    float dmax = pmax[0];
-    for (int b = 1; b < nblk; ++b) dmax = fmaxf(dmax, pmax[b]);
-    const long long src = perm ? perm[t] : t;               // output row t shows selected element perm[t] (the shuffle)
-    if (src < 0 || src >= k) return;
+    long long kc = k, s = t;
+    if constexpr (S3DIS) {
+        kc = st->kc;
+        if (t < kc) {
+            const long long j = sel[t];
+            if (j < cd.n) cd.possibility[j] += (double)crop_gain(dist[t], crop_dmax(pmax, nblk));
+        }
+        if (kc < k) {
+            if (choice == nullptr) return;
+            s = choice[t];
+            if (perm_compact != nullptr) perm = perm_compact;
+        }
+        if (s < 0 || s >= kc) return;
+    }
+    const long long src = perm ? perm[s] : s;
+    if (src < 0 || src >= kc) return;
     const long long i = sel[src];
     if (i >= cd.n) return;
-    const float u = sub_rn(1.0f, __fdiv_rn(dist[src], dmax));
-    const float sq = mul_rn(u, u);
-    const double delta = cd.point_weight ? dmul_rn((double)sq, cd.point_weight[i]) : (double)sq;
-    cd.possibility[i] += delta;                              // rows of a crop are distinct points
-    const float px = (float)((double)cd.points[3 * i + 0] - st->center[0]);
-    const float py = (float)((double)cd.points[3 * i + 1] - st->center[1]);
-    const float pz = cd.points[3 * i + 2];
-    out_pos[3 * t + 0] = px;
-    out_pos[3 * t + 1] = py;
-    out_pos[3 * t + 2] = pz;
-    if (out_x != nullptr) {
-        float* xr = out_x + (size_t)t * xc;
-        xr[0] = px; xr[1] = py; xr[2] = pz;
-        if (xc == 6) {
-            xr[3] = cd.rgb ? cd.rgb[3 * i + 0] : 0.f;
-            xr[4] = cd.rgb ? cd.rgb[3 * i + 1] : 0.f;
-            xr[5] = cd.rgb ? cd.rgb[3 * i + 2] : 0.f;
-        }
+    if constexpr (!S3DIS) {
+        const float sq = crop_gain(dist[src], crop_dmax(pmax, nblk));
+        cd.possibility[i] += cd.point_weight ? dmul_rn((double)sq, cd.point_weight[i]) : (double)sq;
     }
-    if (out_y != nullptr) out_y[t] = cd.labels ? cd.labels[i] : 0;
-    if (out_idx != nullptr) out_idx[t] = i;
+    crop_write_row<S3DIS>(cd.points, cd.rgb, cd.labels, i, st->center, t, out_pos, out_x, xc, out_y, out_idx);
 }
 
 __global__ __launch_bounds__(SB_NT) void sb_argmin_partial_kernel(const crf_cloud_desc* __restrict__ clouds, const SbCrop* __restrict__ st,
                                                                   double* __restrict__ pv, int64_t* __restrict__ pi) {
-    __shared__ double s_v[SB_NT / WAVE];
-    __shared__ long long s_i[SB_NT / WAVE];
     const double* __restrict__ v = clouds[st->cloud].possibility;
     const long long n = st->n;
-    SbMin m{1.0 / 0.0, INT64_MAX};
+    MinIdx m = min_none();
     for (long long i = (long long)blockIdx.x * SB_NT + threadIdx.x; i < n; i += (long long)gridDim.x * SB_NT)
-        m = sb_min_first(m, SbMin{v[i], i});
-    m = sb_wave_min(m);
-    if ((threadIdx.x & 63) == 0) { s_v[threadIdx.x >> 6] = m.v; s_i[threadIdx.x >> 6] = m.i; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < SB_NT / WAVE; ++w) m = sb_min_first(m, SbMin{s_v[w], s_i[w]});
-        pv[blockIdx.x] = m.v;
-        pi[blockIdx.x] = m.i;
-    }
+        m = min_first(m, MinIdx{v[i], i});
+    m = block_min_first(m);
+    if (threadIdx.x == 0) { pv[blockIdx.x] = m.v; pi[blockIdx.x] = m.i; }
 }
 __global__ __launch_bounds__(SB_NT) void sb_argmin_final_kernel(const SbCrop* __restrict__ st, const double* __restrict__ pv,
                                                                 const int64_t* __restrict__ pi, int nblk, double* __restrict__ minv,
                                                                 int64_t* __restrict__ mini) {
-    __shared__ double s_v[SB_NT / WAVE];
-    __shared__ long long s_i[SB_NT / WAVE];
-    SbMin m{1.0 / 0.0, INT64_MAX};
-    for (int b = threadIdx.x; b < nblk; b += SB_NT) m = sb_min_first(m, SbMin{pv[b], (long long)pi[b]});
-    m = sb_wave_min(m);
-    if ((threadIdx.x & 63) == 0) { s_v[threadIdx.x >> 6] = m.v; s_i[threadIdx.x >> 6] = m.i; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < SB_NT / WAVE; ++w) m = sb_min_first(m, SbMin{s_v[w], s_i[w]});
-        minv[st->cloud] = m.v;
-        mini[st->cloud] = m.i;
-    }
+    MinIdx m = min_none();
+    for (int b = threadIdx.x; b < nblk; b += SB_NT) m = min_first(m, MinIdx{pv[b], (long long)pi[b]});
+    m = block_min_first(m);
+    if (threadIdx.x == 0) { minv[st->cloud] = m.v; mini[st->cloud] = m.i; }
 }
 
 // ---- the shuffles
@@ -416,89 +364,8 @@ __global__ __launch_bounds__(SB_NT) void sb_perm_final_kernel(const uint32_t* __
     if (perm_out != nullptr) perm_out[i] = v;
 }
 
-// ---- the S3DIS form (datasets/s3dis_dataset.py:343-379): all three axes centred, float32 distances of the float32 centred
-// coordinates, weight 1, a room smaller than k taken whole (kc = n rows) and padded to k rows by `choice`.
+// ---- the padding of the S3DIS form: a room smaller than k is taken whole (kc = n rows) and padded to k rows by `choice`.
 constexpr unsigned long long SMP_CHOICE_SLOT = 1ull << 32;             // slot (j + 1) 2^32 + t: padding key of element t of block j
-
-// np.sum(np.square(query_xyz.astype(np.float32)), axis=1) (:363): x x + y y + z z in float32, every operation rounded once
-__global__ __launch_bounds__(SB_NT) void sb_dist_s3dis_kernel(const crf_cloud_desc* __restrict__ clouds, const SbCrop* __restrict__ st,
-                                                              const uint32_t* __restrict__ sel, long long k, float* __restrict__ dist,
-                                                              float* __restrict__ pmax) {
-    __shared__ float s_red[SB_NT / WAVE];
-    const long long t = (long long)blockIdx.x * SB_NT + threadIdx.x;
-    const float* __restrict__ points = clouds[st->cloud].points;
-    float d = 0.f;
-    if (t < k) {
-        const long long i = sel[t];
-        if (t < st->kc && i < st->n) {
-            const float px = (float)((double)points[3 * i] - st->center[0]), py = (float)((double)points[3 * i + 1] - st->center[1]),
-                        pz = (float)((double)points[3 * i + 2] - st->center[2]);
-            d = add_rn(add_rn(mul_rn(px, px), mul_rn(py, py)), mul_rn(pz, pz));
-        }
-        dist[t] = d;
-    }
-    float mx = d;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, WAVE));
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < SB_NT / WAVE; ++w) mx = fmaxf(mx, s_red[w]);
-        pmax[blockIdx.x] = mx;
-    }
-}
-
-// possibility[query_idx] += (1 - d / d_max)^2 over the kc DISTINCT rows of the crop (:364-365), then row t of the batch = row
-// choice[t] of the shuffled crop = selected element perm[choice[t]] (:357, :375-377).  kc == k: choice is the identity.
-__global__ __launch_bounds__(SB_NT) void sb_update_s3dis_kernel(const crf_cloud_desc* __restrict__ clouds, const SbCrop* __restrict__ st,
-                                                                const uint32_t* __restrict__ sel, const int64_t* __restrict__ perm,
-                                                                const int64_t* __restrict__ perm_compact,
-                                                                const int64_t* __restrict__ choice, long long k,
-                                                                const float* __restrict__ dist, const float* __restrict__ pmax, int nblk,
-                                                                float* __restrict__ out_pos, float* __restrict__ out_x, int xc,
-                                                                int64_t* __restrict__ out_y, int64_t* __restrict__ out_idx) {
-    const long long t = (long long)blockIdx.x * SB_NT + threadIdx.x;
-    if (t >= k) return;
-    const crf_cloud_desc cd = clouds[st->cloud];
-    const long long kc = st->kc;
-    if (t < kc) {
-        float dmax = pmax[0];
-        for (int b = 1; b < nblk; ++b) dmax = fmaxf(dmax, pmax[b]);
-        const long long j = sel[t];
-        if (j < cd.n) {
-            const float u = sub_rn(1.0f, __fdiv_rn(dist[t], dmax));
-            cd.possibility[j] += (double)mul_rn(u, u);              // the kc selected rows are distinct points
-        }
-    }
-    long long s = t;
-    if (kc < k) {
-        if (choice == nullptr) return;
-        s = choice[t];
-    }
-    if (s < 0 || s >= kc) return;
-    if (kc < k && perm_compact != nullptr) perm = perm_compact;     // the device's own shuffle, restricted to kc rows
-    const long long src = perm ? perm[s] : s;
-    if (src < 0 || src >= kc) return;
-    const long long i = sel[src];
-    if (i >= cd.n) return;
-    const float px = (float)((double)cd.points[3 * i + 0] - st->center[0]);
-    const float py = (float)((double)cd.points[3 * i + 1] - st->center[1]);
-    const float pz = (float)((double)cd.points[3 * i + 2] - st->center[2]);
-    out_pos[3 * t + 0] = px;
-    out_pos[3 * t + 1] = py;
-    out_pos[3 * t + 2] = pz;
-    if (out_x != nullptr) {
-        float* xr = out_x + (size_t)t * xc;
-        xr[0] = px; xr[1] = py; xr[2] = pz;
-        if (xc == 6) {
-            xr[3] = cd.rgb ? cd.rgb[3 * i + 0] : 0.f;
-            xr[4] = cd.rgb ? cd.rgb[3 * i + 1] : 0.f;
-            xr[5] = cd.rgb ? cd.rgb[3 * i + 2] : 0.f;
-        }
-    }
-    if (out_y != nullptr) out_y[t] = cd.labels ? cd.labels[i] : 0;
-    if (out_idx != nullptr) out_idx[t] = i;
-}
 
 // The shuffle of a crop of kc < k rows: the stable ranking of the first kc hashes of row b = the entries below kc of the row's full
 // arg-sort, in their order.  One workgroup, order-preserving compaction; perm_out (or NULL) <- the kc entries, then -1.
@@ -506,7 +373,7 @@ __global__ __launch_bounds__(SB_NT) void sb_perm_compact_kernel(const SbCrop* __
                                                                 int64_t* __restrict__ compact, int64_t* __restrict__ perm_out) {
     __shared__ int s_c[SB_NT / WAVE];
     const long long kc = st->kc;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     if (kc >= k) {
         if (perm_out != nullptr)
             for (long long i = t; i < k; i += SB_NT) perm_out[i] = full[i];
@@ -517,18 +384,11 @@ __global__ __launch_bounds__(SB_NT) void sb_perm_compact_kernel(const SbCrop* __
         const long long i = lo + t;
         const long long v = i < k ? full[i] : k;
         const bool keep = v < kc;
-        const unsigned long long m = __ballot(keep);
-        if (lane == 0) s_c[wave] = __popcll(m);
+        const unsigned long long m = compact_count(keep, s_c);
         __syncthreads();
-        long long slot = base;
-        int total = 0;
-#pragma unroll
-        for (int w = 0; w < SB_NT / WAVE; ++w) {
-            if (w < wave) slot += s_c[w];
-            total += s_c[w];
-        }
+        int total;
+        const long long slot = compact_slot(m, s_c, base, total);
         if (keep) {
-            slot += __popcll(m & ((1ull << lane) - 1ull));
             compact[slot] = v;
             if (perm_out != nullptr) perm_out[slot] = v;
         }
@@ -569,52 +429,69 @@ __global__ __launch_bounds__(SB_NT) void sb_choice_final_kernel(const SbCrop* __
     if (choice_out != nullptr) choice_out[t] = v;
 }
 
-static size_t sb_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct SbLayout {
-    size_t crop, hist, cnt, keys_a, keys_b, vals_a, vals_b, dist, pmax, pv, pi, sort, pkeys_a, pkeys_b, pvals_a, pvals_b, perm, psort, total;
-    size_t compact, choice, ckeys_a, ckeys_b, cvals_a, cvals_b, csort;      // the S3DIS form only
+struct SbWs {                     // the workspace of one call; the last seven pieces exist in the S3DIS form only
+    SbCrop* crop;
+    int32_t *hist, *cnt;
+    unsigned long long *keys_a, *keys_b;
+    uint32_t *vals_a, *vals_b;
+    float *dist, *pmax;
+    double* pv;
+    int64_t* pi;
+    char* sort;
+    unsigned long long *pkeys_a, *pkeys_b;
+    uint32_t *pvals_a, *pvals_b;
+    int64_t* perm;
+    char* psort;
+    int64_t *compact = nullptr, *choice = nullptr;
+    unsigned long long *ckeys_a = nullptr, *ckeys_b = nullptr;
+    uint32_t *cvals_a = nullptr, *cvals_b = nullptr;
+    char* csort = nullptr;
+    size_t bytes;
 };
-static SbLayout sb_layout(int64_t n_max, int64_t k, int64_t B, bool s3dis = false) {
-    SbLayout l;
-    size_t o = 0;
-    auto take = [&o](size_t bytes) { const size_t at = o; o += sb_align(bytes); return at; };
-    const size_t nb = (size_t)cdiv(n_max, SB_TILE), kk = (size_t)k, bk = (size_t)(B * k);
-    l.crop = take(sizeof(SbCrop));
-    l.hist = take(8 * 256 * sizeof(int32_t));
-    l.cnt = take(2 * nb * sizeof(int32_t));
-    l.keys_a = take(8 * kk);
-    l.keys_b = take(8 * kk);
-    l.vals_a = take(4 * kk);
-    l.vals_b = take(4 * kk);
-    l.dist = take(4 * kk);
-    l.pmax = take(4 * (size_t)cdiv(k, SB_NT));
-    l.pv = take(8 * SB_ARGMIN_BLOCKS);
-    l.pi = take(8 * SB_ARGMIN_BLOCKS);
-    l.sort = take(rsort_workspace(k));
-    l.pkeys_a = take(8 * bk);
-    l.pkeys_b = take(8 * bk);
-    l.pvals_a = take(4 * bk);
-    l.pvals_b = take(4 * bk);
-    l.perm = take(8 * bk);
-    l.psort = take(rsort_workspace(B * k));
-    l.compact = l.choice = l.ckeys_a = l.ckeys_b = l.cvals_a = l.cvals_b = l.csort = 0;
+static SbWs sb_carve(void* workspace, int64_t n_max, int64_t k, int64_t B, bool s3dis) {
+    Carve c(workspace);
+    SbWs w;
+    const size_t kk = (size_t)k, bk = (size_t)(B * k);
+    w.crop = c.take<SbCrop>(1);
+    w.hist = c.take<int32_t>(8 * 256);
+    w.cnt = c.take<int32_t>(2 * (size_t)cdiv(n_max, SB_TILE));
+    w.keys_a = c.take<unsigned long long>(kk);
+    w.keys_b = c.take<unsigned long long>(kk);
+    w.vals_a = c.take<uint32_t>(kk);
+    w.vals_b = c.take<uint32_t>(kk);
+    w.dist = c.take<float>(kk);
+    w.pmax = c.take<float>((size_t)cdiv(k, SB_NT));
+    w.pv = c.take<double>(SB_ARGMIN_BLOCKS);
+    w.pi = c.take<int64_t>(SB_ARGMIN_BLOCKS);
+    w.sort = c.take<char>(rsort_workspace(k));
+    w.pkeys_a = c.take<unsigned long long>(bk);
+    w.pkeys_b = c.take<unsigned long long>(bk);
+    w.pvals_a = c.take<uint32_t>(bk);
+    w.pvals_b = c.take<uint32_t>(bk);
+    w.perm = c.take<int64_t>(bk);
+    w.psort = c.take<char>(rsort_workspace(B * k));
     if (s3dis) {
-        l.compact = take(8 * kk);
-        l.choice = take(8 * kk);
-        l.ckeys_a = take(16 * kk);
-        l.ckeys_b = take(16 * kk);
-        l.cvals_a = take(8 * kk);
-        l.cvals_b = take(8 * kk);
-        l.csort = take(rsort_workspace(2 * k));
+        w.compact = c.take<int64_t>(kk);
+        w.choice = c.take<int64_t>(kk);
+        w.ckeys_a = c.take<unsigned long long>(2 * kk);      // the padding's sort: 2 k pairs
+        w.ckeys_b = c.take<unsigned long long>(2 * kk);
+        w.cvals_a = c.take<uint32_t>(2 * kk);
+        w.cvals_b = c.take<uint32_t>(2 * kk);
+        w.csort = c.take<char>(rsort_workspace(2 * k));
     }
-    l.total = o + 256;                                                 // (room to align the caller's pointer)
-    return l;
+    w.bytes = c.bytes();
+    return w;
 }
 
 }  // namespace crf
 
 using namespace crf;
+
+#define SB_LAUNCH(kernel, grid, ...)                                     \
+    do {                                                                 \
+        hipLaunchKernelGGL(kernel, grid, blk, 0, st, __VA_ARGS__);       \
+        CRF_LAUNCH_CHECK();                                              \
+    } while (0)
 
 // Both forms.  s3dis: kc = min(n, k) rows per crop on the device, padded through choice; n_min (the smallest cloud, a property of the
 // table the host knows) >= k means no crop is ever padded and the padding's sort is not enqueued.
@@ -634,163 +511,92 @@ static int sb_run(bool s3dis, const crf_cloud_desc* clouds, int n_clouds, int64_
     CRF_REQUIRE(counter != nullptr || (noise_in != nullptr && (perm_in != nullptr || identity_perm) && (!padded || choice_in != nullptr)),
                 CRF_ERR_ARG, "a counter is needed unless noise_in, the shuffle and (with a cloud below k) the padding are given");
     CRF_REQUIRE(!(perm_in != nullptr && identity_perm), CRF_ERR_ARG, "perm_in and identity_perm exclude each other");
-    const size_t need = sb_layout(n_max, k, B, s3dis).total;
-    CRF_REQUIRE(workspace_bytes >= need, CRF_ERR_WORKSPACE, "possibility_crop_batch workspace %zu < %zu", workspace_bytes, need);
+    const SbWs w = sb_carve(workspace, n_max, k, B, s3dis);
+    CRF_REQUIRE(workspace_bytes >= w.bytes, CRF_ERR_WORKSPACE, "possibility_crop_batch workspace %zu < %zu", workspace_bytes, w.bytes);
     hipStream_t st = as_stream(stream);
-    const SbLayout l = sb_layout(n_max, k, B, s3dis);
-    char* ws = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-    auto at = [ws](size_t off) { return ws + off; };
-    auto* crop = reinterpret_cast<SbCrop*>(at(l.crop));
-    auto* hist = reinterpret_cast<int32_t*>(at(l.hist));
-    auto* cnt = reinterpret_cast<int32_t*>(at(l.cnt));
-    auto* keys_a = reinterpret_cast<unsigned long long*>(at(l.keys_a));
-    auto* keys_b = reinterpret_cast<unsigned long long*>(at(l.keys_b));
-    auto* vals_a = reinterpret_cast<uint32_t*>(at(l.vals_a));
-    auto* vals_b = reinterpret_cast<uint32_t*>(at(l.vals_b));
-    auto* dist = reinterpret_cast<float*>(at(l.dist));
-    auto* pmax = reinterpret_cast<float*>(at(l.pmax));
-    auto* pv = reinterpret_cast<double*>(at(l.pv));
-    auto* pi = reinterpret_cast<int64_t*>(at(l.pi));
-    auto* pkeys_a = reinterpret_cast<unsigned long long*>(at(l.pkeys_a));
-    auto* pkeys_b = reinterpret_cast<unsigned long long*>(at(l.pkeys_b));
-    auto* pvals_a = reinterpret_cast<uint32_t*>(at(l.pvals_a));
-    auto* pvals_b = reinterpret_cast<uint32_t*>(at(l.pvals_b));
-    auto* perm_ws = reinterpret_cast<int64_t*>(at(l.perm));
-
     const int64_t total = B * k;
-    const dim3 blk(SB_NT);
+    const dim3 blk(SB_NT), one(1);
+    const unsigned long long useed = (unsigned long long)seed;
+
+    // ---- once per call: the shuffles
     const int64_t* perm = perm_in;
     if (perm_in == nullptr && !identity_perm) {
         const dim3 pgrid((unsigned)cdiv(total, SB_NT));
-        hipLaunchKernelGGL(sb_perm_keys_kernel, pgrid, blk, 0, st, (unsigned long long)seed, counter, (long long)k, (long long)total,
-                           pkeys_a, pvals_a);
+        SB_LAUNCH(sb_perm_keys_kernel, pgrid, useed, counter, (long long)k, (long long)total, w.pkeys_a, w.pvals_a);
+        const int where = rsort_pairs_u64(w.pkeys_a, w.pvals_a, w.pkeys_b, w.pvals_b, total, 0, 64, w.psort, st);
         CRF_LAUNCH_CHECK();
-        int where = rsort_pairs_u64(pkeys_a, pvals_a, pkeys_b, pvals_b, total, 0, 64, at(l.psort), st);
-        CRF_LAUNCH_CHECK();
+        const uint32_t* sorted = where ? w.pvals_b : w.pvals_a;
         if (B > 1) {                                                   // one stable pass on the crop number: B sorted runs of k
-            unsigned long long* ka = where ? pkeys_b : pkeys_a;
-            unsigned long long* kb = where ? pkeys_a : pkeys_b;
-            uint32_t* va = where ? pvals_b : pvals_a;
-            uint32_t* vb = where ? pvals_a : pvals_b;
-            hipLaunchKernelGGL(sb_perm_crop_keys_kernel, pgrid, blk, 0, st, va, (long long)k, (long long)total, ka);
+            unsigned long long* ka = where ? w.pkeys_b : w.pkeys_a;
+            unsigned long long* kb = where ? w.pkeys_a : w.pkeys_b;
+            uint32_t* va = where ? w.pvals_b : w.pvals_a;
+            uint32_t* vb = where ? w.pvals_a : w.pvals_b;
+            SB_LAUNCH(sb_perm_crop_keys_kernel, pgrid, (const uint32_t*)va, (long long)k, (long long)total, ka);
+            sorted = rsort_pairs_u64(ka, va, kb, vb, total, 0, B > 256 ? 16 : 8, w.psort, st) ? vb : va;
             CRF_LAUNCH_CHECK();
-            const int w2 = rsort_pairs_u64(ka, va, kb, vb, total, 0, B > 256 ? 16 : 8, at(l.psort), st);
-            CRF_LAUNCH_CHECK();
-            pvals_a = w2 ? vb : va;
-        } else if (where) {
-            pvals_a = pvals_b;
         }
         // (S3DIS form: the rows of perm_out are written per crop, cut to the crop's own row count)
-        hipLaunchKernelGGL(sb_perm_final_kernel, pgrid, blk, 0, st, pvals_a, (long long)k, (long long)total, perm_ws,
-                           s3dis ? (int64_t*)nullptr : perm_out);
-        CRF_LAUNCH_CHECK();
-        perm = perm_ws;
+        SB_LAUNCH(sb_perm_final_kernel, pgrid, sorted, (long long)k, (long long)total, w.perm, s3dis ? (int64_t*)nullptr : perm_out);
+        perm = w.perm;
     } else if (perm_out != nullptr && perm_in != nullptr) {
         CRF_HIP(hipMemcpyAsync(perm_out, perm_in, sizeof(int64_t) * (size_t)total, hipMemcpyDeviceToDevice, st));
     }
-
-    const int64_t nb = cdiv(n_max, SB_TILE);
-    const int nblk = (int)cdiv(k, SB_NT);
-    int64_t ablocks = cdiv(n_max, SB_NT);
-    if (ablocks > SB_ARGMIN_BLOCKS) ablocks = SB_ARGMIN_BLOCKS;
-    const dim3 sgrid((unsigned)nb), kgrid((unsigned)nblk);
-    auto* compact = reinterpret_cast<int64_t*>(at(l.compact));
-    auto* choice_ws = reinterpret_cast<int64_t*>(at(l.choice));
-    const bool own_perm = perm == perm_ws;
-    int choice_bits = 32;                                              // sort key of the padding: (block j, upper hash half); j < k
-    while (choice_bits < 64 && (k >> (choice_bits - 32)) != 0) choice_bits += 8;
     if (s3dis && choice_in != nullptr && choice_out != nullptr)
         CRF_HIP(hipMemcpyAsync(choice_out, choice_in, sizeof(int64_t) * (size_t)total, hipMemcpyDeviceToDevice, st));
+
+    // ---- per crop
+    const int64_t nb = cdiv(n_max, SB_TILE);
+    const int nblk = (int)cdiv(k, SB_NT);
+    const int ablocks = (int)(cdiv(n_max, SB_NT) < SB_ARGMIN_BLOCKS ? cdiv(n_max, SB_NT) : SB_ARGMIN_BLOCKS);
+    const dim3 sgrid((unsigned)nb), kgrid((unsigned)nblk);
+    const bool own_perm = perm == w.perm;
+    int choice_bits = 32;                                              // sort key of the padding: (block j, upper hash half); j < k
+    while (choice_bits < 64 && (k >> (choice_bits - 32)) != 0) choice_bits += 8;
+    const auto choose_kernel = s3dis ? sb_choose_kernel<true> : sb_choose_kernel<false>;
+    const auto scatter_kernel = s3dis ? sb_scatter_kernel<true> : sb_scatter_kernel<false>;
+    const auto dist_kernel = s3dis ? sb_dist_kernel<true> : sb_dist_kernel<false>;
+    const auto update_kernel = s3dis ? sb_update_kernel<true> : sb_update_kernel<false>;
+    const SbCrop* crop = w.crop;
     for (int64_t b = 0; b < B; ++b) {
-        if (s3dis) {
-            hipLaunchKernelGGL(sb_choose_kernel<true>, dim3(1), blk, 0, st, clouds, n_clouds, (const double*)min_value,
-                               (const int64_t*)min_index, (unsigned long long)seed, counter, (int)b, (long long)k, noise_scale, noise_in,
-                               crop, hist, noise_out, out_center, out_cloud_idx);
-            CRF_LAUNCH_CHECK();
-            for (int p = 0; p < 8; ++p) {
-                hipLaunchKernelGGL(sb_hist_kernel, sgrid, blk, 0, st, clouds, crop, hist, p);
-                CRF_LAUNCH_CHECK();
-            }
-            hipLaunchKernelGGL(sb_count_kernel, sgrid, blk, 0, st, clouds, crop, (const int32_t*)hist, cnt, (long long)nb);
-            CRF_LAUNCH_CHECK();
-            hipLaunchKernelGGL(sb_scatter_kernel<true>, sgrid, blk, 0, st, clouds, (const SbCrop*)crop, (const int32_t*)cnt, (long long)nb,
-                               (long long)k, keys_a, vals_a);
-            CRF_LAUNCH_CHECK();
-            const uint32_t* sel = rsort_pairs_u64(keys_a, vals_a, keys_b, vals_b, k, 0, 64, at(l.sort), st) ? vals_b : vals_a;
-            CRF_LAUNCH_CHECK();
-            if (own_perm && (padded || perm_out != nullptr)) {
-                hipLaunchKernelGGL(sb_perm_compact_kernel, dim3(1), blk, 0, st, (const SbCrop*)crop, perm + b * k, (long long)k, compact,
-                                   perm_out ? perm_out + b * k : (int64_t*)nullptr);
-                CRF_LAUNCH_CHECK();
-            }
-            const int64_t* choice = choice_in ? choice_in + b * k : (const int64_t*)nullptr;
+        auto row = [b, k](auto* p, int64_t width = 1) { return p ? p + b * k * width : p; };      // crop b's rows of a [B, k, width] array
+        SB_LAUNCH(choose_kernel, one, clouds, n_clouds, (const double*)min_value, (const int64_t*)min_index, useed, counter, (int)b,
+                  (long long)k, noise_scale, noise_in, w.crop, w.hist, noise_out, out_center, out_cloud_idx);
+        for (int p = 0; p < 8; ++p) SB_LAUNCH(sb_hist_kernel, sgrid, clouds, w.crop, w.hist, p);
+        SB_LAUNCH(sb_count_kernel, sgrid, clouds, w.crop, (const int32_t*)w.hist, w.cnt, (long long)nb);
+        SB_LAUNCH(scatter_kernel, sgrid, clouds, crop, (const int32_t*)w.cnt, (long long)nb, (long long)k, w.keys_a, w.vals_a);
+        const uint32_t* sel = rsort_pairs_u64(w.keys_a, w.vals_a, w.keys_b, w.vals_b, k, 0, 64, w.sort, st) ? w.vals_b : w.vals_a;
+        CRF_LAUNCH_CHECK();
+        const int64_t* choice = nullptr;
+        if (s3dis) {                                                   // the padding of a short crop
+            if (own_perm && (padded || perm_out != nullptr))
+                SB_LAUNCH(sb_perm_compact_kernel, one, crop, row(perm), (long long)k, w.compact, row(perm_out));
+            choice = row(choice_in);
             if (choice_in == nullptr && (padded || choice_out != nullptr)) {
                 const uint32_t* cv = nullptr;
                 if (padded) {
-                    auto* cka = reinterpret_cast<unsigned long long*>(at(l.ckeys_a));
-                    auto* ckb = reinterpret_cast<unsigned long long*>(at(l.ckeys_b));
-                    auto* cva = reinterpret_cast<uint32_t*>(at(l.cvals_a));
-                    auto* cvb = reinterpret_cast<uint32_t*>(at(l.cvals_b));
-                    hipLaunchKernelGGL(sb_choice_keys_kernel, dim3((unsigned)cdiv(2 * k, SB_NT)), blk, 0, st, (const SbCrop*)crop,
-                                       (unsigned long long)seed, counter, (int)b, (long long)k, cka, cva);
-                    CRF_LAUNCH_CHECK();
-                    cv = rsort_pairs_u64(cka, cva, ckb, cvb, 2 * k, 0, choice_bits, at(l.csort), st) ? cvb : cva;
+                    SB_LAUNCH(sb_choice_keys_kernel, dim3((unsigned)cdiv(2 * k, SB_NT)), crop, useed, counter, (int)b, (long long)k,
+                              w.ckeys_a, w.cvals_a);
+                    cv = rsort_pairs_u64(w.ckeys_a, w.cvals_a, w.ckeys_b, w.cvals_b, 2 * k, 0, choice_bits, w.csort, st) ? w.cvals_b : w.cvals_a;
                     CRF_LAUNCH_CHECK();
                 }
-                hipLaunchKernelGGL(sb_choice_final_kernel, kgrid, blk, 0, st, (const SbCrop*)crop, cv, (long long)k, choice_ws,
-                                   choice_out ? choice_out + b * k : (int64_t*)nullptr);
-                CRF_LAUNCH_CHECK();
-                choice = choice_ws;
+                SB_LAUNCH(sb_choice_final_kernel, kgrid, crop, cv, (long long)k, w.choice, row(choice_out));
+                choice = w.choice;
             }
-            hipLaunchKernelGGL(sb_dist_s3dis_kernel, kgrid, blk, 0, st, clouds, (const SbCrop*)crop, sel, (long long)k, dist, pmax);
-            CRF_LAUNCH_CHECK();
-            hipLaunchKernelGGL(sb_update_s3dis_kernel, kgrid, blk, 0, st, clouds, (const SbCrop*)crop, sel,
-                               perm ? perm + b * k : (const int64_t*)nullptr, own_perm && padded ? (const int64_t*)compact : (const int64_t*)nullptr,
-                               choice, (long long)k, (const float*)dist, (const float*)pmax, nblk, out_pos + (size_t)b * k * 3,
-                               out_x ? out_x + (size_t)b * k * x_channels : (float*)nullptr, x_channels,
-                               out_y ? out_y + b * k : (int64_t*)nullptr, out_point_idx ? out_point_idx + b * k : (int64_t*)nullptr);
-            CRF_LAUNCH_CHECK();
-            hipLaunchKernelGGL(sb_argmin_partial_kernel, dim3((unsigned)ablocks), blk, 0, st, clouds, (const SbCrop*)crop, pv, pi);
-            CRF_LAUNCH_CHECK();
-            hipLaunchKernelGGL(sb_argmin_final_kernel, dim3(1), blk, 0, st, (const SbCrop*)crop, (const double*)pv, (const int64_t*)pi,
-                               (int)ablocks, min_value, min_index);
-            CRF_LAUNCH_CHECK();
-            continue;
         }
-        hipLaunchKernelGGL(sb_choose_kernel<false>, dim3(1), blk, 0, st, clouds, n_clouds, (const double*)min_value, (const int64_t*)min_index,
-                           (unsigned long long)seed, counter, (int)b, (long long)k, noise_scale, noise_in, crop, hist, noise_out,
-                           out_center, out_cloud_idx);
-        CRF_LAUNCH_CHECK();
-        for (int p = 0; p < 8; ++p) {
-            hipLaunchKernelGGL(sb_hist_kernel, sgrid, blk, 0, st, clouds, crop, hist, p);
-            CRF_LAUNCH_CHECK();
-        }
-        hipLaunchKernelGGL(sb_count_kernel, sgrid, blk, 0, st, clouds, crop, (const int32_t*)hist, cnt, (long long)nb);
-        CRF_LAUNCH_CHECK();
-        hipLaunchKernelGGL(sb_scatter_kernel<false>, sgrid, blk, 0, st, clouds, (const SbCrop*)crop, (const int32_t*)cnt, (long long)nb,
-                           (long long)k, keys_a, vals_a);
-        CRF_LAUNCH_CHECK();
-        const uint32_t* sel = rsort_pairs_u64(keys_a, vals_a, keys_b, vals_b, k, 0, 64, at(l.sort), st) ? vals_b : vals_a;
-        CRF_LAUNCH_CHECK();
-        hipLaunchKernelGGL(sb_dist_kernel, kgrid, blk, 0, st, clouds, (const SbCrop*)crop, sel, (long long)k, dist, pmax);
-        CRF_LAUNCH_CHECK();
-        hipLaunchKernelGGL(sb_update_kernel, kgrid, blk, 0, st, clouds, (const SbCrop*)crop, sel,
-                           perm ? perm + b * k : (const int64_t*)nullptr, (long long)k, (const float*)dist, (const float*)pmax, nblk,
-                           out_pos + (size_t)b * k * 3, out_x ? out_x + (size_t)b * k * x_channels : (float*)nullptr, x_channels,
-                           out_y ? out_y + b * k : (int64_t*)nullptr, out_point_idx ? out_point_idx + b * k : (int64_t*)nullptr);
-        CRF_LAUNCH_CHECK();
-        hipLaunchKernelGGL(sb_argmin_partial_kernel, dim3((unsigned)ablocks), blk, 0, st, clouds, (const SbCrop*)crop, pv, pi);
-        CRF_LAUNCH_CHECK();
-        hipLaunchKernelGGL(sb_argmin_final_kernel, dim3(1), blk, 0, st, (const SbCrop*)crop, (const double*)pv, (const int64_t*)pi,
-                           (int)ablocks, min_value, min_index);
-        CRF_LAUNCH_CHECK();
+        SB_LAUNCH(dist_kernel, kgrid, clouds, crop, sel, (long long)k, w.dist, w.pmax);
+        SB_LAUNCH(update_kernel, kgrid, clouds, crop, sel, row(perm), own_perm && padded ? (const int64_t*)w.compact : (const int64_t*)nullptr,
+                  choice, (long long)k, (const float*)w.dist, (const float*)w.pmax, nblk, row(out_pos, 3), row(out_x, x_channels), x_channels,
+                  row(out_y), row(out_point_idx));
+        SB_LAUNCH(sb_argmin_partial_kernel, dim3((unsigned)ablocks), clouds, crop, w.pv, w.pi);
+        SB_LAUNCH(sb_argmin_final_kernel, one, crop, (const double*)w.pv, (const int64_t*)w.pi, ablocks, min_value, min_index);
     }
     return CRF_OK;
 }
+#undef SB_LAUNCH
 
 extern "C" size_t crfconv_possibility_crop_batch_workspace(int64_t n_max, int64_t k, int64_t B) {
     if (n_max <= 0 || k <= 0 || B <= 0 || k > n_max) return 0;
-    return sb_layout(n_max, k, B).total;
+    return sb_carve(nullptr, n_max, k, B, false).bytes;
 }
 
 extern "C" int crfconv_possibility_crop_batch(const crf_cloud_desc* clouds, int n_clouds, int64_t n_max, double* min_value,
@@ -806,7 +612,7 @@ extern "C" int crfconv_possibility_crop_batch(const crf_cloud_desc* clouds, int 
 
 extern "C" size_t crfconv_possibility_crop_batch_s3dis_workspace(int64_t n_max, int64_t k, int64_t B) {
     if (n_max <= 0 || k <= 0 || B <= 0) return 0;
-    return sb_layout(n_max, k, B, true).total;
+    return sb_carve(nullptr, n_max, k, B, true).bytes;
 }
 
 extern "C" int crfconv_possibility_crop_batch_s3dis(const crf_cloud_desc* clouds, int n_clouds, int64_t n_max, int64_t n_min,

@@ -120,16 +120,11 @@ class PossibilitySampler:
             return self._get_random_s3dis(noise, perm, choice)
         if choice is not None:
             raise ValueError("get_random(choice=) belongs to form='s3dis'")
-        # :424 -- which cloud: the loop's only host decision (a device -> host read; none with a single cloud)
-        c = 0 if len(self.points) == 1 else int(torch.argmin(self._minv).item())
+        c, k, noise, perm = self._next_crop(noise, perm)
         pts = self.points[c]
-        n, k = pts.shape[0], min(self.num_points, pts.shape[0])
-        if noise is None:
-            noise = torch.randn(3, dtype=torch.float64, generator=self.generator) * self.noise_scale
-        noise = to_device(torch.as_tensor(noise, dtype=torch.float64).contiguous(), self.device)
-        if perm is None:
-            perm = torch.randperm(k, generator=self.generator)
-        perm = None if perm is False else to_device(torch.as_tensor(perm, dtype=torch.int64).contiguous(), self.device)
+        n = pts.shape[0]
+        noise = to_device(noise.contiguous(), self.device)
+        perm = None if perm is False else to_device(perm.contiguous(), self.device)
         key = (n, k)
         if key not in self._crop_ws:
             self._crop_ws[key] = _ws(_lib.load().crfconv_possibility_crop_workspace(n, k), self.device)
@@ -156,19 +151,29 @@ class PossibilitySampler:
         """FixedPoints(k, replace=False, allow_duplicates=True) for kc < k rows: ceil(k / kc) permutations end to end, cut to k."""
         return torch.cat([randperm(kc) for _ in range(-(-k // kc))])[:k]
 
-    def _get_random_s3dis(self, noise, perm, choice):
-        """One S3DIS-form crop = the batch call with B = 1 (the same kernels, so get_batch(B) is B of these by construction of the
-        stream order); the draws come from ``self.generator`` in the reference's order: jitter, shuffle, then the padding."""
+    def _next_crop(self, noise, perm):
+        """What get_random decides on the host: the cloud c (:424 -- a device -> host read; none with a single cloud), the crop's row
+        count k_c = min(n_c, num_points), and the jitter float64 [3] and the shuffle int64 (``False`` = none), as given or drawn from
+        ``self.generator`` in the reference's order."""
         c = 0 if len(self.points) == 1 else int(torch.argmin(self._minv).item())
-        k = self.num_points
-        kc = min(k, self.points[c].shape[0])
+        kc = min(self.num_points, self.points[c].shape[0])
         if noise is None:
             noise = torch.randn(3, dtype=torch.float64, generator=self.generator) * self.noise_scale
-        noise = torch.as_tensor(noise, dtype=torch.float64).reshape(1, 3)
+        noise = torch.as_tensor(noise, dtype=torch.float64)
         if perm is None:
             perm = torch.randperm(kc, generator=self.generator)
         if perm is not False:
-            perm = torch.as_tensor(perm, dtype=torch.int64).reshape(-1).cpu()
+            perm = torch.as_tensor(perm, dtype=torch.int64)
+        return c, kc, noise, perm
+
+    def _get_random_s3dis(self, noise, perm, choice):
+        """One S3DIS-form crop = the batch call with B = 1 (the same kernels, so get_batch(B) is B of these by construction of the
+        stream order); the draws come from ``self.generator`` in the reference's order: jitter, shuffle, then the padding."""
+        c, kc, noise, perm = self._next_crop(noise, perm)
+        k = self.num_points
+        noise = noise.reshape(1, 3)
+        if perm is not False:
+            perm = perm.reshape(-1).cpu()
             if perm.numel() < kc:
                 raise ValueError('get_random: perm holds %d entries, the crop %d rows' % (perm.numel(), kc))
             perm = torch.cat([perm[:kc], torch.full((k - kc,), -1, dtype=torch.int64)]).reshape(1, k)
@@ -333,21 +338,16 @@ class PossibilitySampler:
             perm_out = torch.arange(k, dtype=torch.int64, device=dev).repeat(B, 1) if identity \
                 else torch.empty((B, k), dtype=torch.int64, device=dev)
         choice_out = torch.empty((B, k), dtype=torch.int64, device=dev) if return_draws and s3dis else None
+        entry = 'crfconv_possibility_crop_batch_s3dis' if s3dis else 'crfconv_possibility_crop_batch'
         if B not in tb['ws']:
-            query = _lib.load().crfconv_possibility_crop_batch_s3dis_workspace if s3dis else _lib.load().crfconv_possibility_crop_batch_workspace
-            tb['ws'][B] = _ws(query(tb['n_max'], k, B), dev)
+            tb['ws'][B] = _ws(getattr(_lib.load(), entry + '_workspace')(tb['n_max'], k, B), dev)
         ws = tb['ws'][B]
-        if s3dis:
-            _lib.call('crfconv_possibility_crop_batch_s3dis', ptr(tb['table']), len(self.points), tb['n_max'], tb['n_min'], ptr(self._minv),
-                      ptr(self._mini), k, B, seed & _M64, ptr(counter), self.noise_scale, ptr(noise), ptr(perm), 1 if identity else 0,
-                      ptr(choice), ptr(pos), ptr(x), 0 if x is None else x.shape[-1], ptr(res['y']), ptr(res['point_idx']),
-                      ptr(res['cloud_idx']), ptr(res['center']), ptr(noise_out), None if identity else ptr(perm_out), ptr(choice_out),
-                      ptr(ws), ws.numel(), stream_ptr())
-        else:
-            _lib.call('crfconv_possibility_crop_batch', ptr(tb['table']), len(self.points), tb['n_max'], ptr(self._minv), ptr(self._mini),
-                      k, B, seed & _M64, ptr(counter), self.noise_scale, ptr(noise), ptr(perm), 1 if identity else 0, ptr(pos), ptr(x),
-                      0 if x is None else x.shape[-1], ptr(res['y']), ptr(res['point_idx']), ptr(res['cloud_idx']), ptr(res['center']),
-                      ptr(noise_out), None if identity else ptr(perm_out), ptr(ws), ws.numel(), stream_ptr())
+        only_s3dis = lambda *a: a if s3dis else ()      # noqa: E731 -- the three arguments the S3DIS entry has more
+        _lib.call(entry, ptr(tb['table']), len(self.points), tb['n_max'], *only_s3dis(tb['n_min']), ptr(self._minv), ptr(self._mini),
+                  k, B, seed & _M64, ptr(counter), self.noise_scale, ptr(noise), ptr(perm), 1 if identity else 0, *only_s3dis(ptr(choice)),
+                  ptr(pos), ptr(x), 0 if x is None else x.shape[-1], ptr(res['y']), ptr(res['point_idx']), ptr(res['cloud_idx']),
+                  ptr(res['center']), ptr(noise_out), None if identity else ptr(perm_out), *only_s3dis(ptr(choice_out)),
+                  ptr(ws), ws.numel(), stream_ptr())
         for t in list(res.values()) + list(self.possibility) + [self._minv, self._mini]:      # written by library kernels
             if t is not None:
                 torch.autograd.graph.increment_version(t)

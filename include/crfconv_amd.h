@@ -926,7 +926,8 @@ int crfconv_augment(float* pos, float* x, int64_t B, int64_t N, int C, const crf
  *   jitter = noise_in[b] (float64 [B, 3]) or noise_scale x three float64 Box-Muller normals of 53-bit uniforms in (0, 1] of a
  *            splitmix64 hash of (seed, *counter, b, slot); centre = float64(points[seed point]) + jitter
  *   crop   = the k points with the smallest (float64 squared distance, point id), found by a radix select + a sort of k pairs
- *   the possibility update, distances and centred coordinates of crfconv_possibility_crop, bit for bit
+ *   the possibility update, distances and centred coordinates of crfconv_possibility_crop, bit for bit (both entries take them
+ *   from csrc/crop_common.hpp)
  *   min_value / min_index [cloud] <- the cloud's new minimum possibility
  * Row t of crop b shows crop element perm_b[t]: perm_in int64 [B, k], or the identity (identity_perm != 0), or the stable arg-sort
  * over t of the hashes of slot 8 + t.  *counter is a DEVICE word the call reads (never writes): advance it between calls and a
@@ -935,7 +936,8 @@ int crfconv_augment(float* pos, float* x, int64_t B, int64_t N, int C, const crf
  * Outputs (all but out_pos may be NULL): out_pos float32 [B, k, 3] (x, y centred, z raw); out_x float32 [B, k, x_channels],
  * x_channels 3 = [pos] or 6 = [pos, rgb] (zeros without rgb); out_y int64 [B, k] (zeros without labels); out_point_idx int64
  * [B, k]; out_cloud_idx int64 [B]; out_center float64 [B, 3]; noise_out float64 [B, 3] / perm_out int64 [B, k]: the draws used.
- * No host synchronisation, no scratch memory: capturable in a hipGraph.  47 launches per crop + 39 per call for the shuffles. */
+ * No host synchronisation, no scratch memory: capturable in a hipGraph.  47 launches per crop + 39 per call for the shuffles (k = 40 960 ..
+ * 65 536, B <= 256: a pass of the k-pair sort is 4 launches there). */
 typedef struct crf_cloud_desc {
     const float* points;          /* [n, 3] */
     double* possibility;          /* [n] */
@@ -951,7 +953,8 @@ int crfconv_possibility_crop_batch(const crf_cloud_desc* clouds, int n_clouds, i
                                    int x_channels, int64_t* out_y, int64_t* out_point_idx, int64_t* out_cloud_idx, double* out_center,
                                    double* noise_out, int64_t* perm_out, void* workspace, size_t workspace_bytes, crf_stream_t stream);
 
-/* The S3DIS form of the same call (datasets/s3dis_dataset.py:343-379), operation for operation.  Per crop, decided on the device:
+/* The S3DIS form of the same call (datasets/s3dis_dataset.py:343-379), operation for operation: the same per-crop launch sequence, its
+ * kernels instantiated for this form.  Per crop, decided on the device:
  *   kc     = min(n of the chosen cloud, k): a room smaller than k is taken whole
  *   pos    = float32(float64(point) - centre) on ALL three axes; d = x x + y y + z z of those float32 values in float32 (each operation
  *            rounded once); possibility[q] += float64((1 - d / max d)^2) over the kc distinct rows; no class weight, labels as stored

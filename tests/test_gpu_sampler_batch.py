@@ -133,6 +133,27 @@ def test_ties_go_to_the_lower_point_id():
         assert_same_state(smp, twin)
 
 
+@pytest.mark.parametrize('sizes,k', [((4097, 256, 8193), 256), ((4096, 257), 257)], ids=['tile_edges', 'one_row_in_the_second_block'])
+def test_batch_equals_the_twin_loop_at_the_edge_shapes(sizes, k):
+    """The shapes at which the pieces shared by the batch and the single-crop path (csrc/crop_common.hpp) can go wrong: a second select
+    tile holding one point (4097), three tiles (8193), n == k (the select takes the whole cloud; 256: one distance block), and k = 257,
+    where the second distance block holds one row -- the farthest -- so d_max must come from across the blocks.  One point of the
+    n == k cloud starts lowest, so that cloud is certainly drawn first; the update lifts that point and the other clouds follow (the
+    sequence was checked beforehand with a numpy restatement on the host: clouds 1, 2, 2, 0, 2 and 1, 0, 0, 0, 0)."""
+    B = 5
+    sc = scene(sizes, 61 if k == 256 else 62)
+    whole = sizes.index(k)
+    sc[3][whole][0] -= 1e-2
+    smp, twin = pair(sc, k)
+    batch, noise, perm = smp.get_batch(B, seed=1, return_draws=True)
+    drawn = [int(c) for c in batch.cloud_idx[:, 0]]
+    print('clouds drawn:', drawn)
+    assert len(set(drawn)) >= 2 and whole in drawn
+    assert torch.equal(perm.sort(dim=1).values, torch.arange(k, device=DEV).repeat(B, 1))
+    assert_equals_twin_loop(batch, noise, perm, twin, B)
+    assert_same_state(smp, twin)
+
+
 def test_device_draws_are_the_host_twins():
     B, k = 5, 3000
     smp, _ = pair(scene((20000, 9000), 4), k, noise_scale=0.35)

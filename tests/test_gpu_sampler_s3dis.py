@@ -9,7 +9,7 @@ import _seeded as S
 from gpu_util import DEV, t
 from crfconv_amd import transforms as T
 from crfconv_amd.sampling import PossibilitySampler, VoteAccumulator, vote_scene
-from s3dis_restatement import vote_repeated
+from s3dis_restatement import S3DISTwin, vote_repeated
 
 pytestmark = pytest.mark.gpu
 N_DRAWS = 8
@@ -124,6 +124,36 @@ def test_device_draws_batch_equals_get_random_loop_and_the_numpy_twin(sizes, k):
     # the host-drawn path of get_random (generator): shapes and multiplicities only
     d = twin.get_random()
     assert d.pos.shape == (k, 3) and d.x.shape == (k, 6) and d.point_idx.unique().numel() == min(sizes[d.cloud], k)
+
+
+def test_device_draws_equal_the_numpy_restatement_at_the_edge_shapes():
+    """Rooms of 3, 255 and 4097 points at k = 256 (a crop of three rows; one row short of k; a second select tile holding one point),
+    the device's own draws: every crop, the final float64 possibility tables and the minima equal S3DISTwin fed those draws, bit for
+    bit.  The start possibilities of the two small rooms are lowered by 4e-3 and 2e-3 so that all three rooms are drawn (checked
+    beforehand with the restatement on the host: rooms 1, 0, 0, 2, 2, 2; no crop of coincident points, d_max > 0 throughout)."""
+    sizes, k, B = (3, 255, 4097), 256, 6
+    pts, rgb, labels, poss = rooms(sizes, 63)
+    poss = [poss[0] - 4e-3, poss[1] - 2e-3, poss[2]]
+    smp, _ = s3dis_pair((pts, rgb, labels, poss), k, noise_scale=0.35)
+    twin = S3DISTwin([p.cpu().numpy() for p in pts], [r.cpu().numpy() for r in rgb], [lab.cpu().numpy() for lab in labels],
+                     [p.numpy() for p in poss], k)
+    counter = torch.full((1,), 17, dtype=torch.int64, device=DEV)
+    batch, noise, perm, choice = smp.get_batch(B, seed=991, counter=counter, return_draws=True)
+    noise, perm, choice = noise.cpu().numpy(), perm.cpu().numpy(), choice.cpu().numpy()
+    kcs, drawn = [], []
+    for b in range(B):
+        kc = min(sizes[twin.next_cloud()], k)
+        ref = twin.draw(noise[b], perm[b, :kc], choice[b])
+        assert int(batch.cloud_idx[b, 0]) == ref['cloud'], b
+        for name in ('pos', 'x', 'y', 'point_idx'):
+            assert np.array_equal(getattr(batch, name)[b].cpu().numpy(), ref[name]), (b, name)
+        kcs.append(kc)
+        drawn.append(ref['cloud'])
+    print('rooms drawn:', drawn)
+    assert any(kc < k for kc in kcs) and 2 in drawn
+    for c in range(3):
+        assert np.array_equal(smp.possibility[c].cpu().numpy(), twin.possibility[c]), c
+    assert np.array_equal(smp.min_possibility, np.asarray(twin.min_possibility))
 
 
 def test_existing_form_is_untouched():
