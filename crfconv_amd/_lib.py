@@ -200,6 +200,8 @@ SIGNATURES = {
     'crfconv_possibility_crop_batch_s3dis': (_i, [_vp, _i, _i64, _i64, _vp, _vp, _i64, _i64, _u64, _vp, _d, _vp, _vp, _i, _vp, _vp, _vp, _i,
                                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'crfconv_vote_update_repeated': (_i, [_vp, _vp, _vp, _i64, _i, _d, _vp, _i64, _vp, _vp, _vp, _vp]),
+    'crfconv_vote_update_batch': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _d, _vp, _i, _vp]),
+    'crfconv_vote_confusion': (_i, [_vp, _i64, _i, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
 }
 
 

@@ -134,6 +134,105 @@ __global__ __launch_bounds__(EV_BLOCK) void project_kernel(const float* __restri
     preds[i] = (uint8_t)(argmax_first(test_probs + p * C, C) + label_offset);
 }
 
+// ------------------------------------------------------------------------------------------ votes keyed by DEVICE cloud ids
+// One sample of a batch: the four kernels above with the cloud looked up on the device (crf_vote_desc table, *cloud_id), so that no
+// launch argument depends on which cloud was drawn and the call can sit in a captured graph.  A sample whose cloud id lies outside the
+// table is skipped whole and its rows are counted (once: by the first pass of the repeated form).
+__device__ __forceinline__ bool vote_cloud(const crf_vote_desc* __restrict__ clouds, int n_clouds, const int64_t* __restrict__ cloud_id,
+                                           crf_vote_desc& d) {
+    const int64_t c = *cloud_id;
+    if (c < 0 || c >= n_clouds) return false;
+    d = clouds[c];
+    return d.test_probs != nullptr && d.n > 0;
+}
+__device__ __forceinline__ void vote_count_block(int64_t n_rows, int32_t* __restrict__ bad) {       // every row of a skipped sample, once
+    const int64_t first = (int64_t)blockIdx.x * EV_BLOCK;
+    if (threadIdx.x == 0 && first < n_rows) atomicAdd(bad, (int32_t)(n_rows - first < EV_BLOCK ? n_rows - first : EV_BLOCK));
+}
+
+__global__ __launch_bounds__(EV_BLOCK) void vote_batch_kernel(const crf_vote_desc* __restrict__ clouds, int n_clouds,
+                                                              const int64_t* __restrict__ cloud_id, const float* __restrict__ probs,
+                                                              const float* __restrict__ logits, const int64_t* __restrict__ point_idx,
+                                                              int64_t n_rows, int C, float smooth, float one_minus,
+                                                              int32_t* __restrict__ bad) {
+    crf_vote_desc d;
+    if (!vote_cloud(clouds, n_clouds, cloud_id, d)) { vote_count_block(n_rows, bad); return; }
+    const int64_t r = (int64_t)blockIdx.x * EV_BLOCK + threadIdx.x;
+    if (r >= n_rows) return;
+    const int64_t p = point_idx[r];
+    if (p < 0 || p >= d.n) { atomicAdd(bad, 1); return; }
+    if (d.visits != nullptr) d.visits[p] += 1;           // (rows of one sample are distinct points; samples are launches in stream order)
+    vote_row(d.test_probs + p * C, probs ? probs + r * C : nullptr, logits ? logits + r * C : nullptr, C, smooth, one_minus);
+}
+
+// the repeated form: passes (1) (2) (3) of crfconv_vote_update_repeated; a cloud without a last_row table is skipped like a bad cloud id
+__global__ __launch_bounds__(EV_BLOCK) void vote_batch_last_row_kernel(const crf_vote_desc* __restrict__ clouds, int n_clouds,
+                                                                       const int64_t* __restrict__ cloud_id,
+                                                                       const int64_t* __restrict__ point_idx, int64_t n_rows,
+                                                                       int32_t* __restrict__ bad) {
+    crf_vote_desc d;
+    if (!vote_cloud(clouds, n_clouds, cloud_id, d) || d.last_row == nullptr) { vote_count_block(n_rows, bad); return; }
+    const int64_t r = (int64_t)blockIdx.x * EV_BLOCK + threadIdx.x;
+    if (r >= n_rows) return;
+    const int64_t p = point_idx[r];
+    if (p < 0 || p >= d.n) { atomicAdd(bad, 1); return; }
+    atomicMax(&d.last_row[p], (int32_t)r);
+}
+__global__ __launch_bounds__(EV_BLOCK) void vote_batch_repeated_kernel(const crf_vote_desc* __restrict__ clouds, int n_clouds,
+                                                                       const int64_t* __restrict__ cloud_id, const float* __restrict__ probs,
+                                                                       const float* __restrict__ logits, const int64_t* __restrict__ point_idx,
+                                                                       int64_t n_rows, int C, float smooth, float one_minus) {
+    crf_vote_desc d;
+    if (!vote_cloud(clouds, n_clouds, cloud_id, d) || d.last_row == nullptr) return;
+    const int64_t r = (int64_t)blockIdx.x * EV_BLOCK + threadIdx.x;
+    if (r >= n_rows) return;
+    const int64_t p = point_idx[r];
+    if (p < 0 || p >= d.n || d.last_row[p] != (int32_t)r) return;
+    if (d.visits != nullptr) d.visits[p] += 1;           // one row per point passes the test above
+    vote_row(d.test_probs + p * C, probs ? probs + r * C : nullptr, logits ? logits + r * C : nullptr, C, smooth, one_minus);
+}
+__global__ __launch_bounds__(EV_BLOCK) void vote_batch_last_row_clear_kernel(const crf_vote_desc* __restrict__ clouds, int n_clouds,
+                                                                             const int64_t* __restrict__ cloud_id,
+                                                                             const int64_t* __restrict__ point_idx, int64_t n_rows) {
+    crf_vote_desc d;
+    if (!vote_cloud(clouds, n_clouds, cloud_id, d) || d.last_row == nullptr) return;
+    const int64_t r = (int64_t)blockIdx.x * EV_BLOCK + threadIdx.x;
+    if (r >= n_rows) return;
+    const int64_t p = point_idx[r];
+    if (p >= 0 && p < d.n) d.last_row[p] = -1;           // (rows naming one point store the same value)
+}
+
+// Confusion matrix straight from a vote table (trainval.py:271-320): row i is compared through p = proj_idx ? proj_idx[i] : i, pred = first
+// arg-max of test_probs[p] (an unvoted, all-zero row predicts class 0), t = labels[i] - label_shift; labels outside [0, C) are skipped
+// (sklearn's confusion_matrix(labels=...), the mask of utils/metrics.py).  Accumulated like confusion_kernel: exact and order-independent.
+template <bool LDS_HIST>
+__global__ __launch_bounds__(EV_BLOCK) void vote_confusion_kernel(const float* __restrict__ test_probs, int64_t n_cloud, int C,
+                                                                  const int64_t* __restrict__ proj_idx, const int64_t* __restrict__ labels,
+                                                                  int64_t n_rows, int64_t label_shift, unsigned long long* __restrict__ hist,
+                                                                  int32_t* __restrict__ bad) {
+    __shared__ unsigned int s_hist[LDS_HIST ? HIST_LDS_CLASSES * HIST_LDS_CLASSES : 1];
+    if constexpr (LDS_HIST) {
+        for (int i = threadIdx.x; i < C * C; i += EV_BLOCK) s_hist[i] = 0u;
+        __syncthreads();
+    }
+    int nbad = 0;
+    for (int64_t i = (int64_t)blockIdx.x * EV_BLOCK + threadIdx.x; i < n_rows; i += (int64_t)gridDim.x * EV_BLOCK) {
+        const int64_t p = proj_idx ? proj_idx[i] : i;
+        if (p < 0 || p >= n_cloud) { ++nbad; continue; }
+        const int64_t t = labels[i] - label_shift;
+        if (t < 0 || t >= C) continue;
+        const int pred = argmax_first(test_probs + p * C, C);
+        if constexpr (LDS_HIST) atomicAdd(&s_hist[(int)t * C + pred], 1u);
+        else atomicAdd(&hist[t * C + pred], 1ull);
+    }
+    if (nbad) atomicAdd(bad, nbad);
+    if constexpr (LDS_HIST) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < C * C; i += EV_BLOCK)
+            if (s_hist[i]) atomicAdd(&hist[i], (unsigned long long)s_hist[i]);
+    }
+}
+
 // ------------------------------------------------------------------------------------------ possibility sampler
 // arg-min with the first index on ties (np.argmin; crop_common.hpp), two passes: per-block candidates, then one block.
 __global__ __launch_bounds__(EV_BLOCK) void argmin_partial_kernel(const double* __restrict__ v, int64_t n,
@@ -339,6 +438,59 @@ extern "C" int crfconv_vote_project(const float* test_probs, const int64_t* proj
     if (n_proj <= 0) return CRF_OK;
     hipLaunchKernelGGL(project_kernel, dim3((unsigned)cdiv(n_proj, EV_BLOCK)), dim3(EV_BLOCK), 0, as_stream(stream),
                        test_probs, proj_idx, n_proj, C, n_cloud, label_offset, preds, bad_count);
+    CRF_LAUNCH_CHECK();
+    return CRF_OK;
+}
+
+extern "C" int crfconv_vote_update_batch(const crf_vote_desc* clouds, int n_clouds, const float* probs, const float* logits,
+                                         const int64_t* point_idx, const int64_t* cloud_idx, int64_t cloud_idx_stride, int64_t B,
+                                         int64_t N, int C, double smooth, int32_t* bad_count, int repeated, crf_stream_t stream) {
+    CRF_REQUIRE(clouds && point_idx && cloud_idx && bad_count, CRF_ERR_ARG, "null pointer");
+    CRF_REQUIRE((probs != nullptr) != (logits != nullptr), CRF_ERR_ARG, "exactly one of probs and logits");
+    CRF_REQUIRE(n_clouds >= 1 && C >= 1 && B >= 0 && N >= 0 && N < ((int64_t)1 << 31), CRF_ERR_ARG,
+                "n_clouds=%d C=%d B=%lld N=%lld invalid", n_clouds, C, (long long)B, (long long)N);
+    if (B == 0 || N == 0) return CRF_OK;
+    const float one_minus = (float)(1.0 - smooth);          // as vote_accumulate_impl
+    const dim3 grid((unsigned)cdiv(N, EV_BLOCK)), blk(EV_BLOCK);
+    hipStream_t st = as_stream(stream);
+    // one sample after the other in stream order: the reference's `for b in range(batch_size)`; two samples of one call may name the
+    // same cloud and the same points, and the second then sees what the first stored
+    for (int64_t b = 0; b < B; ++b) {
+        const float* pb = probs ? probs + b * N * C : nullptr;
+        const float* lb = logits ? logits + b * N * C : nullptr;
+        const int64_t* ib = point_idx + b * N;
+        const int64_t* cb = cloud_idx + b * cloud_idx_stride;
+        if (repeated) {
+            hipLaunchKernelGGL(vote_batch_last_row_kernel, grid, blk, 0, st, clouds, n_clouds, cb, ib, N, bad_count);
+            CRF_LAUNCH_CHECK();
+            hipLaunchKernelGGL(vote_batch_repeated_kernel, grid, blk, 0, st, clouds, n_clouds, cb, pb, lb, ib, N, C, (float)smooth, one_minus);
+            CRF_LAUNCH_CHECK();
+            hipLaunchKernelGGL(vote_batch_last_row_clear_kernel, grid, blk, 0, st, clouds, n_clouds, cb, ib, N);
+            CRF_LAUNCH_CHECK();
+        } else {
+            hipLaunchKernelGGL(vote_batch_kernel, grid, blk, 0, st, clouds, n_clouds, cb, pb, lb, ib, N, C, (float)smooth, one_minus, bad_count);
+            CRF_LAUNCH_CHECK();
+        }
+    }
+    return CRF_OK;
+}
+
+extern "C" int crfconv_vote_confusion(const float* test_probs, int64_t n_cloud, int C, const int64_t* proj_idx, const int64_t* labels,
+                                      int64_t n_rows, int64_t label_shift, int64_t* hist, int32_t* bad_count, crf_stream_t stream) {
+    CRF_REQUIRE(test_probs && labels && hist && bad_count, CRF_ERR_ARG, "null pointer");
+    CRF_REQUIRE(C >= 1 && C <= 4096 && n_cloud > 0, CRF_ERR_ARG, "C=%d n_cloud=%lld invalid", C, (long long)n_cloud);
+    CRF_REQUIRE(proj_idx || n_rows <= n_cloud, CRF_ERR_ARG, "n_rows=%lld labels for a cloud of %lld points (no proj_idx)", (long long)n_rows,
+                (long long)n_cloud);
+    if (n_rows <= 0) return CRF_OK;
+    int64_t blocks = cdiv(n_rows, EV_BLOCK);
+    if (blocks > 2048) blocks = 2048;
+    auto* h = reinterpret_cast<unsigned long long*>(hist);
+    if (C <= HIST_LDS_CLASSES)
+        hipLaunchKernelGGL(vote_confusion_kernel<true>, dim3((unsigned)blocks), dim3(EV_BLOCK), 0, as_stream(stream), test_probs, n_cloud, C,
+                           proj_idx, labels, n_rows, label_shift, h, bad_count);
+    else
+        hipLaunchKernelGGL(vote_confusion_kernel<false>, dim3((unsigned)blocks), dim3(EV_BLOCK), 0, as_stream(stream), test_probs, n_cloud, C,
+                           proj_idx, labels, n_rows, label_shift, h, bad_count);
     CRF_LAUNCH_CHECK();
     return CRF_OK;
 }

@@ -398,6 +398,7 @@ class VoteAccumulator:
         self.visits = [torch.zeros(int(n), dtype=torch.int32, device=device) for n in cloud_sizes] if track_visits else None
         self._bad = torch.zeros(1, dtype=torch.int32, device=device)
         self._last = [torch.full((int(n),), -1, dtype=torch.int32, device=device) for n in cloud_sizes] if allow_repeats else None
+        self._table = None                                  # update_batch's device table of the tensors above, built at its first call
 
     def update(self, point_idx, cloud_idx, probs=None, logits=None, repeated=None):
         """point_idx int64 [B, N]; cloud_idx int64 [B] or [B, 1]; probs or logits float32 [B * N, C] (the network's
@@ -433,6 +434,94 @@ class VoteAccumulator:
                 _lib.call('crfconv_vote_accumulate_counted', ptr(src[b]) if probs is not None else None,
                           ptr(src[b]) if probs is None else None, ptr(point_idx[b]), N, self.num_classes, self.smooth,
                           ptr(tp), tp.shape[0], ptr(self._bad), ptr(self.visits[int(clouds[b])]), stream_ptr())
+
+    def _desc_table(self):
+        """crf_vote_desc [n_clouds] on the device (four 8-byte words per cloud), built once from the accumulator's own tensors."""
+        own = list(self.test_probs) + list(self.visits or []) + list(self._last or [])
+        keep = [t.data_ptr() for t in own]
+        if self._table is None:
+            rows = [[tp.data_ptr(), 0 if self.visits is None else self.visits[c].data_ptr(),
+                     0 if self._last is None else self._last[c].data_ptr(), tp.shape[0]] for c, tp in enumerate(self.test_probs)]
+            self._table = (to_device(torch.tensor(rows, dtype=torch.int64), self.test_probs[0].device), keep)
+        elif self._table[1] != keep:
+            raise _lib.CrfConvError('VoteAccumulator: a vote / visit table was replaced after the first update_batch (copy into the '
+                                    'existing tensors instead)')
+        return self._table[0]
+
+    def update_batch(self, point_idx, cloud_idx, probs=None, logits=None, repeated=None):
+        """``update`` for a batch whose cloud ids stay on the device: point_idx int64 [B, N]; cloud_idx an int64 DEVICE tensor [B] or
+        [B, 1] (what ``get_batch`` and ``CollateGraph(sampler=)`` deliver); probs or logits float32 [B, N, C] or [B * N, C].  ONE library
+        call (crfconv_vote_update_batch), no host read: capturable in a hipGraph, and a replay follows the tensors' contents.  The
+        samples are applied in batch order; two samples of one call may name the same cloud and the same points, and the tables are
+        those of B per-sample ``update`` calls, bit for bit.  repeated: as ``update``.  A cloud id outside the accumulator skips the
+        sample and counts its rows (``check()``)."""
+        if repeated is None:
+            repeated = self._last is not None
+        if repeated and self._last is None:
+            raise _lib.CrfConvError('VoteAccumulator.update_batch(repeated=True) needs allow_repeats=True at construction')
+        if (probs is None) == (logits is None):
+            raise ValueError('update_batch: exactly one of probs and logits')
+        if not torch.is_tensor(cloud_idx):
+            raise TypeError('update_batch: cloud_idx must be an int64 device tensor (host cloud ids go through update)')
+        if not torch.is_tensor(point_idx) or point_idx.dim() != 2:
+            raise ValueError('update_batch: point_idx must be [B, N]')
+        B, N = point_idx.shape
+        if cloud_idx.dtype != torch.int64 or cloud_idx.dim() not in (1, 2) or cloud_idx.shape[0] != B:
+            raise ValueError('update_batch: cloud_idx must be int64 [B] or [B, 1] with B = %d, got %s %s' % (B, cloud_idx.dtype, tuple(cloud_idx.shape)))
+        src = probs if probs is not None else logits
+        if src.numel() != B * N * self.num_classes:
+            raise ValueError('update_batch: %s holds %d values, [B, N, C] = [%d, %d, %d]' % ('probs' if probs is not None else 'logits', src.numel(), B, N, self.num_classes))
+        require_gpu(point_idx, cloud_idx, src)
+        src = src.reshape(B, N, self.num_classes).float().contiguous()
+        point_idx = point_idx.long().contiguous()
+        table = self._desc_table()
+        _lib.call('crfconv_vote_update_batch', ptr(table), len(self.test_probs), ptr(src) if probs is not None else None,
+                  ptr(src) if probs is None else None, ptr(point_idx), ptr(cloud_idx), cloud_idx.stride(0), B, N, self.num_classes,
+                  self.smooth, ptr(self._bad), 1 if repeated else 0, stream_ptr())
+        for t in list(self.test_probs) + list(self.visits or []) + [self._bad]:      # written by library kernels
+            torch.autograd.graph.increment_version(t)
+
+    def confusion(self, cloud, labels, proj_idx=None, label_shift=0, out=None):
+        """Confusion matrix of one cloud's votes, device int64 [C, C] (rows = ground truth), in one pass over the vote table
+        (trainval.py:275-278 / :298-310): the prediction of row i is the first arg-max of test_probs[cloud][proj_idx[i]] (of row i itself
+        without proj_idx), its class labels[i] - label_shift; labels outside [0, C) are skipped.  Accumulates into `out` when given."""
+        tp = self.test_probs[cloud]
+        C = self.num_classes
+        if out is None:
+            out = torch.zeros((C, C), dtype=torch.int64, device=tp.device)
+        elif not (torch.is_tensor(out) and out.dtype == torch.int64 and tuple(out.shape) == (C, C) and out.is_contiguous()):
+            raise ValueError('confusion(out=): a contiguous int64 [%d, %d] tensor is needed' % (C, C))
+        n_rows = labels.numel()
+        if proj_idx is None:
+            if n_rows != tp.shape[0]:
+                raise ValueError('confusion: %d labels for the %d points of cloud %d (no proj_idx)' % (n_rows, tp.shape[0], cloud))
+        elif proj_idx.numel() != n_rows:
+            raise ValueError('confusion: %d labels for %d projection indices' % (n_rows, proj_idx.numel()))
+        require_gpu(labels, proj_idx, out)
+        labels = labels.reshape(-1).long().contiguous()
+        proj_idx = None if proj_idx is None else proj_idx.reshape(-1).long().contiguous()
+        _lib.call('crfconv_vote_confusion', ptr(tp), tp.shape[0], C, ptr(proj_idx), ptr(labels), n_rows, int(label_shift), ptr(out),
+                  ptr(self._bad), stream_ptr())
+        torch.autograd.graph.increment_version(out)
+        return out
+
+    def scores(self, labels, proj=None, class_proportions=None, label_shift=0):
+        """(mean IoU, IoUs [C]) of the votes against `labels` (one tensor per cloud): the confusions of all clouds summed
+        (trainval.py:272-281, or :304-315 through `proj`, the list of proj_idx tensors onto the full clouds whose labels are then given),
+        with class_proportions the rows rescaled to the right number of points per class (:283), then Trainer._iou_from_confusions
+        (:286-287, :316-317).  One host copy of a C x C matrix."""
+        from .utils.metrics import iou_from_confusions
+        if len(labels) != len(self.test_probs) or (proj is not None and len(proj) != len(self.test_probs)):
+            raise ValueError('scores: one label (and proj) tensor per cloud: %d clouds' % len(self.test_probs))
+        hist = None
+        for c in range(len(self.test_probs)):
+            hist = self.confusion(c, labels[c], None if proj is None else proj[c], label_shift=label_shift, out=hist)
+        conf = hist.cpu().numpy()
+        if class_proportions is not None:
+            conf = conf.astype(np.float32)
+            conf *= np.expand_dims(class_proportions / (np.sum(conf, axis=1) + 1e-6), 1)
+        ious = iou_from_confusions(conf)
+        return float(np.mean(ious)), ious
 
     def fold_(self, later_probs, later_visits):
         """self <- the tables ONE accumulator would hold that applied self's updates first and then those behind `later_probs` /
@@ -586,3 +675,112 @@ def vote_scene(sampler, net, votes, n_crops, kernel_size=(16, 16, 16, 16, 16), r
     finally:
         net.train(was_training)
     return votes
+
+
+class SceneVoter:
+    """The inference loop of trainval.py:170-189 / :236-262 for ``batch_size`` crops per forward, replayed: every ``step()`` after the
+    first is TWO hipGraph replays and nothing else on the host --
+
+    * ``data.CollateGraph(static, sampler=sampler)``: sample B crops (possibility sampler, the cloud of every crop chosen on the device)
+      -> Morton order, kNN at every scale, subsets -> ``load_`` into the static batch, ``point_idx`` / ``cloud_idx`` carried along;
+    * one graph of ``net(static)`` (eval, no grad) and ``votes.update_batch(static.point_idx, static.cloud_idx, logits=...)``: the
+      vote is library launches on the capturing stream, keyed by the DEVICE cloud ids, so it sits in the same capture.
+
+    The first ``step()`` runs eagerly (``sampler.get_batch(B)`` on the sampler's own seed and counter, ``multiscale_compute(sort='morton')``
+    with ``torch.randperm`` subsets from `generator`, forward, ``update_batch``), makes that batch the static one and captures the forward
+    + vote graph; the collate graph is captured by the second step (its warm-up puts the sampler's state back: no crop is lost).  Later
+    crops are keyed on the collate graph's seed and counter (``self.cg``).  Crops reach the votes in sampler order, sample b of a batch
+    before sample b + 1.  The sampler must hold colours (x = [pos, rgb]).  An S3DIS-form sampler needs ``votes`` built with
+    ``allow_repeats=True`` and votes with the repeated-index rule, as ``vote_scene`` demands.  ``votes.check()`` is the caller's.
+
+    Crops sharded over ranks stay with ``vote_scene(rank=, world=)`` + ``votes.merge()``: with a process group of more than one rank
+    initialised every rank would vote the whole scene, which is refused unless ``allow_replicated=True`` says that this is meant."""
+
+    def __init__(self, sampler, net, votes, batch_size, kernel_size=(16, 16, 16, 16, 16), ratio=(4, 4, 4, 4, 2), generator=None,
+                 allow_replicated=False):
+        import torch.distributed as dist
+        self.B = int(batch_size)
+        if self.B < 1:
+            raise ValueError('SceneVoter: batch_size = %d' % self.B)
+        if len(kernel_size) != len(ratio):
+            raise ValueError('SceneVoter: %d kernel sizes for %d ratios' % (len(kernel_size), len(ratio)))
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 and not allow_replicated:
+            raise ValueError('SceneVoter votes the whole scene on every rank; crops sharded over %d ranks are vote_scene(rank=, world=) + '
+                             'votes.merge() (allow_replicated=True runs the replicated loop)' % dist.get_world_size())
+        self.repeated = True if getattr(sampler, 'form', 'semantic3d') == 's3dis' else None
+        if self.repeated and votes._last is None:
+            raise _lib.CrfConvError('SceneVoter: an S3DIS-form sampler pads small rooms (repeated rows): VoteAccumulator needs '
+                                    'allow_repeats=True at construction')
+        if sampler.rgb is None:
+            raise ValueError('SceneVoter: the sampler holds no colours (the batch form builds x = [pos, rgb])')
+        self.sampler, self.net, self.votes = sampler, net, votes
+        self.kernel_size, self.ratio, self.generator = tuple(kernel_size), tuple(ratio), generator
+        self.static = self.cg = self.graph = self.logits = None
+        self.batches = 0                                  # steps taken so far
+
+    def _first(self):
+        from .data import CollateGraph, multiscale_compute
+        crops = self.sampler.get_batch(self.B)
+        data = multiscale_compute(crops.pos, x=crops.x, point_idx=crops.point_idx, cloud_idx=crops.cloud_idx, kernel_size=self.kernel_size,
+                                  ratio=self.ratio, num_scales=len(self.kernel_size), generator=self.generator, sort='morton')
+        with torch.no_grad():
+            logits = self.net(data)
+        # the collate reordered every crop along its Morton curve: point_idx travelled with it
+        self.votes.update_batch(data.point_idx, data.cloud_idx, logits=logits, repeated=self.repeated)
+        self.static = data
+        self.cg = CollateGraph(data, kernel_size=self.kernel_size, ratio=self.ratio, generator=self.generator, sampler=self.sampler)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side), torch.no_grad():
+            self.net(data)                                # warm-up outside the capture (the forward only: a vote would count)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.no_grad(), torch.cuda.graph(self.graph):
+            self.logits = self.net(data)
+            self.votes.update_batch(data.point_idx, data.cloud_idx, logits=self.logits, repeated=self.repeated)
+        return logits
+
+    def _step(self, on_batch):
+        if self.graph is None:
+            logits = self._first()
+        else:
+            self.cg.run()                                 # static batch <- the next B crops
+            self.graph.replay()                           # forward + votes
+            logits = self.logits
+        self.batches += 1
+        if on_batch is not None:
+            on_batch(self.static, logits)
+
+    def step(self, on_batch=None):
+        """One batch of B crops into the votes.  on_batch(static_batch, logits): the collated batch (static buffers: clone what is kept)
+        and the logits [B * N, C] of this batch."""
+        if not self.net.training:
+            return self._step(on_batch)
+        self.net.eval()
+        try:
+            return self._step(on_batch)
+        finally:
+            self.net.train(True)
+
+    def run(self, n_batches=None, until_min_possibility=None, on_batch=None, check_every=32):
+        """``step()`` until `n_batches` have run and / or the smallest possibility of the scene has reached `until_min_possibility`
+        (the reference's stop rule, trainval.py:192,264: read once per "epoch" of `check_every` batches -- one host read per epoch, never
+        one per batch).  Returns the votes."""
+        if n_batches is None and until_min_possibility is None:
+            raise ValueError('SceneVoter.run: n_batches or until_min_possibility is needed')
+        if int(check_every) < 1:
+            raise ValueError('SceneVoter.run: check_every = %d' % check_every)
+        was_training = self.net.training
+        self.net.eval()
+        try:
+            done = 0
+            while n_batches is None or done < n_batches:
+                if until_min_possibility is not None and done and done % int(check_every) == 0 \
+                        and float(np.min(self.sampler.min_possibility)) >= until_min_possibility:
+                    break
+                self._step(on_batch)
+                done += 1
+        finally:
+            self.net.train(was_training)
+        return self.votes

@@ -984,6 +984,38 @@ int crfconv_vote_update_repeated(const float* probs, const float* logits, const 
                                  float* test_probs, int64_t n_cloud, int32_t* bad_count, int32_t* visits, int32_t* last_row,
                                  crf_stream_t stream);
 
+/* The update of trainval.py:184-189 / :257-262 for all B samples of a batch in ONE call, the cloud of every sample read on the device:
+ * for b = 0 .. B-1 in stream order (the reference's `for b in range(batch_size)`)
+ *   c = cloud_idx[b * cloud_idx_stride]  (int64; element stride, so [B] and [B, 1] both pass)
+ *   repeated == 0: crfconv_vote_accumulate(_counted) of rows point_idx[b] into clouds[c] (the rows of ONE sample are distinct points)
+ *   repeated != 0: crfconv_vote_update_repeated of those rows (numpy's fancy assignment: the last row naming a point is stored;
+ *                  clouds[c].last_row is -1 everywhere before and after; a cloud whose last_row is NULL is skipped like a bad cloud id)
+ * Two samples of one call may name the same cloud and the same points: the result is that of B consecutive per-sample calls, bit for
+ * bit (the same row arithmetic, one launch per sample -- three in the repeated form -- in batch order).  clouds: DEVICE array of
+ * n_clouds descriptors.  Exactly one of probs / logits float32 [B, N, C] is non-NULL; point_idx int64 [B, N]; N < 2^31.  visits (may be
+ * NULL) counts as the per-sample entries do.  Rows outside [0, n) are skipped and counted in *bad_count; a sample whose cloud id lies
+ * outside [0, n_clouds) is skipped whole and its N rows are counted.  No host read, no scratch memory, launch shapes a function of
+ * (B, N) only: capturable in a hipGraph, and a replay follows whatever cloud_idx / point_idx / probs hold by then. */
+typedef struct crf_vote_desc {
+    float* test_probs;            /* [n, C] */
+    int32_t* visits;              /* [n] or NULL */
+    int32_t* last_row;            /* [n] or NULL (needed by the repeated form) */
+    int64_t n;
+} crf_vote_desc;
+int crfconv_vote_update_batch(const crf_vote_desc* clouds, int n_clouds, const float* probs, const float* logits, const int64_t* point_idx,
+                              const int64_t* cloud_idx, int64_t cloud_idx_stride, int64_t B, int64_t N, int C, double smooth,
+                              int32_t* bad_count, int repeated, crf_stream_t stream);
+
+/* Confusion matrix straight from a vote table (the evaluation of trainval.py:271-320 in one pass): for row i of n_rows,
+ * p = proj_idx ? proj_idx[i] : i, pred = FIRST arg-max of test_probs[p, 0..C) (ties go to the lowest class, as np.argmax and
+ * crfconv_vote_project: an unvoted, all-zero row predicts class 0), t = labels[i] - label_shift; if 0 <= t < C then
+ * hist[t * C + pred] += 1 (int64 [C, C], rows = ground truth, accumulated: the caller zeroes it).  Labels outside that range are skipped
+ * (sklearn's confusion_matrix(labels=...) at :278,310; the mask of utils/metrics.py).  p outside [0, n_cloud) is skipped and counted
+ * in *bad_count.  Without proj_idx, n_rows <= n_cloud.  Exact and order-independent (integer atomics, as
+ * crfconv_confusion_accumulate). */
+int crfconv_vote_confusion(const float* test_probs, int64_t n_cloud, int C, const int64_t* proj_idx, const int64_t* labels, int64_t n_rows,
+                           int64_t label_shift, int64_t* hist, int32_t* bad_count, crf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
