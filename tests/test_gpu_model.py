@@ -1732,7 +1732,10 @@ def test_mlp_block_cat_equals_block_on_concatenation(M, Ca, Cb, Co):
 @pytest.mark.parametrize('M,C,slope,training', [(163840, 32, 0.1, True), (40960, 8, 1.0, True), (1000, 512, 0.1, True),
                                                 (777, 128, 0.1, False), (33, 1024, 1.0, True), (2560, 256, 0.1, True),
                                                 (640, 512, 1.0, True), (4096, 64, 0.1, True), (4097, 64, 0.1, True),
-                                                (2, 16, 0.1, True), (2560, 24, 0.1, True)])
+                                                (2, 16, 0.1, True), (2560, 24, 0.1, True),
+                                                # the switch-over rows of csrc/bn.hip: bn_small<1> / bn_small<3> / the streaming form
+                                                (1024, 16, 0.1, True), (1025, 16, 0.1, True), (3072, 8, 1.0, True), (3073, 8, 0.1, True),
+                                                (1024, 1024, 0.1, True), (1025, 32, 0.1, False)])
 def test_fused_batchnorm_lrelu(M, C, slope, training):
     """csrc/bn.hip against torch BatchNorm1d + LeakyReLU in float64.  The LeakyReLU branch of the handful of
     elements whose pre-activation is within fp32 rounding of 0 is taken from the kernel's own output sign, so the
