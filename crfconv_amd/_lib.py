@@ -100,6 +100,7 @@ SIGNATURES = {
     'crfconv_mlp_dw_jobs': (_i, [_vp, _i, _vp]),
     'crfconv_mlp_dw_jobs_hosting': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     'crfconv_mlp_backward_add': (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    'crfconv_mlp_backward_add_mask': (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i64, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     'crfconv_mlp_backward_cat': (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     'crfconv_bn_workspace': (_sz, [_i64, _i]),
     'crfconv_bn_forward': (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp, _f, _f, _i, _f, _vp, _vp, _vp, _sz, _vp]),
@@ -166,6 +167,7 @@ SIGNATURES = {
     'crfconv_linear_forward_dropout': (_i, [_vp, _vp, _i64, _i, _i, _i, _f, _u64, _vp, _vp, _vp]),
     'crfconv_dropout_backward': (_i, [_vp, _i64, _f, _u64, _vp, _vp, _vp]),
     'crfconv_add_lrelu_backward': (_i, [_vp, _vp, _i64, _f, _vp, _vp]),
+    'crfconv_add_mask': (_i, [_vp, _vp, _vp, _i64, _f, _vp, _vp]),
     'crfconv_sgd_step': (_i, [_vp, _vp, _vp, _i64, _f, _f, _f, _f, _i, _i, _vp]),
     'crfconv_sgd_step_hyper': (_i, [_vp, _vp, _vp, _i64, _vp, _i, _i, _vp]),
     'crfconv_sgd_step_guarded': (_i, [_vp, _vp, _vp, _i64, _vp, _i, _i, _vp, _vp]),
@@ -276,7 +278,8 @@ class MlpBwdJob(ctypes.Structure):
     _fields_ = [('gA', ctypes.c_void_p), ('Y', ctypes.c_void_p), ('coef', ctypes.c_void_p), ('W', ctypes.c_void_p), ('addend', ctypes.c_void_p),
                 ('M', ctypes.c_int64), ('Ci', ctypes.c_int32), ('Co', ctypes.c_int32), ('training', ctypes.c_int32), ('slope', ctypes.c_float),
                 ('gY', ctypes.c_void_p), ('dX', ctypes.c_void_p), ('dgamma', ctypes.c_void_p), ('dbeta', ctypes.c_void_p),
-                ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_size_t)]
+                ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_size_t),
+                ('mask_ref', ctypes.c_void_p), ('mask_slope', ctypes.c_float)]
 
 
 class Reduce64Job(ctypes.Structure):

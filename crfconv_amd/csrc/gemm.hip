@@ -78,6 +78,10 @@ struct GemmPro {
     unsigned* sync = nullptr;
     unsigned need = 0, nprod = 0;
     unsigned* fail = nullptr;
+    // the product's epilogue also applies the LeakyReLU mask of the ResNet join that produced the block's input (mref [M, N]: that
+    // join's saved output): C = mref > 0 ? v : mslope v, v = product + addend -- lrelu_bwd_kernel's arithmetic (pool.hip).  NULL: no mask.
+    const float* mref = nullptr;
+    float mslope = 1.f;
 };
 constexpr int GM_PRO_LDS = 6 * GM_PRO_MAXK + 4;     // a | b | mean | rstd | sum g1 / M | sum g1 yh / M | one flag word
 
@@ -331,6 +335,15 @@ __device__ __forceinline__ void gemm_tile(const float* __restrict__ A, const flo
                 const float4 a4 = gm_ld4<VEC>(addend + (int64_t)row * N + n, N - n);
                 o.x += a4.x; o.y += a4.y; o.z += a4.z; o.w += a4.w;
             }
+            if constexpr (PRO) {
+                if (pro.mref != nullptr) {
+                    const float4 r4 = gm_ld4<VEC>(pro.mref + (int64_t)row * N + n, N - n);
+                    o.x = r4.x > 0.f ? o.x : pro.mslope * o.x;
+                    o.y = r4.y > 0.f ? o.y : pro.mslope * o.y;
+                    o.z = r4.z > 0.f ? o.z : pro.mslope * o.z;
+                    o.w = r4.w > 0.f ? o.w : pro.mslope * o.w;
+                }
+            }
             float* cp = C + (int64_t)row * N + n;
             if constexpr (VEC) {
                 *reinterpret_cast<float4*>(cp) = o;
@@ -438,6 +451,7 @@ __global__ __launch_bounds__(GM_BLOCK) void gemm_pro_jobs_kernel(const GemmProJo
     const unsigned local = blockIdx.x - (unsigned)t.tile_base[j];
     GemmPro pro;                                        // the job's entry, pinned into scalar registers
     pro.Y = uni(t.pro[j].Y); pro.coef = uni(t.pro[j].coef); pro.fin = uni(t.pro[j].fin); pro.slope = uni(t.pro[j].slope); pro.gY = uni(t.pro[j].gY);
+    pro.mref = uni(t.pro[j].mref); pro.mslope = uni(t.pro[j].mslope);
     const unsigned tx = (unsigned)uni(t.tiles_x[j]);
     const unsigned bx = (unsigned)uni((int)(local % tx)), by = (unsigned)uni((int)(local / tx));
     __shared__ __attribute__((aligned(16))) float lds[gemm_lds_floats<1, 2, 2, 2, false, true>()];
@@ -609,6 +623,7 @@ __global__ __launch_bounds__(GM_BLOCK) void mlp_small_bwd_jobs_kernel(const Tile
     const unsigned local = (unsigned)(blk - t.tile_base[j]);
     GemmPro pro;
     pro.Y = uni(t.pro[j].Y); pro.coef = uni(t.pro[j].coef); pro.fin = uni(t.pro[j].fin); pro.slope = uni(t.pro[j].slope); pro.gY = uni(t.pro[j].gY);
+    pro.mref = uni(t.pro[j].mref); pro.mslope = uni(t.pro[j].mslope);
     pro.sync = uni(t.pro[j].sync); pro.need = (unsigned)uni((int)t.pro[j].need); pro.nprod = (unsigned)uni((int)t.pro[j].nprod); pro.fail = uni(t.pro[j].fail);
     const unsigned tx = (unsigned)uni(t.tiles_x[j]);
     const unsigned bx = (unsigned)uni((int)(local % tx)), by = (unsigned)uni((int)(local / tx));
@@ -655,6 +670,7 @@ extern "C" int crfconv_mlp_small_backward(const float* gA, const float* Y, const
     crf_mlp_bwd_job job;
     job.gA = gA; job.Y = Y; job.coef = coef; job.W = W; job.addend = addend; job.M = M; job.Ci = Ci; job.Co = Co; job.training = training;
     job.slope = slope; job.gY = gY; job.dX = dX; job.dgamma = dgamma; job.dbeta = dbeta; job.workspace = workspace; job.workspace_bytes = workspace_bytes;
+    job.mask_ref = nullptr; job.mask_slope = 1.f;
     return crfconv_mlp_small_backward_jobs(&job, 1, ticket, stream);
 }
 
@@ -706,6 +722,7 @@ static int mlp_small_backward_jobs_impl(const crf_mlp_bwd_job* jobs, int njobs, 
         blocks += (int64_t)ntile * ((b.Co + crf::BT_CH - 1) / crf::BT_CH);
         crf::GemmPro pro;
         pro.Y = b.Y; pro.coef = b.coef; pro.fin = fin; pro.slope = b.slope; pro.gY = b.gY;
+        pro.mref = b.mask_ref; pro.mslope = b.mask_slope;
         gp.A[j] = b.gA; gp.B[j] = b.W; gp.addend[j] = b.addend; gp.C[j] = b.dX; gp.pro[j] = pro; gp.M[j] = (int)b.M; gp.N[j] = b.Ci; gp.K[j] = b.Co;
         gp.tiles_x[j] = (int)((b.M + 31) / 32);
         gp.wide[j] = crf::gm_wide(b.M, b.Ci) ? 1 : 0;

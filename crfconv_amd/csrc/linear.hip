@@ -885,7 +885,9 @@ constexpr int LF_BLOCK = LF_BLOCK_, LF_WAVES = LF_BLOCK / WAVE;
 // 4x the store instructions and 3x the write requests, 983 k instead of 328 k per 21 MB -- TCP_TCC_WRITE_REQ.)
 // EPI: 0 plain store; 1 (PRO) Y += addend; 2 (not PRO) dropout mask on Y.  Template forms, so that the common kernels keep their
 // register budget (as run-time branches the two epilogues cost <2, false> and <4, true> one wavefront per SIMD each).
-constexpr int EPI_NONE = 0, EPI_ADD = 1, EPI_DROPOUT = 2;
+// 3 (PRO, VEC4) Y = mask(Y + addend; mask_ref, mask_slope), mask(v; ref, s) = ref > 0 ? v : s v -- lrelu_bwd_kernel's (pool.hip): the
+// dX of a block whose input is the output of a ResNet join is handed to that join with the join's LeakyReLU mask already applied.
+constexpr int EPI_NONE = 0, EPI_ADD = 1, EPI_DROPOUT = 2, EPI_ADD_MASK = 3;
 // NCH > 0 (round 4; Ci <= 16 NCH, VEC4): the operand fragments of ALL k chunks of a row group are requested at once and those of
 // the wavefront's NEXT row group before the current group's products (NCH <= LF_PF_MAX) -- the rolled loop (NCH = 0) pays one
 // dependent memory round trip per chunk, eight per group at 128 inputs, with two to four wavefronts per SIMD to hide them.
@@ -904,7 +906,10 @@ __global__ __launch_bounds__(LF_BLOCK) void linear_fwd_kernel(const float* __res
                                                               const float* __restrict__ addend = nullptr,
                                                               const long long* __restrict__ drop_counter = nullptr,
                                                               unsigned long long drop_seed = 0ull, unsigned drop_threshold = 0u,
-                                                              float drop_scale = 1.f) {
+                                                              float drop_scale = 1.f,
+                                                              const float* __restrict__ mask_ref = nullptr, float mask_slope = 1.f) {
+    static_assert(EPI != EPI_ADD_MASK || (PRO && VEC4), "the masked epilogue is the aligned dX product's");
+    // mask_ref [M, Co] (EPI_ADD_MASK): the saved output of the join in front of this block (this block's own input x)
     // drop_counter (not PRO, one-pointer output): Y = dropout_mask .* (X W^T) * drop_scale with the counter-based mask of
     // common.hpp (element e = row * Co + column) -- the backward of nn.Dropout applied while the gradient of the Linear
     // BEHIND the dropout is written, instead of in a pass of its own over [M, Co].
@@ -1105,6 +1110,15 @@ __global__ __launch_bounds__(LF_BLOCK) void linear_fwd_kernel(const float* __res
                             }
                         }
                     }
+                    if constexpr (EPI == EPI_ADD_MASK) {
+                        const float4 a4 = *reinterpret_cast<const float4*>(addend + orow * Co + co);
+                        const float4 r4 = *reinterpret_cast<const float4*>(mask_ref + orow * Co + co);
+                        o4.x += a4.x; o4.y += a4.y; o4.z += a4.z; o4.w += a4.w;
+                        o4.x = r4.x > 0.f ? o4.x : mask_slope * o4.x;
+                        o4.y = r4.y > 0.f ? o4.y : mask_slope * o4.y;
+                        o4.z = r4.z > 0.f ? o4.z : mask_slope * o4.z;
+                        o4.w = r4.w > 0.f ? o4.w : mask_slope * o4.w;
+                    }
                     if constexpr (EPI == EPI_DROPOUT) {
                         {
                             const unsigned long long ctr = (unsigned long long)drop_counter[0];
@@ -1138,6 +1152,18 @@ __global__ __launch_bounds__(LF_BLOCK) void linear_fwd_kernel(const float* __res
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
                         if (co + e < Co) acc[t][e] += addend[r * Co + co + e];
+                }
+            }
+            if constexpr (EPI == EPI_ADD_MASK) {
+                if (rv && co < Co) {
+                    const float4 a4 = *reinterpret_cast<const float4*>(addend + r * Co + co);
+                    const float4 r4 = *reinterpret_cast<const float4*>(mask_ref + r * Co + co);
+                    const float av[4] = {a4.x, a4.y, a4.z, a4.w}, rf[4] = {r4.x, r4.y, r4.z, r4.w};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float v = acc[t][e] + av[e];
+                        acc[t][e] = rf[e] > 0.f ? v : mask_slope * v;
+                    }
                 }
             }
             if constexpr (EPI == EPI_DROPOUT) {
@@ -1681,7 +1707,8 @@ extern "C" size_t crfconv_mlp_backward_workspace(int64_t M, int Ci, int Co) {
 static int mlp_backward_impl(const float* gA, const float* Y, const float* X, const float* Xb, int xsplit, const float* W,
                              const float* coef, float slope, int64_t M, int Ci, int Co, float* dX, float* dXb, float* dW,
                              float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, unsigned* ticket,
-                             crf_stream_t stream, const float* dX_add = nullptr);
+                             crf_stream_t stream, const float* dX_add = nullptr, const float* mask_ref = nullptr,
+                             float mask_slope = 1.f);
 
 extern "C" int crfconv_mlp_backward(const float* gA, const float* Y, const float* X, const float* W, const float* coef,
                                     float slope, int64_t M, int Ci, int Co, float* dX, float* dW, float* dgamma,
@@ -1700,6 +1727,26 @@ extern "C" int crfconv_mlp_backward_add(const float* gA, const float* Y, const f
     CRF_REQUIRE(dX != nullptr || dX_add == nullptr, CRF_ERR_ARG, "dX_add without dX");
     return mlp_backward_impl(gA, Y, X, nullptr, 0, W, coef, slope, M, Ci, Co, dX, nullptr, dW, dgamma, dbeta, workspace,
                              workspace_bytes, ticket, stream, dX_add);
+}
+
+// The same with the LeakyReLU mask of the ResNet join that PRODUCED the block's input x folded in: dX = mask(gY W + dX_add; X, mask_slope),
+// mask(v; ref, s) = ref > 0 ? v : s v -- what crfconv_add_lrelu_backward(dX, X, ...) would make of crfconv_mlp_backward_add's dX in a
+// pass of its own (same float operations: bit-identical).  dX is then the join's g1.  Ci % 4 == 0.  dX_add == NULL (the alias had no
+// gradient): the plain product, then that pass in place.
+extern "C" int crfconv_add_lrelu_backward(const float* gout, const float* out, int64_t n, float slope, float* gin, crf_stream_t stream);
+extern "C" int crfconv_mlp_backward_add_mask(const float* gA, const float* Y, const float* X, const float* W, const float* coef,
+                                             float slope, int64_t M, int Ci, int Co, const float* dX_add, float mask_slope, float* dX,
+                                             float* dW, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
+                                             unsigned* ticket, crf_stream_t stream) {
+    CRF_REQUIRE(dX != nullptr && Ci % 4 == 0, CRF_ERR_ARG, "the masked form writes dX, Ci=%d a multiple of 4", Ci);
+    if (dX_add == nullptr) {
+        if (int rc = mlp_backward_impl(gA, Y, X, nullptr, 0, W, coef, slope, M, Ci, Co, dX, nullptr, dW, dgamma, dbeta, workspace,
+                                       workspace_bytes, ticket, stream))
+            return rc;
+        return crfconv_add_lrelu_backward(dX, X, M * Ci, mask_slope, dX, stream);
+    }
+    return mlp_backward_impl(gA, Y, X, nullptr, 0, W, coef, slope, M, Ci, Co, dX, nullptr, dW, dgamma, dbeta, workspace,
+                             workspace_bytes, ticket, stream, dX_add, X, mask_slope);
 }
 
 // The block's input was the column concatenation [Xa | Xb]: dXa [M, split], dXb [M, Ci - split] (both or neither NULL).
@@ -1775,8 +1822,10 @@ extern "C" int crfconv_mlp_dw_jobs_hosting(const crf_mlp_dw_job* jobs, int njobs
 static int mlp_backward_impl(const float* gA, const float* Y, const float* X, const float* Xb, int xsplit, const float* W,
                              const float* coef, float slope, int64_t M, int Ci, int Co, float* dX, float* dXb, float* dW,
                              float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, unsigned* ticket,
-                             crf_stream_t stream, const float* dX_add) {
+                             crf_stream_t stream, const float* dX_add, const float* mask_ref, float mask_slope) {
     CRF_REQUIRE(gA && Y && X && W && coef && dgamma && dbeta && workspace, CRF_ERR_ARG, "null pointer");
+    CRF_REQUIRE(mask_ref == nullptr || (dX_add != nullptr && dX != nullptr && Ci % 4 == 0 && Co % 4 == 0), CRF_ERR_ARG,
+                "the masked dX takes an addend and widths that are multiples of 4 (Ci=%d Co=%d)", Ci, Co);
     CRF_REQUIRE(dX_add == nullptr || dXb == nullptr, CRF_ERR_ARG, "dX_add is for the one-operand form");
     CRF_REQUIRE(crfconv_mlp_backward_supported(M, Ci, Co) == 1, CRF_ERR_UNSUPPORTED, "shape M=%lld Ci=%d Co=%d not supported",
                 (long long)M, Ci, Co);
@@ -1827,9 +1876,9 @@ static int mlp_backward_impl(const float* gA, const float* Y, const float* X, co
         const size_t lds = lf_lds_bytes(gCi, gCo, true);
         const bool vec4 = (gCi % 4) == 0 && (gCo % 4) == 0;
         const int nch = lf_hoist_chunks(gCi, vec4);
-#define DX4(T, V, E, N) hipLaunchKernelGGL((crf::linear_fwd_kernel<T, true, V, E, N>), grid, blk, lds, st, gA, W, (const float*)nullptr, M, gCi, gCo, 1, dX, (float*)nullptr, Y, pro, slope, (const float*)nullptr, 0, dXb, xsplit, dX_add)
+#define DX4(T, V, E, N) hipLaunchKernelGGL((crf::linear_fwd_kernel<T, true, V, E, N>), grid, blk, lds, st, gA, W, (const float*)nullptr, M, gCi, gCo, 1, dX, (float*)nullptr, Y, pro, slope, (const float*)nullptr, 0, dXb, xsplit, dX_add, (const long long*)nullptr, 0ull, 0u, 1.f, mask_ref, mask_slope)
 #define DX3(T, V, E) do { if (V && nch == 1) DX4(T, V, E, 1); else if (V && nch == 2) DX4(T, V, E, 2); else if (V && nch == 4) DX4(T, V, E, 4); else if (V && nch == 8) DX4(T, V, E, 8); else DX4(T, V, E, 0); } while (0)
-#define DX2(T, V) do { if (dX_add != nullptr) DX3(T, V, crf::EPI_ADD); else DX3(T, V, crf::EPI_NONE); } while (0)
+#define DX2(T, V) do { if (mask_ref != nullptr) DX3(T, V, crf::EPI_ADD_MASK); else if (dX_add != nullptr) DX3(T, V, crf::EPI_ADD); else DX3(T, V, crf::EPI_NONE); } while (0)
 #define DX(T) do { if (vec4) DX2(T, true); else if (dX_add != nullptr) DX4(T, false, crf::EPI_ADD, 0); else DX4(T, false, crf::EPI_NONE, 0); } while (0)
         switch (tco) {
             case 1: DX(1); break;

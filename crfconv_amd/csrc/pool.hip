@@ -166,6 +166,18 @@ __global__ __launch_bounds__(256) void lrelu_bwd_kernel(const float* __restrict_
                                  o.z > 0.f ? u.z : slope * u.z, o.w > 0.f ? u.w : slope * u.w));
 }
 
+// gin = mask(a + b; ref, slope): add_lrelu_kernel(slope 1) followed by lrelu_bwd_kernel, the sum kept in registers
+__global__ __launch_bounds__(256) void add_mask_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                       const float* __restrict__ ref, int64_t n4, float slope,
+                                                       float* __restrict__ gin) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n4) return;
+    const float4 u = ld4(a + 4 * t), v = ld4(b + 4 * t), o = ld4(ref + 4 * t);
+    const float4 s = make_float4(u.x + v.x, u.y + v.y, u.z + v.z, u.w + v.w);
+    st4(gin + 4 * t, make_float4(o.x > 0.f ? s.x : slope * s.x, o.y > 0.f ? s.y : slope * s.y,
+                                 o.z > 0.f ? s.z : slope * s.z, o.w > 0.f ? s.w : slope * s.w));
+}
+
 }  // namespace crf
 
 using namespace crf;
@@ -244,6 +256,16 @@ extern "C" int crfconv_add_lrelu_backward(const float* gout, const float* out, i
     CRF_REQUIRE(n > 0 && n % 4 == 0 && n < ((int64_t)1 << 40), CRF_ERR_ARG, "n=%lld must be a positive multiple of 4", (long long)n);
     hipLaunchKernelGGL(crf::lrelu_bwd_kernel, dim3((unsigned)crf::cdiv(n / 4, 256)), dim3(256), 0, crf::as_stream(stream), gout,
                        out, n / 4, slope, gin);
+    CRF_LAUNCH_CHECK();
+    return CRF_OK;
+}
+
+extern "C" int crfconv_add_mask(const float* a, const float* b, const float* ref, int64_t n, float slope, float* gin,
+                                crf_stream_t stream) {
+    CRF_REQUIRE(a && b && ref && gin, CRF_ERR_ARG, "null pointer");
+    CRF_REQUIRE(n > 0 && n % 4 == 0 && n < ((int64_t)1 << 40), CRF_ERR_ARG, "n=%lld must be a positive multiple of 4", (long long)n);
+    hipLaunchKernelGGL(crf::add_mask_kernel, dim3((unsigned)crf::cdiv(n / 4, 256)), dim3(256), 0, crf::as_stream(stream), a, b, ref,
+                       n / 4, slope, gin);
     CRF_LAUNCH_CHECK();
     return CRF_OK;
 }

@@ -57,17 +57,18 @@ class MLP(nn.Module):
         return x
 
 
-def mlp_fork(mlp, x):
+def mlp_fork(mlp, x, input_mask=None):
     """(mlp(x), x') for an input with a second consumer (the ResNet block: lin_in(x) and shortcut(x),
     models/point_conv_big.py:83-88).  x' is x; where the fused block applies it is an alias whose gradient is added inside the
-    block's backward while dX is written, instead of by an accumulation pass of autograd's (ops._MLPBlock, fork)."""
+    block's backward while dX is written, instead of by an accumulation pass of autograd's (ops._MLPBlock, fork).
+    input_mask: the ops.JoinMask of the join that produced x, from a caller who knows that x has no use outside this fork chain."""
     if (mlp.training and mlp.bn is not None and x.dtype == torch.float32 and mlp.bn.batch_norm.affine and x.requires_grad
             and mlp.lin.out_features % 4 == 0 and mlp.lin.out_features <= 1024
             and (mlp.activation is None or isinstance(mlp.activation, nn.LeakyReLU))
             and ops.mlp_block_ok(x, mlp.lin.weight, mlp.lin.bias, mlp.bn.batch_norm, True)):
         require_gpu(x)
         slope = 1.0 if mlp.activation is None else mlp.activation.negative_slope
-        return ops.mlp_block(x, mlp.lin.weight, mlp.bn.batch_norm, slope, fork=True)
+        return ops.mlp_block(x, mlp.lin.weight, mlp.bn.batch_norm, slope, fork=True, input_mask=input_mask)
     return mlp(x), x
 
 
@@ -80,10 +81,10 @@ def _group_spec(mlp, x):
     return mlp.lin.weight, mlp.bn.batch_norm, (1.0 if mlp.activation is None else mlp.activation.negative_slope)
 
 
-def mlp_group(pairs, shared=False):
+def mlp_group(pairs, shared=False, input_mask=None):
     """[(mlp, x, fork)] -> [mlp(x) or (mlp(x), x_alias)] with all the MLPs in ONE autograd node of two launches each way
     (ops.mlp_group: coarse-level training blocks whose inputs are all ready), or None when that form does not apply to every member
-    -- the caller then runs them one by one."""
+    -- the caller then runs them one by one.  input_mask (shared): as mlp_fork's, for the tensor the first two MLPs read."""
     blocks = []
     for mlp, x, fork in pairs:
         spec = _group_spec(mlp, x)
@@ -91,16 +92,17 @@ def mlp_group(pairs, shared=False):
             return None
         require_gpu(x)
         blocks.append((x, spec[0], spec[1], spec[2], fork))
-    return ops.mlp_group(blocks, shared=shared)
+    return ops.mlp_group(blocks, shared=shared, input_mask=input_mask)
 
 
-def mlp_join(mlp, x, skip, slope=0.01):
+def mlp_join(mlp, x, skip, slope=0.01, mask=None):
     """leaky_relu(mlp(x) + skip, slope) for an MLP without activation -- the tail of a ResNet block
     (models/point_conv_big.py:84-88).  One fused node (BatchNorm + add + LeakyReLU in a single pass) where it applies
-    (training, MFMA-sized rows), else the module followed by ops.add_lrelu."""
+    (training, MFMA-sized rows), else the module followed by ops.add_lrelu.  mask: the ops.JoinMask the fused node shares with the
+    node that writes its output's gradient (left unarmed by the fallback)."""
     if (mlp.training and mlp.bn is not None and mlp.activation is None and mlp.lin.bias is None and x.dtype == torch.float32
             and mlp.bn.batch_norm.affine and mlp.lin.out_features % 4 == 0):
-        out = ops.mlp_block_join(x, mlp.lin.weight, mlp.bn.batch_norm, skip, slope)
+        out = ops.mlp_block_join(x, mlp.lin.weight, mlp.bn.batch_norm, skip, slope, mask=mask)
         if out is not None:
             return out
     return ops.add_lrelu(mlp(x), skip, slope)

@@ -86,25 +86,29 @@ class ResNetBBlock(nn.Module):
         pooled = ops.neighbor_maxpool(_flat(x), table_of(idx, x.shape[1]))
         return pooled.reshape(x.shape[0], -1, x.shape[-1])
 
-    def forward(self, x, pos, neighbor_idx, return_input_alias=False, prefold=None):
+    def forward(self, x, pos, neighbor_idx, return_input_alias=False, prefold=None, join_mask=None, input_mask=None):
         """return_input_alias=True: also returns the block's input as the LAST alias of its fork chain (x -> lin_in -> strided
         shortcut): a further consumer of x -- the decoder stage that takes it as skip feature -- reads the alias, and its
-        gradient is added inside this block's backward kernels instead of by an accumulation pass of autograd's."""
+        gradient is added inside this block's backward kernels instead of by an accumulation pass of autograd's.
+        join_mask / input_mask (ops.JoinMask): the handshakes of this block's join with the consumer of its output, and of the join that
+        produced x with this block.  input_mask is a promise of the CALLER's that x is used nowhere but here and through the returned
+        alias (the block cannot know); lin_in -- the last link of the fork chain -- then writes x's gradient with that join's LeakyReLU
+        mask applied, and the join skips its mask pass."""
         strided = not torch.is_tensor(pos)
         skip = None
         sc = self.shortcut
         grouped = None
         if isinstance(sc, MLP):
             # lin_in and the shortcut read the same tensor: at the coarse levels ONE node runs both (two launches each way instead of four)
-            grouped = mlp_group([(self.lin_in, x, True), (sc, x, False)], shared=True)
+            grouped = mlp_group([(self.lin_in, x, True), (sc, x, False)], shared=True, input_mask=input_mask)
         if grouped is not None:
             (h_in, x), skip = grouped
             if strided:
                 skip = self.max_pooling(skip, neighbor_idx)
             y = self.point_conv(h_in, pos, neighbor_idx, prefold=prefold)
-            out = mlp_join(self.lin_out, y, skip, 0.01)
+            out = mlp_join(self.lin_out, y, skip, 0.01, mask=join_mask)
             return (out, x) if return_input_alias else out
-        h_in, x = mlp_fork(self.lin_in, x)                 # x: now the alias whose gradient lin_in's backward adds to its own
+        h_in, x = mlp_fork(self.lin_in, x, input_mask)                # x: now the alias whose gradient lin_in's backward adds to its own
         if (strided and self.training and isinstance(sc, MLP) and sc.bn is not None and sc.activation is None
                 and sc.lin.bias is None and x.dtype == torch.float32 and sc.bn.batch_norm.affine):
             # shortcut MLP + max-pool as one node: BatchNorm applied while the pool gathers (ops.mlp_block_pool)
@@ -123,7 +127,7 @@ class ResNetBBlock(nn.Module):
             if strided:                                    # strided block: pool the shortcut onto the coarse points
                 skip = self.max_pooling(skip, neighbor_idx)
         y = self.point_conv(h_in, pos, neighbor_idx, prefold=prefold)
-        out = mlp_join(self.lin_out, y, skip, 0.01)        # lin_out + add + F.leaky_relu (default slope), as the reference
+        out = mlp_join(self.lin_out, y, skip, 0.01, mask=join_mask)        # lin_out + add + F.leaky_relu (default slope), as the reference
         return (out, x) if return_input_alias else out
 
 
@@ -197,16 +201,20 @@ class PointConvResNet(Base):
         pre = [None] * len(plan)
         if self.training and data.x.is_cuda and not ops.state.no_prefold:      # BatchNorm-1 of all ten weight MLPs folded in ONE launch, up front
             pre = ops.point_conv_prefold([blk.point_conv.prefold_entry(p, i) for blk, p, i in plan], True)
-        h = plan[0][0](data.x, plan[0][1], plan[0][2], prefold=pre[0])
-        h = plan[1][0](h, plan[1][1], plan[1][2], prefold=pre[1])
+        # block n's output is read by block n + 1 alone (the decoder takes the alias block n + 1 returns): one handshake per join, so
+        # that block n + 1 writes the gradient with block n's LeakyReLU mask applied (ops.JoinMask); conv5_2's output goes to the decoder
+        masks = [ops.JoinMask() for _ in plan]
+        h = plan[0][0](data.x, plan[0][1], plan[0][2], prefold=pre[0], join_mask=masks[0])
+        h = plan[1][0](h, plan[1][1], plan[1][2], prefold=pre[1], join_mask=masks[1], input_mask=masks[0])
         skips = [h]
         for lvl in range(1, len(WIDTHS)):
             if lvl == 2 and self.phase_hook is not None:
                 self.phase_hook('coarse')                      # from here to the decoder's level 1 the launches are coarse-level ones
             (b1, p1, i1), (b2, p2, i2) = plan[2 * lvl], plan[2 * lvl + 1]
             # the level's output has three consumers (this block's lin_in and shortcut, the decoder): one fork chain, no add pass
-            h, skips[-1] = b1(h, p1, i1, return_input_alias=True, prefold=pre[2 * lvl])
-            h = b2(h, p2, i2, prefold=pre[2 * lvl + 1])
+            h, skips[-1] = b1(h, p1, i1, return_input_alias=True, prefold=pre[2 * lvl], join_mask=masks[2 * lvl], input_mask=masks[2 * lvl - 1])
+            h = b2(h, p2, i2, prefold=pre[2 * lvl + 1], join_mask=masks[2 * lvl + 1] if lvl + 1 < len(WIDTHS) else None,
+                   input_mask=masks[2 * lvl])
             skips.append(h)
         ops.flush_riders()
         for d, mat, lvl in zip(decoders, mats, range(len(WIDTHS) - 2, -1, -1)):

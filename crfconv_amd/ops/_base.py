@@ -162,6 +162,9 @@ class _State:
     no_join = False              # tests: True = lin_out, bn_apply and add_lrelu as separate nodes (the fused nodes must give the same results)
     no_fork = False              # tests: True = autograd's own accumulation pass instead of the fork chain
     no_prefold = False           # tests: True = one fold launch inside every PointConv layer
+    # the LeakyReLU mask of a ResNet join's backward applied by the kernel that writes the join's gradient (ops.mlp.JoinMask);
+    # CRFCONV_NO_MASK_FOLD=1: every join runs its own mask pass again (A/B runs of bench.py)
+    no_mask_fold = __import__('os').environ.get('CRFCONV_NO_MASK_FOLD') is not None
     # set by check_gridsync after a barrier failure (CRFCONV_NO_ONE_LAUNCH_MLP: from the start): launch-separated forward from then on
     small_mlp_disabled = __import__('os').environ.get('CRFCONV_NO_ONE_LAUNCH_MLP') is not None
     # the two launches of a coarse-level MLP backward (tile sums, dX product) as one whose product workgroups wait for the sums inside

@@ -10,6 +10,28 @@ from ._base import _f32c, _mlp_ticket, _ticket, gridsync_ws, state
 # ------------------------------------------------------------------------------ Linear -> BatchNorm -> LeakyReLU as one op
 
 
+class JoinMask:
+    """Forward-time handshake between a ResNet join node (_MLPBlockJoin / _MLPSmallJoin: out = lrelu(BN(lin_out(y)) + skip, slope)) and
+    the ONE node that writes the total gradient of `out` -- the next block's lin_in, last link of the fork chain, or its shared group.
+    The caller that wires the two (PointConvResNet._forward) makes one object per join and hands it to both: the join arms it (`slope`)
+    when it runs as a fused node, the consumer sets `folded` when its backward will write g1 = g lrelu'(out) itself (its dX epilogue,
+    mask reference = its own saved input, which IS `out`).  The join's backward then uses the incoming gradient as g1 and runs no mask
+    pass.  Both decisions are taken while the forward is issued, so a captured backward replays the same launches."""
+    __slots__ = ('slope', 'folded')
+
+    def __init__(self):
+        self.slope = None          # set by the join: its LeakyReLU slope (None: no fused join node in front)
+        self.folded = False        # set by the consumer
+
+
+def _take_mask(mask, ok):
+    """The slope a consumer node folds into its dX (None: no fold) -- an armed handshake, widths its masked kernels take."""
+    if mask is None or mask.slope is None or mask.folded or state.no_mask_fold or not ok:
+        return None
+    mask.folded = True
+    return float(mask.slope)
+
+
 class _MLPBlock(torch.autograd.Function):
     """A = lrelu(BN_train(x W^T), slope) (models/common.py:34-40).  Forward: the MFMA Linear with statistic records in its
     epilogue, coefficients, one fused apply pass.  Backward: crfconv_mlp_backward -- one pass over (gA, y, x) for dgamma,
@@ -20,11 +42,13 @@ class _MLPBlock(torch.autograd.Function):
     (crfconv_mlp_backward_add) instead of autograd running an accumulation pass over three [M, Ci] tensors."""
 
     @staticmethod
-    def forward(ctx, x_in, W, gamma, beta, run_mean, run_var, momentum, eps, slope, fork=False):
+    def forward(ctx, x_in, W, gamma, beta, run_mean, run_var, momentum, eps, slope, fork=False, mask=None):
         x = x_in.contiguous()
         Wc = W.contiguous()
         m, ci = x.shape
         co = Wc.shape[0]
+        # x is a join's output and dX its total gradient (JoinMask): the join's LeakyReLU mask goes into the dX epilogue
+        ctx.mask_slope = _take_mask(mask, fork and ci % 4 == 0 and co % 4 == 0)
         y, rec = _mfma_matmul(x, Wc, None, False, True)
         coef = torch.empty(4 * co, dtype=torch.float32, device=x.device)
         g, b = _f32c(gamma), _f32c(beta)
@@ -53,9 +77,16 @@ class _MLPBlock(torch.autograd.Function):
         dW, dgamma, dbeta = (o[0] for o in outs)
         nbytes = _lib.load().crfconv_mlp_backward_workspace(m, ci, co)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        _lib.call('crfconv_mlp_backward_add', ptr(gA), ptr(y), ptr(x), ptr(W), ptr(coef), ctx.slope, m, ci, co, ptr(add), ptr(dX),
-                  ptr(None if dfr else dW), ptr(dgamma), ptr(dbeta), ptr(ws), nbytes, _mlp_ticket(dev), stream_ptr())
-        return dX, *_mlp_param_rets(ctx.prm, outs, dfr, ws, m, ci, co, coef), None, None, None, None, None, None
+        if ctx.mask_slope is not None:
+            if dX is None:
+                raise _lib.CrfConvError('_MLPBlock: a folded join mask without an input gradient')
+            _lib.call('crfconv_mlp_backward_add_mask', ptr(gA), ptr(y), ptr(x), ptr(W), ptr(coef), ctx.slope, m, ci, co, ptr(add),
+                      ctx.mask_slope, ptr(dX), ptr(None if dfr else dW), ptr(dgamma), ptr(dbeta), ptr(ws), nbytes, _mlp_ticket(dev),
+                      stream_ptr())
+        else:
+            _lib.call('crfconv_mlp_backward_add', ptr(gA), ptr(y), ptr(x), ptr(W), ptr(coef), ctx.slope, m, ci, co, ptr(add), ptr(dX),
+                      ptr(None if dfr else dW), ptr(dgamma), ptr(dbeta), ptr(ws), nbytes, _mlp_ticket(dev), stream_ptr())
+        return dX, *_mlp_param_rets(ctx.prm, outs, dfr, ws, m, ci, co, coef), None, None, None, None, None, None, None
 
 
 
@@ -64,11 +95,13 @@ class _MLPBlockJoin(torch.autograd.Function):
     """out = lrelu(BN_train(x W^T) + skip, slope): the tail of a ResNet block (models/point_conv_big.py:84-88: lin_out has no
     activation, then F.leaky_relu(x + shortcut)) as one node -- forward: MFMA Linear with statistic records, coefficients, ONE
     pass for BatchNorm + residual add + LeakyReLU (crfconv_bn_apply_add; the normalised tensor never reaches memory);
-    backward: g1 = g lrelu'(out) is both the skip gradient and the gA of crfconv_mlp_backward (BatchNorm without activation)."""
+    backward: g1 = g lrelu'(out) is both the skip gradient and the gA of crfconv_mlp_backward (BatchNorm without activation).
+    mask (JoinMask): when the node that writes g has folded the mask into its epilogue, g IS g1 and the mask pass does not run."""
 
     @staticmethod
-    def forward(ctx, x, W, gamma, beta, run_mean, run_var, momentum, eps, skip, slope):
+    def forward(ctx, x, W, gamma, beta, run_mean, run_var, momentum, eps, skip, slope, mask=None):
         x, Wc, skip = x.contiguous(), W.contiguous(), skip.contiguous()
+        ctx.mask = mask
         m, ci = x.shape
         co = Wc.shape[0]
         y, rec = _mfma_matmul(x, Wc, None, False, True)
@@ -89,9 +122,12 @@ class _MLPBlockJoin(torch.autograd.Function):
         co = W.shape[0]
         dev = x.device
         g = g.contiguous()
-        g1 = torch.empty_like(g)
         st = stream_ptr()
-        _lib.call('crfconv_add_lrelu_backward', ptr(g), ptr(out), out.numel(), ctx.slope, ptr(g1), st)
+        if ctx.mask is not None and ctx.mask.folded:
+            g1 = g
+        else:
+            g1 = torch.empty_like(g)
+            _lib.call('crfconv_add_lrelu_backward', ptr(g), ptr(out), out.numel(), ctx.slope, ptr(g1), st)
         dX = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         outs, dfr = _mlp_param_outs(ctx.prm, W, dev)       # (dW, dgamma, dbeta) targets; dfr: dW finished at the end of the pass
         dW, dgamma, dbeta = (o[0] for o in outs)
@@ -100,7 +136,7 @@ class _MLPBlockJoin(torch.autograd.Function):
         _lib.call('crfconv_mlp_backward', ptr(g1), ptr(y), ptr(x), ptr(W), ptr(coef), 1.0, m, ci, co, ptr(dX), ptr(None if dfr else dW),
                   ptr(dgamma), ptr(dbeta), ptr(ws), nbytes, _mlp_ticket(dev), st)
         gskip = g1 if ctx.needs_input_grad[8] else None
-        return dX, *_mlp_param_rets(ctx.prm, outs, dfr, ws, m, ci, co, coef), None, None, None, None, gskip, None
+        return dX, *_mlp_param_rets(ctx.prm, outs, dfr, ws, m, ci, co, coef), None, None, None, None, gskip, None, None
 
 
 
@@ -431,10 +467,11 @@ def _small_bwd_jobs(jobs, n, dev, st):
         _lib.call('crfconv_mlp_small_backward_jobs', ctypes.cast(jobs, ctypes.c_void_p), n, ptr(_ticket(dev)), st)
 
 
-def _small_bwd(gA, y, coef, W, addend, slope, dgamma, dbeta, need_dx):
+def _small_bwd(gA, y, coef, W, addend, slope, dgamma, dbeta, need_dx, mask=None):
     """(gY, dX) of a coarse-level MLP block: BatchNorm(+LeakyReLU) backward and dX = gY W (+ addend) as TWO launches
     (crfconv_mlp_small_backward: tile sums, then the product with gY formed in its operand load), else -- no dX wanted, widths the
-    fused form does not take -- crfconv_bn_backward followed by the plain product."""
+    fused form does not take -- crfconv_bn_backward followed by the plain product.  mask = (ref [M, Ci], slope): the product's
+    epilogue applies a join's LeakyReLU mask (crf_mlp_bwd_job.mask_ref; _MLPSmall checked at forward time that the fused form applies)."""
     m, co = y.shape
     ci = W.shape[1]
     dev = y.device
@@ -447,9 +484,12 @@ def _small_bwd(gA, y, coef, W, addend, slope, dgamma, dbeta, need_dx):
         add = None if addend is None else addend.contiguous()
         jobs = (_lib.MlpBwdJob * 1)()
         jobs[0] = _lib.MlpBwdJob(gA.data_ptr(), y.data_ptr(), coef.data_ptr(), W.data_ptr(), None if add is None else add.data_ptr(), m, ci, co, 1,
-                                 float(slope), gY.data_ptr(), dX.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), nbytes)
+                                 float(slope), gY.data_ptr(), dX.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), nbytes,
+                                 None if mask is None else mask[0].data_ptr(), 1.0 if mask is None else float(mask[1]))
         _small_bwd_jobs(jobs, 1, dev, stream_ptr())
         return gY, dX
+    if mask is not None:
+        raise _lib.CrfConvError('_small_bwd: a folded join mask needs the fused dX product (%d x %d -> %d)' % (m, ci, co))
     nbytes = lib.crfconv_bn_workspace(m, co)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     _lib.call('crfconv_bn_backward', ptr(gA), ptr(y), ptr(coef), m, co, 1, float(slope), ptr(gY), ptr(dgamma), ptr(dbeta), ptr(ws),
@@ -493,11 +533,12 @@ def _small_fwd(x, Wc, gamma, beta, run_mean, run_var, momentum, eps, slope, skip
 
 class _MLPSmallJoin(torch.autograd.Function):
     """_MLPBlockJoin at the coarse levels: the one-launch Linear + BatchNorm kernel (csrc/mlp_small.hip) also adds the skip and
-    applies the join's LeakyReLU to the tile it holds in registers (crfconv_mlp_small_forward_join)."""
+    applies the join's LeakyReLU to the tile it holds in registers (crfconv_mlp_small_forward_join).  mask: as _MLPBlockJoin."""
 
     @staticmethod
-    def forward(ctx, x, W, gamma, beta, run_mean, run_var, momentum, eps, skip, slope):
+    def forward(ctx, x, W, gamma, beta, run_mean, run_var, momentum, eps, skip, slope, mask=None):
         x, Wc, skip = x.contiguous(), W.contiguous(), skip.contiguous()
+        ctx.mask = mask
         y, out, coef = _small_fwd(x, Wc, gamma, beta, run_mean, run_var, momentum, eps, 1.0, skip, slope)
         ctx.prm = (W, gamma, beta)
         ctx.save_for_backward(x, Wc, y, coef, out)
@@ -513,25 +554,29 @@ class _MLPSmallJoin(torch.autograd.Function):
         dev = x.device
         g = g.contiguous()
         st = stream_ptr()
-        g1 = torch.empty_like(g)
-        _lib.call('crfconv_add_lrelu_backward', ptr(g), ptr(out), out.numel(), ctx.slope, ptr(g1), st)
+        if ctx.mask is not None and ctx.mask.folded:
+            g1 = g
+        else:
+            g1 = torch.empty_like(g)
+            _lib.call('crfconv_add_lrelu_backward', ptr(g), ptr(out), out.numel(), ctx.slope, ptr(g1), st)
         outs = [_param_out(q, (co,), dev) for q in ctx.prm[1:]]      # (dgamma, dbeta) targets
         dgamma, dbeta = outs[0][0], outs[1][0]
         gY, dX = _small_bwd(g1, y, coef, W, None, 1.0, dgamma, dbeta, ctx.needs_input_grad[0])
         gskip = g1 if ctx.needs_input_grad[8] else None
         if _defer_ok(ctx.params):
             _defer_weight_grad(gY, x, ctx.params, False)
-            return dX, None, *(_param_ret(q, o, k) for q, (o, k) in zip(ctx.prm[1:], outs)), None, None, None, None, gskip, None
+            return dX, None, *(_param_ret(q, o, k) for q, (o, k) in zip(ctx.prm[1:], outs)), None, None, None, None, gskip, None, None
         dW = torch.empty((co, ci), dtype=torch.float32, device=dev)
         nb = _lib.load().crfconv_linear_wgrad_workspace(m, co, ci)
         wsw = torch.empty(nb, dtype=torch.uint8, device=dev)
         _lib.call('crfconv_linear_wgrad', ptr(gY), ptr(x), m, co, ci, ptr(dW), None, ptr(wsw), nb, st)
-        return dX, dW, *(_param_ret(q, o, k) for q, (o, k) in zip(ctx.prm[1:], outs)), None, None, None, None, gskip, None
+        return dX, dW, *(_param_ret(q, o, k) for q, (o, k) in zip(ctx.prm[1:], outs)), None, None, None, None, gskip, None, None
 
 
-def mlp_block_join(x, W, bn, skip, slope):
+def mlp_block_join(x, W, bn, skip, slope, mask=None):
     """lrelu(BatchNorm_train(x W^T) + skip, slope) as one node where the big-level fused block applies, else None (the
-    caller then runs its own lin_out + add_lrelu)."""
+    caller then runs its own lin_out + add_lrelu).  mask: the JoinMask shared with the node that will write the output's total gradient;
+    armed here, so a consumer only folds the mask behind a fused join node."""
     if state.no_join or skip.shape[:-1] != x.shape[:-1] or skip.shape[-1] != W.shape[0] or skip.dtype != torch.float32:
         return None
     m = x.numel() // x.shape[-1]
@@ -542,8 +587,12 @@ def mlp_block_join(x, W, bn, skip, slope):
     tick(bn)
     mom = 0.1 if bn.momentum is None else bn.momentum
     fn = _MLPSmallJoin if _mlp_small_ok(m, ci, co) else _MLPBlockJoin      # coarse levels: folded into the one-launch kernel
+    if mask is not None and not state.no_mask_fold and torch.is_grad_enabled():
+        mask.slope = float(slope)
+    else:
+        mask = None
     out = fn.apply(x.reshape(-1, ci), W, bn.weight, bn.bias, bn.running_mean, bn.running_var, mom, bn.eps,
-                   skip.reshape(-1, co), slope)
+                   skip.reshape(-1, co), slope, mask)
     return out.reshape(x.shape[:-1] + (co,))
 
 
@@ -564,9 +613,11 @@ class _MLPSmall(torch.autograd.Function):
     addend of the dX product (the GEMM's beta = 1 epilogue)."""
 
     @staticmethod
-    def forward(ctx, x_in, W, gamma, beta, run_mean, run_var, momentum, eps, slope, fork=False):
+    def forward(ctx, x_in, W, gamma, beta, run_mean, run_var, momentum, eps, slope, fork=False, mask=None):
         x = x_in.contiguous()
         Wc = W.contiguous()
+        # as _MLPBlock: the mask of the join that produced x, applied by the dX product's epilogue (crf_mlp_bwd_job.mask_ref)
+        ctx.mask_slope = _take_mask(mask, fork and _lib.load().crfconv_mlp_small_backward_supported(x.shape[0], x.shape[1], Wc.shape[0]) == 1)
         y, out, coef = _small_fwd(x, Wc, gamma, beta, run_mean, run_var, momentum, eps, slope)
         ctx.prm = (W, gamma, beta)
         ctx.save_for_backward(x, Wc, y, coef)
@@ -587,15 +638,15 @@ class _MLPSmall(torch.autograd.Function):
         outs = [_param_out(q, (co,), dev) for q in ctx.prm[1:]]      # (dgamma, dbeta) targets
         dgamma, dbeta = outs[0][0], outs[1][0]
         gY, dX = _small_bwd(gA, y, coef, W, None if g_alias is None else g_alias.reshape(m, ci), ctx.slope, dgamma, dbeta,
-                            ctx.needs_input_grad[0])
+                            ctx.needs_input_grad[0], None if ctx.mask_slope is None else (x, ctx.mask_slope))
         if _defer_ok(ctx.params):
             _defer_weight_grad(gY, x, ctx.params, False)
-            return dX, None, *(_param_ret(q, o, k) for q, (o, k) in zip(ctx.prm[1:], outs)), None, None, None, None, None, None
+            return dX, None, *(_param_ret(q, o, k) for q, (o, k) in zip(ctx.prm[1:], outs)), None, None, None, None, None, None, None
         dW = torch.empty((co, ci), dtype=torch.float32, device=dev)          # same partials + reduction as the deferred form
         nb = _lib.load().crfconv_linear_wgrad_workspace(m, co, ci)
         wsw = torch.empty(nb, dtype=torch.uint8, device=dev)
         _lib.call('crfconv_linear_wgrad', ptr(gY), ptr(x), m, co, ci, ptr(dW), None, ptr(wsw), nb, stream_ptr())
-        return dX, dW, *(_param_ret(q, o, k) for q, (o, k) in zip(ctx.prm[1:], outs)), None, None, None, None, None, None
+        return dX, dW, *(_param_ret(q, o, k) for q, (o, k) in zip(ctx.prm[1:], outs)), None, None, None, None, None, None, None
 
 
 
@@ -608,12 +659,13 @@ class _MLPSmallGroup(torch.autograd.Function):
     unary_nn[i] / pairwise_nn[i] of a CRF layer (models/continuous_crf_conv_big.py:56-60), shortcut / lin_in of a strided ResNet block
     (models/point_conv_big.py:79-88).  Per block: (x, W, gamma, beta, run_mean, run_var, momentum, eps, slope, fork); a block with
     fork returns (out, x_alias) as _MLPBlock does.  shared: blocks 0 and 1 read the SAME tensor -- their input gradients are summed by
-    one library launch here and returned once (autograd would add them with a framework kernel)."""
+    one library launch here and returned once (autograd would add them with a framework kernel).  mask (JoinMask, shared only): the
+    shared input is a join's output and that sum its total gradient -- the sum launch applies the join's mask (crfconv_add_mask)."""
 
     NARG = 10
 
     @staticmethod
-    def forward(ctx, shared, *args):
+    def forward(ctx, shared, mask, *args):
         n = len(args) // _MLPSmallGroup.NARG
         jobs = [args[i * _MLPSmallGroup.NARG:(i + 1) * _MLPSmallGroup.NARG] for i in range(n)]
         lib = _lib.load()
@@ -650,6 +702,7 @@ class _MLPSmallGroup(torch.autograd.Function):
         _lib.call('crfconv_bn_apply_from_records_jobs', ctypes.cast(ba, ctypes.c_void_p), n, st)
         del tmp
         ctx.n, ctx.prm, ctx.slopes, ctx.forks, ctx.shared = n, prm, slopes, forks, bool(shared)
+        ctx.mask_slope = _take_mask(mask, bool(shared) and n >= 2 and forks[0] and ctx.needs_input_grad[2])
         ctx.save_for_backward(*keep)
         ctx.set_materialize_grads(False)
         return tuple(outs)
@@ -674,7 +727,7 @@ class _MLPSmallGroup(torch.autograd.Function):
                 g_alias = grads[gi]
                 gi += 1
             gA = torch.zeros_like(y) if gA is None else gA.contiguous()
-            need_dx = ctx.needs_input_grad[1 + (0 if (ctx.shared and i == 1) else i) * _MLPSmallGroup.NARG]
+            need_dx = ctx.needs_input_grad[2 + (0 if (ctx.shared and i == 1) else i) * _MLPSmallGroup.NARG]
             outs = [_param_out(q, (co,), dev) for q in ctx.prm[i][1:]]      # (dgamma, dbeta) targets
             gY = torch.empty_like(y)
             dX = torch.empty((m, ci), dtype=torch.float32, device=dev)
@@ -685,12 +738,17 @@ class _MLPSmallGroup(torch.autograd.Function):
                                      ctx.slopes[i], gY.data_ptr(), dX.data_ptr(), outs[0][0].data_ptr(), outs[1][0].data_ptr(), ws.data_ptr(), nbytes)
             per.append((x, W, gY, dX, outs, need_dx, (gA, add, ws)))
         _small_bwd_jobs(jobs, n, per[0][0].device, st)
-        rets = [None]
+        rets = [None, None]
         dxs = [p[3] if p[5] else None for p in per]
         if ctx.shared and dxs[0] is not None and dxs[1] is not None:
             tot = torch.empty_like(dxs[0])
-            _lib.call('crfconv_add_lrelu', ptr(dxs[0]), ptr(dxs[1]), tot.numel(), 1.0, ptr(tot), st)
+            if ctx.mask_slope is not None:             # the shared input is saved[0]: the output of the join whose mask this is
+                _lib.call('crfconv_add_mask', ptr(dxs[0]), ptr(dxs[1]), ptr(saved[0]), tot.numel(), ctx.mask_slope, ptr(tot), st)
+            else:
+                _lib.call('crfconv_add_lrelu', ptr(dxs[0]), ptr(dxs[1]), tot.numel(), 1.0, ptr(tot), st)
             dxs[0], dxs[1] = tot, None
+        elif ctx.mask_slope is not None:
+            raise _lib.CrfConvError('_MLPSmallGroup: a folded join mask without both input gradients')
         for i, (x, W, gY, dX, outs, need_dx, _) in enumerate(per):
             m, ci = x.shape
             co = W.shape[0]
@@ -707,10 +765,11 @@ class _MLPSmallGroup(torch.autograd.Function):
         return tuple(rets)
 
 
-def mlp_group(blocks, shared=False):
+def mlp_group(blocks, shared=False, input_mask=None):
     """[(x [.., Ci], W, bn, slope, fork)] -> per block its output (or (out, x_alias) with fork), all blocks in ONE node -- or None when
     the group form does not apply to every block (training-mode coarse-level blocks: _mlp_small_ok rows, affine float32 BatchNorm with
-    running statistics, widths the two-launch backward takes).  shared: blocks 0 and 1 read the same tensor."""
+    running statistics, widths the two-launch backward takes).  shared: blocks 0 and 1 read the same tensor.  input_mask (shared): the
+    JoinMask of the join that produced that tensor, given by a caller who knows that its every other use goes through block 0's alias."""
     if not (2 <= len(blocks) <= 4):
         return None
     lib = _lib.load()
@@ -731,7 +790,8 @@ def mlp_group(blocks, shared=False):
         xa = None if (shared and i == 1) else x.reshape(-1, x.shape[-1])
         args += [xa, W, bn.weight, bn.bias, bn.running_mean, bn.running_var, mom, bn.eps, float(slope), use_fork]
         shapes.append((x.shape, W.shape[0], fork, use_fork))
-    res = list(_MLPSmallGroup.apply(bool(shared), *args))
+    fold = input_mask if (shared and len(blocks) == 2 and args[9]) else None      # block 0 forks: its alias carries the other uses
+    res = list(_MLPSmallGroup.apply(bool(shared), fold, *args))
     out = []
     for (xs, co, fork, use_fork), (x, _, _, _, _) in zip(shapes, blocks):
         o = res.pop(0).reshape(xs[:-1] + (co,))
@@ -860,10 +920,11 @@ def mlp_block_ok(x, W, bias, bn, training):
 
 
 
-def mlp_block(x, W, bn, slope=1.0, fork=False):
+def mlp_block(x, W, bn, slope=1.0, fork=False, input_mask=None):
     """lrelu(BatchNorm_train(x W^T), slope) on [..., Ci] rows; `bn`: the torch.nn.BatchNorm1d with the parameters.
     fork=True returns (out, x_alias): hand x_alias to the OTHER consumer of x and its gradient is added inside this block's
-    backward (see _MLPBlock)."""
+    backward (see _MLPBlock).  input_mask (with fork): the JoinMask of the join that produced x, given by a caller who knows that every
+    other use of x goes through x_alias -- this block's dX is then the join's total gradient and carries the join's mask."""
     require_gpu(x, W)
     shape = x.shape
     tick(bn)
@@ -871,9 +932,9 @@ def mlp_block(x, W, bn, slope=1.0, fork=False):
     x2 = x.reshape(-1, shape[-1])
     fn = _MLPSmall if _mlp_small_ok(x2.shape[0], shape[-1], W.shape[0]) else _MLPBlock
     if fork and x2.requires_grad and torch.is_grad_enabled() and not state.no_fork:
-        out, alias = fn.apply(x2, W, bn.weight, bn.bias, bn.running_mean, bn.running_var, mom, bn.eps, slope, True)
+        out, alias = fn.apply(x2, W, bn.weight, bn.bias, bn.running_mean, bn.running_var, mom, bn.eps, slope, True, input_mask)
         return out.reshape(shape[:-1] + (W.shape[0],)), alias.reshape(shape)
-    out = fn.apply(x2, W, bn.weight, bn.bias, bn.running_mean, bn.running_var, mom, bn.eps, slope, False)
+    out = fn.apply(x2, W, bn.weight, bn.bias, bn.running_mean, bn.running_var, mom, bn.eps, slope, False, None)
     out = out.reshape(shape[:-1] + (W.shape[0],))
     return (out, x) if fork else out
 

@@ -524,6 +524,14 @@ int crfconv_mlp_dw_jobs_hosting(const crf_mlp_dw_job* jobs, int njobs, const flo
 int crfconv_mlp_backward_add(const float* gA, const float* Y, const float* X, const float* W, const float* coef, float slope,
                              int64_t M, int Ci, int Co, const float* dX_add, float* dX, float* dW, float* dgamma, float* dbeta,
                              void* workspace, size_t workspace_bytes, unsigned* ticket, crf_stream_t stream);
+/* crfconv_mlp_backward_add for a block whose input x is the OUTPUT of a ResNet join out = lrelu(.., mask_slope) and whose dX is the total
+ * gradient of that output: dX = mask(gY W + dX_add; x, mask_slope), mask(v; ref, s) = ref > 0 ? v : s v -- the join's
+ * crfconv_add_lrelu_backward applied while dX is written (same float operations, bit-identical), so the join starts from its g1 and runs
+ * no mask pass.  Ci % 4 == 0, dX not NULL; dX_add == NULL: the plain product followed by that pass in place. */
+int crfconv_mlp_backward_add_mask(const float* gA, const float* Y, const float* X, const float* W, const float* coef, float slope,
+                                  int64_t M, int Ci, int Co, const float* dX_add, float mask_slope, float* dX, float* dW,
+                                  float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, unsigned* ticket,
+                                  crf_stream_t stream);
 /* The block whose input is the column concatenation [Xa | Xb] (the CRF layers' fusion_nn(cat[x, pairwise]),
  * models/continuous_crf_conv_big.py:76) without materialising it: Xa [M, split], Xb [M, Ci - split], split % 4 == 0;
  * the forward product is crfconv_linear_forward_cat, the backward writes dXa / dXb separately. */
@@ -622,6 +630,9 @@ typedef struct { const float* stat_rec; int64_t nrec; const float* x; int64_t M;
 int crfconv_bn_apply_from_records_jobs(const crf_bn_apply_job* jobs, int njobs, crf_stream_t stream);
 typedef struct { const float* gA; const float* Y; const float* coef; const float* W; const float* addend; int64_t M; int Ci; int Co;
                  int training; float slope; float* gY; float* dX; float* dgamma; float* dbeta; void* workspace; size_t workspace_bytes;
+                 /* mask_ref [M, Ci] not NULL: dX = mask(gY W + addend; mask_ref, mask_slope) as crfconv_mlp_backward_add_mask (the block's
+                  * input is a ResNet join's output, mask_ref that output); NULL: no mask */
+                 const float* mask_ref; float mask_slope;
 } crf_mlp_bwd_job;
 int crfconv_mlp_small_backward_jobs(const crf_mlp_bwd_job* jobs, int njobs, unsigned* ticket, crf_stream_t stream);
 /* The same in ONE launch (round 6): tile-sum workgroups first, the product's workgroups wait inside the launch for their job's channel
@@ -741,6 +752,10 @@ int crfconv_bn_apply_add(const float* x, int64_t M, int C, const float* coef, co
                          crf_stream_t stream);
 int crfconv_add_lrelu_backward(const float* gout, const float* out, int64_t n, float slope, float* gin,
                                crf_stream_t stream);
+/* gin = mask(a + b; ref, slope), mask(v; ref, s) = ref > 0 ? v : s v, over n floats (n % 4 == 0): the sum of the two input gradients
+ * of a shared-input group (crfconv_add_lrelu with slope 1) and the crfconv_add_lrelu_backward of the join that produced that input,
+ * in one pass. */
+int crfconv_add_mask(const float* a, const float* b, const float* ref, int64_t n, float slope, float* gin, crf_stream_t stream);
 
 /* ===================================================================== (B) training loss
  * Replaces trainval.py:101-104: F.cross_entropy(y_pred, data.y.reshape(-1) - 1, weight=class_weights,
