@@ -3,7 +3,7 @@
     _base      conversions, per-stream zero words, the grid-barrier workspace and its failure check, run-time switches (`state`)
     defer      deferred parameter work of a backward pass: queues and the batched launches at its end
     crf        continuous CRF mean field (dense / wide), its matrices and their riders, the discrete CRF layer
-    dense      per-point Linear, BatchNorm step counters, BatchNorm (+ LeakyReLU)
+    dense      per-point Linear and the weight gradient of a plain product (now or deferred), BatchNorm step counters, BatchNorm (+ LeakyReLU)
     mlp        Linear -> BatchNorm -> LeakyReLU blocks as single nodes (row-streaming, classifier head, coarse-level forms, groups)
     rows       residual join, LeakyReLU, row gather, neighbour max-pool
     loss       weighted soft-max cross-entropy

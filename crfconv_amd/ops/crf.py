@@ -4,7 +4,7 @@ import ctypes
 import torch
 
 from .. import _lib
-from ..graph import NeighborTable, ptr, require_gpu, stream_ptr
+from ..graph import ptr, require_gpu, stream_ptr
 from ._base import _f32c, _next_supported, _pad_channels, _ptr_array, _ticket, gridsync_ws, state
 
 # ------------------------------------------------------------------------------ CRF mean field
@@ -114,10 +114,7 @@ class _MeanField(torch.autograd.Function):
         lib = _lib.load()
 
         def skinny_tn(A, B, out):      # out = A^T B for [rows, H] operands: the MFMA row-reduction kernel
-            rows = A.shape[0]
-            wbytes = lib.crfconv_linear_wgrad_workspace(rows, H, H)
-            wws = torch.empty(wbytes, dtype=torch.uint8, device=z.device)
-            _lib.call('crfconv_linear_wgrad', ptr(A), ptr(B), rows, H, H, ptr(out), None, ptr(wws), wbytes, st)
+            _wgrad(A, B, out=out)
 
         if lib.crfconv_meanfield_backward_supported(H, table.K, k0) == 1:
             # T + 1 launches (csrc/crf_bwd.hip): T - 1 reverse walks | one edge pass over all steps + softmax backward |
@@ -569,4 +566,4 @@ def discrete_meanfield(p, u, w, C, table, steps):
 
 # names of the sibling modules, imported LAST: every use is inside a function body, so import cycles between the families are harmless
 from .defer import _DEFER, _arm_flush, _defer_ok, _defer_tn, _install_grad, _param_out  # noqa: E402
-from .dense import _gemm, _gemm_tn  # noqa: E402
+from .dense import _gemm, _gemm_tn, _wgrad  # noqa: E402

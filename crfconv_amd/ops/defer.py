@@ -4,7 +4,7 @@ import ctypes
 import torch
 
 from .. import _lib
-from ..graph import NeighborTable, ptr, require_gpu, stream_ptr
+from ..graph import ptr, stream_ptr
 from ._base import state
 
 # ------------------------------------------------------------------------------ deferred weight gradients

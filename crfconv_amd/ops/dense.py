@@ -1,15 +1,13 @@
-"""Per-point Linear, BatchNorm step counters, BatchNorm (+ LeakyReLU)."""
+"""Per-point Linear and the weight gradient of a plain product, BatchNorm step counters, BatchNorm (+ LeakyReLU)."""
 import ctypes
 
 import torch
 
 from .. import _lib
-from ..graph import NeighborTable, ptr, require_gpu, stream_ptr
+from ..graph import ptr, require_gpu, stream_ptr
 from ._base import _f32c, state
 
 # ------------------------------------------------------------------------------ per-point Linear
-
-
 
 
 def _mfma_ok(m, ci, co):
@@ -40,12 +38,29 @@ def _gemm_tn(A, B):
     cb = B.shape[1]
     if m == 0:
         return A.new_zeros((ca, cb))
-    A, B = A.contiguous(), B.contiguous()
-    out = torch.empty((ca, cb), dtype=torch.float32, device=A.device)
-    wbytes = _lib.load().crfconv_linear_wgrad_workspace(m, ca, cb)
-    wws = torch.empty(wbytes, dtype=torch.uint8, device=A.device)
-    _lib.call('crfconv_linear_wgrad', ptr(A), ptr(B), m, ca, cb, ptr(out), None, ptr(wws), wbytes, stream_ptr())
-    return out
+    return _wgrad(A.contiguous(), B.contiguous())[0]
+
+
+def _wgrad(g, x, has_bias=False, out=None):
+    """(dW [Co, Ci] = g^T x, db [Co] = the column sums of g, or None) for contiguous [m, Co] / [m, Ci] rows, launched now
+    (crfconv_linear_wgrad: partials and their reduction).  out: where dW goes, else a new tensor."""
+    m, co = g.shape
+    ci = x.shape[1]
+    dW = torch.empty((co, ci), dtype=torch.float32, device=g.device) if out is None else out
+    db = torch.empty(co, dtype=torch.float32, device=g.device) if has_bias else None
+    nbytes = _lib.load().crfconv_linear_wgrad_workspace(m, co, ci)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=g.device)
+    _lib.call('crfconv_linear_wgrad', ptr(g), ptr(x), m, co, ci, ptr(dW), ptr(db), ptr(ws), nbytes, stream_ptr())
+    return dW, db
+
+
+def _weight_grad(g, x, params, has_bias):
+    """(dW, db) of a plain product y = x W^T (+ b) with params = (W, b): (None, None) where they are left to the batched launches at
+    the end of the backward pass (deferred_weight_grads), else computed now."""
+    if _defer_ok(params):
+        _defer_weight_grad(g, x, params, has_bias)
+        return None, None
+    return _wgrad(g, x, has_bias)
 
 
 def _mfma_matmul(x, W, b, transpose_w, want_stats=False):
@@ -103,15 +118,7 @@ class _Linear(torch.autograd.Function):
             gx = _mfma_matmul(g, W, None, True)[0] if _mfma_ok(m, Co, Ci) else _gemm(g, W)
         dW = db = None
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            if _defer_ok(ctx.params):
-                _defer_weight_grad(g, x, ctx.params, ctx.has_bias)
-                return gx, None, None, None
-            dW = torch.empty((Co, Ci), dtype=torch.float32, device=g.device)
-            db = torch.empty(Co, dtype=torch.float32, device=g.device) if ctx.has_bias else None
-            nbytes = _lib.load().crfconv_linear_wgrad_workspace(m, Co, Ci)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=g.device)
-            _lib.call('crfconv_linear_wgrad', ptr(g), ptr(x), m, Co, Ci, ptr(dW), ptr(db), ptr(ws), nbytes,
-                      stream_ptr())
+            dW, db = _weight_grad(g, x, ctx.params, ctx.has_bias)
         return gx, dW, db, None
 
 

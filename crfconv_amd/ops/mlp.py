@@ -1,10 +1,11 @@
-"""Linear -> BatchNorm -> LeakyReLU blocks as single nodes: row-streaming forms, the classifier head, coarse-level forms and groups."""
+"""Linear -> BatchNorm -> LeakyReLU blocks as single nodes: row-streaming forms (one forward stem, one backward tail), the classifier head,
+coarse-level forms and groups."""
 import ctypes
 
 import torch
 
 from .. import _lib
-from ..graph import NeighborTable, ptr, require_gpu, stream_ptr
+from ..graph import ptr, require_gpu, stream_ptr
 from ._base import _f32c, _mlp_ticket, _ticket, gridsync_ws, state
 
 # ------------------------------------------------------------------------------ Linear -> BatchNorm -> LeakyReLU as one op
@@ -32,10 +33,103 @@ def _take_mask(mask, ok):
     return float(mask.slope)
 
 
+def _bn_args(bn):
+    """(weight, bias, running_mean, running_var, momentum, eps) of a BatchNorm module as the nodes take them."""
+    return bn.weight, bn.bias, bn.running_mean, bn.running_var, 0.1 if bn.momentum is None else bn.momentum, bn.eps
+
+
+def _use_fork(fork, x):
+    """A fork node hands out an alias only where a gradient can come back through it."""
+    return bool(fork and x.requires_grad and torch.is_grad_enabled() and not state.no_fork)
+
+
+def _stream_fwd(x, Wc, gamma, beta, run_mean, run_var, momentum, eps, slope=None, skip=None):
+    """Forward stem of the row-streaming blocks, (y, coef, out): the MFMA Linear with statistic records in its epilogue -- x [m, Ci],
+    or the pair (xa, xb) read through two pointers --, then coefficients and apply (+ skip) + LeakyReLU in one launch.
+    slope None: the coefficients only (out = None) -- the dropout and pool nodes apply in a kernel of their own."""
+    st = stream_ptr()
+    if isinstance(x, tuple):
+        xa, xb = x
+        m, split = xa.shape
+        ci, co = split + xb.shape[1], Wc.shape[0]
+        y = torch.empty((m, co), dtype=torch.float32, device=xa.device)
+        nrec = _lib.load().crfconv_linear_forward_stat_records(m)
+        rec = torch.empty((nrec, 4, co), dtype=torch.float32, device=xa.device)
+        _lib.call('crfconv_linear_forward_cat', ptr(xa), ptr(xb), split, ptr(Wc), None, m, ci, co, ptr(y), ptr(rec), st)
+    else:
+        y, rec = _mfma_matmul(x, Wc, None, False, True)
+    m, co = y.shape
+    coef = torch.empty(4 * co, dtype=torch.float32, device=y.device)
+    g, b = _f32c(gamma), _f32c(beta)
+    if slope is None:
+        _lib.call('crfconv_bn_coef_from_records', ptr(rec), m, co, ptr(g), ptr(b), ptr(run_mean), ptr(run_var), float(momentum),
+                  float(eps), ptr(coef), st)
+        return y, coef, None
+    out = torch.empty_like(y)
+    _lib.call('crfconv_bn_apply_from_records', ptr(rec), rec.shape[0], ptr(y), m, co, ptr(g), ptr(b), ptr(run_mean), ptr(run_var),
+              float(momentum), float(eps), ptr(skip), float(slope), ptr(coef), ptr(out), st)
+    return y, coef, out
+
+
+def _dropout_fwd(x, Wc, gamma, beta, run_mean, run_var, momentum, eps, slope, p, seed, counter):
+    """Front of the dropout nodes, (y, coef, out, used): the stem's coefficients, then ONE pass for BatchNorm + LeakyReLU + dropout.
+    used: the counter value of THIS call's mask, for its backward."""
+    y, coef, _ = _stream_fwd(x, Wc, gamma, beta, run_mean, run_var, momentum, eps)
+    m, co = y.shape
+    out = torch.empty_like(y)
+    used = torch.empty(1, dtype=torch.int64, device=y.device)
+    _lib.call('crfconv_bn_apply_dropout', ptr(y), m, co, ptr(coef), float(slope), float(p), int(seed), ptr(counter), ptr(out),
+              ptr(used), stream_ptr())
+    return y, coef, out, used
+
+
+def _stream_bwd(prm, x, W, y, coef, gA, slope, want_dx, adds=False, g_alias=None, mask_slope=None):
+    """Backward tail of the row-streaming blocks: one pass over (gA, y, x) for dgamma, dbeta, dW, one over (gA, y) for dX.  x: the
+    saved input, or the pair (xa, xb) of the two-pointer form; prm: the (W, gamma, beta) objects the forward was given.  adds: the
+    node is one that can fork (crfconv_mlp_backward_add, whether or not an alias gradient `g_alias` came back); mask_slope: a
+    join's LeakyReLU mask goes into the dX epilogue.  Returns (dX, or dxa, dxb) + what the backward returns for (W, gamma, beta)."""
+    m = y.shape[0]
+    co, ci = W.shape
+    dev = y.device
+    outs, dfr = _mlp_param_outs(prm, W, dev)       # (dW, dgamma, dbeta) targets; dfr: dW finished at the end of the pass
+    dW, dgamma, dbeta = outs[0][0], outs[1][0], outs[2][0]
+    nbytes = _lib.load().crfconv_mlp_backward_workspace(m, ci, co)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    tail = (ptr(None if dfr else dW), ptr(dgamma), ptr(dbeta), ptr(ws), nbytes, _mlp_ticket(dev), stream_ptr())
+    if isinstance(x, tuple):
+        xa, xb = x
+        dxs = (torch.empty_like(xa), torch.empty_like(xb)) if want_dx else (None, None)
+        _lib.call('crfconv_mlp_backward_cat', ptr(gA), ptr(y), ptr(xa), ptr(xb), xa.shape[1], ptr(W), ptr(coef), slope, m, ci, co,
+                  ptr(dxs[0]), ptr(dxs[1]), *tail)
+        return (*dxs, *_mlp_param_rets(prm, outs, dfr, ws, m, ci, co, coef))
+    dX = torch.empty_like(x) if want_dx else None
+    head = (ptr(gA), ptr(y), ptr(x), ptr(W), ptr(coef), slope, m, ci, co)
+    if adds or mask_slope is not None:
+        add = _f32c(g_alias) if (g_alias is not None and want_dx) else None
+        if mask_slope is None:
+            _lib.call('crfconv_mlp_backward_add', *head, ptr(add), ptr(dX), *tail)
+        elif not want_dx:
+            raise _lib.CrfConvError('_MLPBlock: a folded join mask without an input gradient')
+        else:
+            _lib.call('crfconv_mlp_backward_add_mask', *head, ptr(add), mask_slope, ptr(dX), *tail)
+    else:
+        _lib.call('crfconv_mlp_backward', *head, ptr(dX), *tail)
+    return (dX, *_mlp_param_rets(prm, outs, dfr, ws, m, ci, co, coef))
+
+
+def _join_g1(ctx, g, out):
+    """g1 = g lrelu'(out) of a join node: g itself when the node that wrote g has folded the mask into its epilogue (JoinMask)."""
+    if ctx.mask is not None and ctx.mask.folded:
+        return g
+    g1 = torch.empty_like(g)
+    _lib.call('crfconv_add_lrelu_backward', ptr(g), ptr(out), out.numel(), ctx.slope, ptr(g1), stream_ptr())
+    return g1
+
+
 class _MLPBlock(torch.autograd.Function):
     """A = lrelu(BN_train(x W^T), slope) (models/common.py:34-40).  Forward: the MFMA Linear with statistic records in its
-    epilogue, coefficients, one fused apply pass.  Backward: crfconv_mlp_backward -- one pass over (gA, y, x) for dgamma,
-    dbeta, dW, one pass over (gA, y) for dX; the BatchNorm input gradient never reaches memory.
+    epilogue, coefficients and apply as one fused pass (_stream_fwd).  Backward: crfconv_mlp_backward -- one pass over (gA, y, x)
+    for dgamma, dbeta, dW, one pass over (gA, y) for dX; the BatchNorm input gradient never reaches memory (_stream_bwd).
 
     fork: the node also returns its input (as an alias) for the input's OTHER consumer -- the shortcut of a ResNet block --
     so that the gradient coming back through the alias reaches this node's backward, which adds it while writing dX
@@ -45,17 +139,10 @@ class _MLPBlock(torch.autograd.Function):
     def forward(ctx, x_in, W, gamma, beta, run_mean, run_var, momentum, eps, slope, fork=False, mask=None):
         x = x_in.contiguous()
         Wc = W.contiguous()
-        m, ci = x.shape
-        co = Wc.shape[0]
+        ci, co = x.shape[1], Wc.shape[0]
         # x is a join's output and dX its total gradient (JoinMask): the join's LeakyReLU mask goes into the dX epilogue
         ctx.mask_slope = _take_mask(mask, fork and ci % 4 == 0 and co % 4 == 0)
-        y, rec = _mfma_matmul(x, Wc, None, False, True)
-        coef = torch.empty(4 * co, dtype=torch.float32, device=x.device)
-        g, b = _f32c(gamma), _f32c(beta)
-        out = torch.empty_like(y)
-        # coefficients and apply in one launch (same values)
-        _lib.call('crfconv_bn_apply_from_records', ptr(rec), rec.shape[0], ptr(y), m, co, ptr(g), ptr(b), ptr(run_mean), ptr(run_var),
-                  float(momentum), float(eps), None, float(slope), ptr(coef), ptr(out), stream_ptr())
+        y, coef, out = _stream_fwd(x, Wc, gamma, beta, run_mean, run_var, momentum, eps, slope)
         ctx.prm = (W, gamma, beta)
         ctx.save_for_backward(x, Wc, y, coef)
         ctx.slope = float(slope)
@@ -67,34 +154,15 @@ class _MLPBlock(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gA, g_alias=None):
         x, W, y, coef = ctx.saved_tensors
-        m, ci = x.shape
-        co = W.shape[0]
-        dev = x.device
         gA = torch.zeros_like(y) if gA is None else gA.contiguous()
-        dX = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        add = _f32c(g_alias) if (g_alias is not None and dX is not None) else None
-        outs, dfr = _mlp_param_outs(ctx.prm, W, dev)       # (dW, dgamma, dbeta) targets; dfr: dW finished at the end of the pass
-        dW, dgamma, dbeta = (o[0] for o in outs)
-        nbytes = _lib.load().crfconv_mlp_backward_workspace(m, ci, co)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        if ctx.mask_slope is not None:
-            if dX is None:
-                raise _lib.CrfConvError('_MLPBlock: a folded join mask without an input gradient')
-            _lib.call('crfconv_mlp_backward_add_mask', ptr(gA), ptr(y), ptr(x), ptr(W), ptr(coef), ctx.slope, m, ci, co, ptr(add),
-                      ctx.mask_slope, ptr(dX), ptr(None if dfr else dW), ptr(dgamma), ptr(dbeta), ptr(ws), nbytes, _mlp_ticket(dev),
-                      stream_ptr())
-        else:
-            _lib.call('crfconv_mlp_backward_add', ptr(gA), ptr(y), ptr(x), ptr(W), ptr(coef), ctx.slope, m, ci, co, ptr(add), ptr(dX),
-                      ptr(None if dfr else dW), ptr(dgamma), ptr(dbeta), ptr(ws), nbytes, _mlp_ticket(dev), stream_ptr())
-        return dX, *_mlp_param_rets(ctx.prm, outs, dfr, ws, m, ci, co, coef), None, None, None, None, None, None, None
-
-
+        return (*_stream_bwd(ctx.prm, x, W, y, coef, gA, ctx.slope, ctx.needs_input_grad[0], True, g_alias, ctx.mask_slope),
+                None, None, None, None, None, None, None)
 
 
 class _MLPBlockJoin(torch.autograd.Function):
     """out = lrelu(BN_train(x W^T) + skip, slope): the tail of a ResNet block (models/point_conv_big.py:84-88: lin_out has no
     activation, then F.leaky_relu(x + shortcut)) as one node -- forward: MFMA Linear with statistic records, coefficients, ONE
-    pass for BatchNorm + residual add + LeakyReLU (crfconv_bn_apply_add; the normalised tensor never reaches memory);
+    pass for BatchNorm + residual add + LeakyReLU (the normalised tensor never reaches memory);
     backward: g1 = g lrelu'(out) is both the skip gradient and the gA of crfconv_mlp_backward (BatchNorm without activation).
     mask (JoinMask): when the node that writes g has folded the mask into its epilogue, g IS g1 and the mask pass does not run."""
 
@@ -102,14 +170,7 @@ class _MLPBlockJoin(torch.autograd.Function):
     def forward(ctx, x, W, gamma, beta, run_mean, run_var, momentum, eps, skip, slope, mask=None):
         x, Wc, skip = x.contiguous(), W.contiguous(), skip.contiguous()
         ctx.mask = mask
-        m, ci = x.shape
-        co = Wc.shape[0]
-        y, rec = _mfma_matmul(x, Wc, None, False, True)
-        coef = torch.empty(4 * co, dtype=torch.float32, device=x.device)
-        st = stream_ptr()
-        out = torch.empty_like(y)
-        _lib.call('crfconv_bn_apply_from_records', ptr(rec), rec.shape[0], ptr(y), m, co, ptr(_f32c(gamma)), ptr(_f32c(beta)),
-                  ptr(run_mean), ptr(run_var), float(momentum), float(eps), ptr(skip), float(slope), ptr(coef), ptr(out), st)
+        y, coef, out = _stream_fwd(x, Wc, gamma, beta, run_mean, run_var, momentum, eps, slope, skip)
         ctx.prm = (W, gamma, beta)
         ctx.save_for_backward(x, Wc, y, coef, out)
         ctx.slope = float(slope)
@@ -118,74 +179,34 @@ class _MLPBlockJoin(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, W, y, coef, out = ctx.saved_tensors
-        m, ci = x.shape
-        co = W.shape[0]
-        dev = x.device
-        g = g.contiguous()
-        st = stream_ptr()
-        if ctx.mask is not None and ctx.mask.folded:
-            g1 = g
-        else:
-            g1 = torch.empty_like(g)
-            _lib.call('crfconv_add_lrelu_backward', ptr(g), ptr(out), out.numel(), ctx.slope, ptr(g1), st)
-        dX = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        outs, dfr = _mlp_param_outs(ctx.prm, W, dev)       # (dW, dgamma, dbeta) targets; dfr: dW finished at the end of the pass
-        dW, dgamma, dbeta = (o[0] for o in outs)
-        nbytes = _lib.load().crfconv_mlp_backward_workspace(m, ci, co)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        _lib.call('crfconv_mlp_backward', ptr(g1), ptr(y), ptr(x), ptr(W), ptr(coef), 1.0, m, ci, co, ptr(dX), ptr(None if dfr else dW),
-                  ptr(dgamma), ptr(dbeta), ptr(ws), nbytes, _mlp_ticket(dev), st)
+        g1 = _join_g1(ctx, g.contiguous(), out)
         gskip = g1 if ctx.needs_input_grad[8] else None
-        return dX, *_mlp_param_rets(ctx.prm, outs, dfr, ws, m, ci, co, coef), None, None, None, None, gskip, None, None
-
-
+        return (*_stream_bwd(ctx.prm, x, W, y, coef, g1, 1.0, ctx.needs_input_grad[0]), None, None, None, None, gskip, None, None)
 
 
 class _MLPBlockDropout(torch.autograd.Function):
     """dropout(lrelu(BN_train(x W^T), slope), p): the classifier's MLP -> nn.Dropout (models/point_conv_big.py:131-134) as one
     node.  Forward: MFMA Linear with statistic records, coefficients, ONE pass for BatchNorm + LeakyReLU + dropout
-    (crfconv_bn_apply_dropout); the mask is a hash of (seed, the BatchNorm's step counter, element index), so nothing is
+    (_dropout_fwd); the mask is a hash of (seed, the BatchNorm's step counter, element index), so nothing is
     stored, forward and backward of a step agree, and a replayed hipGraph draws a new mask every step (the counter is a
     device word that the forward advances).  Backward: the same mask on the incoming gradient, then crfconv_mlp_backward."""
 
     @staticmethod
     def forward(ctx, x, W, gamma, beta, run_mean, run_var, momentum, eps, slope, p, seed, counter):
         x, Wc = x.contiguous(), W.contiguous()
-        m, ci = x.shape
-        co = Wc.shape[0]
-        y, rec = _mfma_matmul(x, Wc, None, False, True)
-        coef = torch.empty(4 * co, dtype=torch.float32, device=x.device)
-        st = stream_ptr()
-        _lib.call('crfconv_bn_coef_from_records', ptr(rec), m, co, ptr(_f32c(gamma)), ptr(_f32c(beta)), ptr(run_mean),
-                  ptr(run_var), float(momentum), float(eps), ptr(coef), st)
-        out = torch.empty_like(y)
-        used = torch.empty(1, dtype=torch.int64, device=x.device)     # the counter value of THIS call's mask, for its backward
-        _lib.call('crfconv_bn_apply_dropout', ptr(y), m, co, ptr(coef), float(slope), float(p), int(seed), ptr(counter), ptr(out),
-                  ptr(used), st)
-        counter = used
+        y, coef, out, used = _dropout_fwd(x, Wc, gamma, beta, run_mean, run_var, momentum, eps, slope, p, seed, counter)
         ctx.prm = (W, gamma, beta)
-        ctx.save_for_backward(x, Wc, y, coef, counter)
+        ctx.save_for_backward(x, Wc, y, coef, used)
         ctx.slope, ctx.p, ctx.seed = float(slope), float(p), int(seed)
         return out
 
     @staticmethod
     def backward(ctx, g):
         x, W, y, coef, counter = ctx.saved_tensors
-        m, ci = x.shape
-        co = W.shape[0]
-        dev = x.device
         g = g.contiguous()
         gA = torch.empty_like(g)
-        st = stream_ptr()
-        _lib.call('crfconv_dropout_backward', ptr(g), g.numel(), ctx.p, ctx.seed, ptr(counter), ptr(gA), st)
-        dX = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        outs, dfr = _mlp_param_outs(ctx.prm, W, dev)       # (dW, dgamma, dbeta) targets; dfr: dW finished at the end of the pass
-        dW, dgamma, dbeta = (o[0] for o in outs)
-        nbytes = _lib.load().crfconv_mlp_backward_workspace(m, ci, co)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        _lib.call('crfconv_mlp_backward', ptr(gA), ptr(y), ptr(x), ptr(W), ptr(coef), ctx.slope, m, ci, co, ptr(dX), ptr(None if dfr else dW),
-                  ptr(dgamma), ptr(dbeta), ptr(ws), nbytes, _mlp_ticket(dev), st)
-        return dX, *_mlp_param_rets(ctx.prm, outs, dfr, ws, m, ci, co, coef), None, None, None, None, None, None, None, None
+        _lib.call('crfconv_dropout_backward', ptr(g), g.numel(), ctx.p, ctx.seed, ptr(counter), ptr(gA), stream_ptr())
+        return (*_stream_bwd(ctx.prm, x, W, y, coef, gA, ctx.slope, ctx.needs_input_grad[0]), None, None, None, None, None, None, None, None)
 
 
 class _MLPDropoutLinear(torch.autograd.Function):
@@ -197,21 +218,10 @@ class _MLPDropoutLinear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, W, gamma, beta, run_mean, run_var, momentum, eps, slope, p, seed, counter, W2, b2):
         x, Wc, W2c = x.contiguous(), W.contiguous(), W2.contiguous()
-        m, ci = x.shape
-        co = Wc.shape[0]
-        y, rec = _mfma_matmul(x, Wc, None, False, True)
-        coef = torch.empty(4 * co, dtype=torch.float32, device=x.device)
-        st = stream_ptr()
-        _lib.call('crfconv_bn_coef_from_records', ptr(rec), m, co, ptr(_f32c(gamma)), ptr(_f32c(beta)), ptr(run_mean),
-                  ptr(run_var), float(momentum), float(eps), ptr(coef), st)
-        h = torch.empty_like(y)
-        used = torch.empty(1, dtype=torch.int64, device=x.device)     # the counter value of THIS call's mask, for its backward
-        _lib.call('crfconv_bn_apply_dropout', ptr(y), m, co, ptr(coef), float(slope), float(p), int(seed), ptr(counter), ptr(h),
-                  ptr(used), st)
-        counter = used
+        y, coef, h, used = _dropout_fwd(x, Wc, gamma, beta, run_mean, run_var, momentum, eps, slope, p, seed, counter)
         logits = _mfma_matmul(h, W2c, None if b2 is None else b2.contiguous(), False)[0]
         ctx.prm = (W, gamma, beta)
-        ctx.save_for_backward(x, Wc, y, coef, counter, h, W2c)
+        ctx.save_for_backward(x, Wc, y, coef, used, h, W2c)
         ctx.slope, ctx.p, ctx.seed = float(slope), float(p), int(seed)
         ctx.params2 = (W2, b2)
         return logits
@@ -219,33 +229,14 @@ class _MLPDropoutLinear(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, W, y, coef, counter, h, W2 = ctx.saved_tensors
-        m, ci = x.shape
+        m = x.shape[0]
         co, c2 = W.shape[0], W2.shape[0]
-        dev = x.device
         g = g.contiguous()
-        st = stream_ptr()
-        gA = torch.empty((m, co), dtype=torch.float32, device=dev)       # = dropout'(g W2): masked by the kernel that forms it
-        _lib.call('crfconv_linear_forward_dropout', ptr(g), ptr(W2), m, c2, co, 1, ctx.p, ctx.seed, ptr(counter), ptr(gA), st)
-        W2p, b2p = ctx.params2
-        dW2 = db2 = None
-        if _defer_ok(ctx.params2):
-            _defer_weight_grad(g, h, ctx.params2, b2p is not None)
-        else:
-            dW2 = torch.empty((c2, co), dtype=torch.float32, device=dev)
-            db2 = torch.empty(c2, dtype=torch.float32, device=dev) if b2p is not None else None
-            nb = _lib.load().crfconv_linear_wgrad_workspace(m, c2, co)
-            wsw = torch.empty(nb, dtype=torch.uint8, device=dev)
-            _lib.call('crfconv_linear_wgrad', ptr(g), ptr(h), m, c2, co, ptr(dW2), ptr(db2), ptr(wsw), nb, st)
-        dX = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        outs, dfr = _mlp_param_outs(ctx.prm, W, dev)       # (dW, dgamma, dbeta) targets; dfr: dW finished at the end of the pass
-        dW, dgamma, dbeta = (o[0] for o in outs)
-        nbytes = _lib.load().crfconv_mlp_backward_workspace(m, ci, co)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        _lib.call('crfconv_mlp_backward', ptr(gA), ptr(y), ptr(x), ptr(W), ptr(coef), ctx.slope, m, ci, co, ptr(dX), ptr(None if dfr else dW),
-                  ptr(dgamma), ptr(dbeta), ptr(ws), nbytes, _mlp_ticket(dev), st)
-        return dX, *_mlp_param_rets(ctx.prm, outs, dfr, ws, m, ci, co, coef), None, None, None, None, None, None, None, None, dW2, db2
-
-
+        gA = torch.empty((m, co), dtype=torch.float32, device=x.device)       # = dropout'(g W2): masked by the kernel that forms it
+        _lib.call('crfconv_linear_forward_dropout', ptr(g), ptr(W2), m, c2, co, 1, ctx.p, ctx.seed, ptr(counter), ptr(gA), stream_ptr())
+        dW2, db2 = _weight_grad(g, h, ctx.params2, ctx.params2[1] is not None)
+        return (*_stream_bwd(ctx.prm, x, W, y, coef, gA, ctx.slope, ctx.needs_input_grad[0]), None, None, None, None, None, None, None, None,
+                dW2, db2)
 
 
 class _HeadRecompute(torch.autograd.Function):
@@ -346,7 +337,6 @@ def mlp_dropout_linear(x, W, bn, slope, p, W2, b2, recompute=None):
         return None
     require_gpu(x, W, W2)
     tick(bn)
-    mom = 0.1 if bn.momentum is None else bn.momentum
     seed = dropout_seed(ci, co)                          # as mlp_block_dropout
     node = _MLPDropoutLinear
     head_ok = bool(_lib.load().crfconv_head_supported(m, ci, co, c2))
@@ -354,8 +344,7 @@ def mlp_dropout_linear(x, W, bn, slope, p, W2, b2, recompute=None):
         return None
     if head_ok and (recompute or recompute is None):
         node = _HeadRecompute                            # no [m, 4 C] tensor at all
-    out = node.apply(x.reshape(-1, ci), W, bn.weight, bn.bias, bn.running_mean, bn.running_var, mom, bn.eps, slope,
-                                  p, seed, bn.num_batches_tracked, W2, b2)
+    out = node.apply(x.reshape(-1, ci), W, *_bn_args(bn), slope, p, seed, bn.num_batches_tracked, W2, b2)
     return out.reshape(x.shape[:-1] + (c2,))
 
 
@@ -377,10 +366,8 @@ def mlp_block_dropout(x, W, bn, slope, p):
             return None
     require_gpu(x, W)
     tick(bn)                                              # advances the counter the mask is keyed on (unless the model already did)
-    mom = 0.1 if bn.momentum is None else bn.momentum
     seed = dropout_seed(ci, co)                          # stable per layer shape
-    out = _MLPBlockDropout.apply(x.reshape(-1, ci), W, bn.weight, bn.bias, bn.running_mean, bn.running_var, mom, bn.eps, slope,
-                                 p, seed, bn.num_batches_tracked)
+    out = _MLPBlockDropout.apply(x.reshape(-1, ci), W, *_bn_args(bn), slope, p, seed, bn.num_batches_tracked)
     return out.reshape(x.shape[:-1] + (co,))
 
 
@@ -394,18 +381,12 @@ class _MLPBlockPool(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x_in, W, gamma, beta, run_mean, run_var, momentum, eps, table, fork=False):
         x, Wc = x_in.contiguous(), W.contiguous()
-        m, ci = x.shape
         co = Wc.shape[0]
-        dev = x.device
-        y, rec = _mfma_matmul(x, Wc, None, False, True)
-        coef = torch.empty(4 * co, dtype=torch.float32, device=dev)
-        st = stream_ptr()
-        _lib.call('crfconv_bn_coef_from_records', ptr(rec), m, co, ptr(_f32c(gamma)), ptr(_f32c(beta)), ptr(run_mean),
-                  ptr(run_var), float(momentum), float(eps), ptr(coef), st)
-        out = torch.empty((table.m_tgt, co), dtype=torch.float32, device=dev)
-        arg = torch.empty((table.m_tgt, co), dtype=torch.int32, device=dev)
+        y, coef, _ = _stream_fwd(x, Wc, gamma, beta, run_mean, run_var, momentum, eps)
+        out = torch.empty((table.m_tgt, co), dtype=torch.float32, device=x.device)
+        arg = torch.empty((table.m_tgt, co), dtype=torch.int32, device=x.device)
         _lib.call('crfconv_neighbor_maxpool_affine_forward', ptr(y), ptr(coef), ptr(table.idx32), table.K, table.m_tgt, co,
-                  ptr(out), ptr(arg), st)
+                  ptr(out), ptr(arg), stream_ptr())
         ctx.table = table
         ctx.prm = (W, gamma, beta)
         ctx.save_for_backward(x, Wc, y, coef, arg)
@@ -418,23 +399,13 @@ class _MLPBlockPool(torch.autograd.Function):
     def backward(ctx, g, g_alias=None):
         x, W, y, coef, arg = ctx.saved_tensors
         table = ctx.table
-        m, ci = x.shape
-        co = W.shape[0]
+        m, co = y.shape
         dev = x.device
         g = torch.zeros((table.m_tgt, co), dtype=torch.float32, device=dev) if g is None else _f32c(g)
-        st = stream_ptr()
         rev_ptr, rev_eid = table.reverse
         gA = torch.empty((m, co), dtype=torch.float32, device=dev)
-        _lib.call('crfconv_neighbor_maxpool_backward', ptr(g), ptr(arg), ptr(rev_ptr), ptr(rev_eid), table.K, m, co, ptr(gA), st)
-        dX = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        add = _f32c(g_alias) if (g_alias is not None and dX is not None) else None
-        outs, dfr = _mlp_param_outs(ctx.prm, W, dev)       # (dW, dgamma, dbeta) targets; dfr: dW finished at the end of the pass
-        dW, dgamma, dbeta = (o[0] for o in outs)
-        nbytes = _lib.load().crfconv_mlp_backward_workspace(m, ci, co)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        _lib.call('crfconv_mlp_backward_add', ptr(gA), ptr(y), ptr(x), ptr(W), ptr(coef), 1.0, m, ci, co, ptr(add), ptr(dX),
-                  ptr(None if dfr else dW), ptr(dgamma), ptr(dbeta), ptr(ws), nbytes, _mlp_ticket(dev), st)
-        return dX, *_mlp_param_rets(ctx.prm, outs, dfr, ws, m, ci, co, coef), None, None, None, None, None, None
+        _lib.call('crfconv_neighbor_maxpool_backward', ptr(g), ptr(arg), ptr(rev_ptr), ptr(rev_eid), table.K, m, co, ptr(gA), stream_ptr())
+        return (*_stream_bwd(ctx.prm, x, W, y, coef, gA, 1.0, ctx.needs_input_grad[0], True, g_alias), None, None, None, None, None, None)
 
 
 def mlp_block_pool(x, W, bn, table, fork=False):
@@ -448,14 +419,10 @@ def mlp_block_pool(x, W, bn, table, fork=False):
         return None
     require_gpu(x, W)
     tick(bn)
-    mom = 0.1 if bn.momentum is None else bn.momentum
-    if fork and x.requires_grad and torch.is_grad_enabled() and not state.no_fork:
-        return _MLPBlockPool.apply(x, W, bn.weight, bn.bias, bn.running_mean, bn.running_var, mom, bn.eps, table, True)
-    out = _MLPBlockPool.apply(x, W, bn.weight, bn.bias, bn.running_mean, bn.running_var, mom, bn.eps, table, False)
+    if _use_fork(fork, x):
+        return _MLPBlockPool.apply(x, W, *_bn_args(bn), table, True)
+    out = _MLPBlockPool.apply(x, W, *_bn_args(bn), table, False)
     return (out, x) if fork else out
-
-
-
 
 def _small_bwd_jobs(jobs, n, dev, st):
     """The BatchNorm(+LeakyReLU) backward + dX product of up to four coarse-level blocks: ONE launch whose product workgroups wait for
@@ -465,6 +432,19 @@ def _small_bwd_jobs(jobs, n, dev, st):
         _lib.call('crfconv_mlp_small_backward_jobs_one_launch', ctypes.cast(jobs, ctypes.c_void_p), n, ptr(_ticket(dev)), ptr(gridsync_ws(dev)), st)
     else:
         _lib.call('crfconv_mlp_small_backward_jobs', ctypes.cast(jobs, ctypes.c_void_p), n, ptr(_ticket(dev)), st)
+
+
+def _mlp_bwd_jobs(blocks):
+    """The crf_mlp_bwd_job array of coarse-level blocks, each (gA, y, coef, W, add, slope, gY, dX, dgamma, dbeta, ws, mask); mask:
+    None or (ref [M, Ci], slope) -- without a reference the kernels do not read the mask slope (csrc/gemm.hip)."""
+    jobs = (_lib.MlpBwdJob * len(blocks))()
+    for i, (gA, y, coef, W, add, slope, gY, dX, dgamma, dbeta, ws, mask) in enumerate(blocks):
+        m, co = y.shape
+        mref, mslope = (None, 1.0) if mask is None else (mask[0].data_ptr(), float(mask[1]))
+        jobs[i] = _lib.MlpBwdJob(gA.data_ptr(), y.data_ptr(), coef.data_ptr(), W.data_ptr(), None if add is None else add.data_ptr(), m,
+                                 W.shape[1], co, 1, float(slope), gY.data_ptr(), dX.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
+                                 ws.data_ptr(), ws.numel(), mref, mslope)
+    return jobs
 
 
 def _small_bwd(gA, y, coef, W, addend, slope, dgamma, dbeta, need_dx, mask=None):
@@ -482,10 +462,7 @@ def _small_bwd(gA, y, coef, W, addend, slope, dgamma, dbeta, need_dx, mask=None)
         nbytes = lib.crfconv_mlp_small_backward_workspace(m, co)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         add = None if addend is None else addend.contiguous()
-        jobs = (_lib.MlpBwdJob * 1)()
-        jobs[0] = _lib.MlpBwdJob(gA.data_ptr(), y.data_ptr(), coef.data_ptr(), W.data_ptr(), None if add is None else add.data_ptr(), m, ci, co, 1,
-                                 float(slope), gY.data_ptr(), dX.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), nbytes,
-                                 None if mask is None else mask[0].data_ptr(), 1.0 if mask is None else float(mask[1]))
+        jobs = _mlp_bwd_jobs([(gA, y, coef, W, add, slope, gY, dX, dgamma, dbeta, ws, mask)])
         _small_bwd_jobs(jobs, 1, dev, stream_ptr())
         return gY, dX
     if mask is not None:
@@ -531,6 +508,15 @@ def _small_fwd(x, Wc, gamma, beta, run_mean, run_var, momentum, eps, slope, skip
     return y, out, coef
 
 
+def _small_tail(ctx, x, W, y, coef, gA, addend, slope, mask=None):
+    """What the backward of a coarse-level node returns for (x, W, gamma, beta): _small_bwd with the (dgamma, dbeta) targets, then
+    dW = gY^T x -- queued or launched (_weight_grad: same partials + reduction in both forms)."""
+    outs = [_param_out(q, (W.shape[0],), x.device) for q in ctx.prm[1:]]      # (dgamma, dbeta) targets
+    gY, dX = _small_bwd(gA, y, coef, W, addend, slope, outs[0][0], outs[1][0], ctx.needs_input_grad[0], mask)
+    dW = _weight_grad(gY, x, ctx.params, False)[0]
+    return (dX, dW, *(_param_ret(q, o, k) for q, (o, k) in zip(ctx.prm[1:], outs)))
+
+
 class _MLPSmallJoin(torch.autograd.Function):
     """_MLPBlockJoin at the coarse levels: the one-launch Linear + BatchNorm kernel (csrc/mlp_small.hip) also adds the skip and
     applies the join's LeakyReLU to the tile it holds in registers (crfconv_mlp_small_forward_join).  mask: as _MLPBlockJoin."""
@@ -549,28 +535,9 @@ class _MLPSmallJoin(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, W, y, coef, out = ctx.saved_tensors
-        m, ci = x.shape
-        co = W.shape[0]
-        dev = x.device
-        g = g.contiguous()
-        st = stream_ptr()
-        if ctx.mask is not None and ctx.mask.folded:
-            g1 = g
-        else:
-            g1 = torch.empty_like(g)
-            _lib.call('crfconv_add_lrelu_backward', ptr(g), ptr(out), out.numel(), ctx.slope, ptr(g1), st)
-        outs = [_param_out(q, (co,), dev) for q in ctx.prm[1:]]      # (dgamma, dbeta) targets
-        dgamma, dbeta = outs[0][0], outs[1][0]
-        gY, dX = _small_bwd(g1, y, coef, W, None, 1.0, dgamma, dbeta, ctx.needs_input_grad[0])
+        g1 = _join_g1(ctx, g.contiguous(), out)
         gskip = g1 if ctx.needs_input_grad[8] else None
-        if _defer_ok(ctx.params):
-            _defer_weight_grad(gY, x, ctx.params, False)
-            return dX, None, *(_param_ret(q, o, k) for q, (o, k) in zip(ctx.prm[1:], outs)), None, None, None, None, gskip, None, None
-        dW = torch.empty((co, ci), dtype=torch.float32, device=dev)
-        nb = _lib.load().crfconv_linear_wgrad_workspace(m, co, ci)
-        wsw = torch.empty(nb, dtype=torch.uint8, device=dev)
-        _lib.call('crfconv_linear_wgrad', ptr(gY), ptr(x), m, co, ci, ptr(dW), None, ptr(wsw), nb, st)
-        return dX, dW, *(_param_ret(q, o, k) for q, (o, k) in zip(ctx.prm[1:], outs)), None, None, None, None, gskip, None, None
+        return (*_small_tail(ctx, x, W, y, coef, g1, None, 1.0), None, None, None, None, gskip, None, None)
 
 
 def mlp_block_join(x, W, bn, skip, slope, mask=None):
@@ -585,14 +552,12 @@ def mlp_block_join(x, W, bn, skip, slope, mask=None):
         return None
     require_gpu(x, W, skip)
     tick(bn)
-    mom = 0.1 if bn.momentum is None else bn.momentum
     fn = _MLPSmallJoin if _mlp_small_ok(m, ci, co) else _MLPBlockJoin      # coarse levels: folded into the one-launch kernel
     if mask is not None and not state.no_mask_fold and torch.is_grad_enabled():
         mask.slope = float(slope)
     else:
         mask = None
-    out = fn.apply(x.reshape(-1, ci), W, bn.weight, bn.bias, bn.running_mean, bn.running_var, mom, bn.eps,
-                   skip.reshape(-1, co), slope, mask)
+    out = fn.apply(x.reshape(-1, ci), W, *_bn_args(bn), skip.reshape(-1, co), slope, mask)
     return out.reshape(x.shape[:-1] + (co,))
 
 
@@ -631,24 +596,9 @@ class _MLPSmall(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gA, g_alias=None):
         x, W, y, coef = ctx.saved_tensors
-        m, ci = x.shape
-        co = W.shape[0]
-        dev = x.device
         gA = torch.zeros_like(y) if gA is None else gA.contiguous()
-        outs = [_param_out(q, (co,), dev) for q in ctx.prm[1:]]      # (dgamma, dbeta) targets
-        dgamma, dbeta = outs[0][0], outs[1][0]
-        gY, dX = _small_bwd(gA, y, coef, W, None if g_alias is None else g_alias.reshape(m, ci), ctx.slope, dgamma, dbeta,
-                            ctx.needs_input_grad[0], None if ctx.mask_slope is None else (x, ctx.mask_slope))
-        if _defer_ok(ctx.params):
-            _defer_weight_grad(gY, x, ctx.params, False)
-            return dX, None, *(_param_ret(q, o, k) for q, (o, k) in zip(ctx.prm[1:], outs)), None, None, None, None, None, None, None
-        dW = torch.empty((co, ci), dtype=torch.float32, device=dev)          # same partials + reduction as the deferred form
-        nb = _lib.load().crfconv_linear_wgrad_workspace(m, co, ci)
-        wsw = torch.empty(nb, dtype=torch.uint8, device=dev)
-        _lib.call('crfconv_linear_wgrad', ptr(gY), ptr(x), m, co, ci, ptr(dW), None, ptr(wsw), nb, stream_ptr())
-        return dX, dW, *(_param_ret(q, o, k) for q, (o, k) in zip(ctx.prm[1:], outs)), None, None, None, None, None, None, None
-
-
+        return (*_small_tail(ctx, x, W, y, coef, gA, None if g_alias is None else g_alias.reshape(x.shape), ctx.slope,
+                             None if ctx.mask_slope is None else (x, ctx.mask_slope)), None, None, None, None, None, None, None)
 
 
 class _MLPSmallGroup(torch.autograd.Function):
@@ -713,7 +663,6 @@ class _MLPSmallGroup(torch.autograd.Function):
         saved = ctx.saved_tensors
         lib = _lib.load()
         st = stream_ptr()
-        jobs = (_lib.MlpBwdJob * n)()
         per, gi = [], 0
         for i in range(n):
             x, W, y, coef = saved[4 * i:4 * i + 4]
@@ -734,10 +683,8 @@ class _MLPSmallGroup(torch.autograd.Function):
             nbytes = lib.crfconv_mlp_small_backward_workspace(m, co)
             ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             add = None if g_alias is None else _f32c(g_alias).reshape(m, ci)
-            jobs[i] = _lib.MlpBwdJob(gA.data_ptr(), y.data_ptr(), coef.data_ptr(), W.data_ptr(), None if add is None else add.data_ptr(), m, ci, co, 1,
-                                     ctx.slopes[i], gY.data_ptr(), dX.data_ptr(), outs[0][0].data_ptr(), outs[1][0].data_ptr(), ws.data_ptr(), nbytes)
-            per.append((x, W, gY, dX, outs, need_dx, (gA, add, ws)))
-        _small_bwd_jobs(jobs, n, per[0][0].device, st)
+            per.append((x, W, gY, dX, outs, need_dx, (gA, y, coef, W, add, ctx.slopes[i], gY, dX, outs[0][0], outs[1][0], ws, None)))
+        _small_bwd_jobs(_mlp_bwd_jobs([p[6] for p in per]), n, per[0][0].device, st)     # (per keeps gA, add and ws alive until here)
         rets = [None, None]
         dxs = [p[3] if p[5] else None for p in per]
         if ctx.shared and dxs[0] is not None and dxs[1] is not None:
@@ -750,17 +697,8 @@ class _MLPSmallGroup(torch.autograd.Function):
         elif ctx.mask_slope is not None:
             raise _lib.CrfConvError('_MLPSmallGroup: a folded join mask without both input gradients')
         for i, (x, W, gY, dX, outs, need_dx, _) in enumerate(per):
-            m, ci = x.shape
-            co = W.shape[0]
             Wp, gp, bp = ctx.prm[i]
-            if _defer_ok((Wp, None)):
-                _defer_weight_grad(gY, x, (Wp, None), False)
-                dW = None
-            else:
-                dW = torch.empty((co, ci), dtype=torch.float32, device=x.device)
-                nb = lib.crfconv_linear_wgrad_workspace(m, co, ci)
-                wsw = torch.empty(nb, dtype=torch.uint8, device=x.device)
-                _lib.call('crfconv_linear_wgrad', ptr(gY), ptr(x), m, co, ci, ptr(dW), None, ptr(wsw), nb, st)
+            dW = _weight_grad(gY, x, (Wp, None), False)[0]
             rets += [dxs[i], dW, _param_ret(gp, outs[0][0], outs[0][1]), _param_ret(bp, outs[1][0], outs[1][1]), None, None, None, None, None, None]
         return tuple(rets)
 
@@ -785,10 +723,9 @@ def mlp_group(blocks, shared=False, input_mask=None):
         return None                                    # (tests: the un-forked graph runs the blocks one by one)
     for i, (x, W, bn, slope, fork) in enumerate(blocks):
         tick(bn)
-        mom = 0.1 if bn.momentum is None else bn.momentum
-        use_fork = bool(fork and x.requires_grad and torch.is_grad_enabled() and not state.no_fork)
+        use_fork = _use_fork(fork, x)
         xa = None if (shared and i == 1) else x.reshape(-1, x.shape[-1])
-        args += [xa, W, bn.weight, bn.bias, bn.running_mean, bn.running_var, mom, bn.eps, float(slope), use_fork]
+        args += [xa, W, *_bn_args(bn), float(slope), use_fork]
         shapes.append((x.shape, W.shape[0], fork, use_fork))
     fold = input_mask if (shared and len(blocks) == 2 and args[9]) else None      # block 0 forks: its alias carries the other uses
     res = list(_MLPSmallGroup.apply(bool(shared), fold, *args))
@@ -811,17 +748,7 @@ class _MLPBlockCat(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xa, xb, W, gamma, beta, run_mean, run_var, momentum, eps, slope):
         xa, xb, Wc = xa.contiguous(), xb.contiguous(), W.contiguous()
-        m, split = xa.shape
-        ci, co = split + xb.shape[1], Wc.shape[0]
-        y = torch.empty((m, co), dtype=torch.float32, device=xa.device)
-        nrec = _lib.load().crfconv_linear_forward_stat_records(m)
-        rec = torch.empty((nrec, 4, co), dtype=torch.float32, device=xa.device)
-        st = stream_ptr()
-        _lib.call('crfconv_linear_forward_cat', ptr(xa), ptr(xb), split, ptr(Wc), None, m, ci, co, ptr(y), ptr(rec), st)
-        coef = torch.empty(4 * co, dtype=torch.float32, device=xa.device)
-        out = torch.empty_like(y)
-        _lib.call('crfconv_bn_apply_from_records', ptr(rec), nrec, ptr(y), m, co, ptr(_f32c(gamma)), ptr(_f32c(beta)), ptr(run_mean),
-                  ptr(run_var), float(momentum), float(eps), None, float(slope), ptr(coef), ptr(out), st)
+        y, coef, out = _stream_fwd((xa, xb), Wc, gamma, beta, run_mean, run_var, momentum, eps, slope)
         ctx.prm = (W, gamma, beta)
         ctx.save_for_backward(xa, xb, Wc, y, coef)
         ctx.slope = float(slope)
@@ -830,22 +757,9 @@ class _MLPBlockCat(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gA):
         xa, xb, W, y, coef = ctx.saved_tensors
-        m, split = xa.shape
-        ci, co = split + xb.shape[1], W.shape[0]
-        gA = gA.contiguous()
-        dev = xa.device
-        want_dx = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
-        dxa = torch.empty_like(xa) if want_dx else None
-        dxb = torch.empty_like(xb) if want_dx else None
-        outs, dfr = _mlp_param_outs(ctx.prm, W, dev)       # (dW, dgamma, dbeta) targets; dfr: dW finished at the end of the pass
-        dW, dgamma, dbeta = (o[0] for o in outs)
-        nbytes = _lib.load().crfconv_mlp_backward_workspace(m, ci, co)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        _lib.call('crfconv_mlp_backward_cat', ptr(gA), ptr(y), ptr(xa), ptr(xb), split, ptr(W), ptr(coef), ctx.slope, m, ci, co,
-                  ptr(dxa), ptr(dxb), ptr(None if dfr else dW), ptr(dgamma), ptr(dbeta), ptr(ws), nbytes, _mlp_ticket(dev), stream_ptr())
-        return (dxa if ctx.needs_input_grad[0] else None, dxb if ctx.needs_input_grad[1] else None,
-                *_mlp_param_rets(ctx.prm, outs, dfr, ws, m, ci, co, coef),
-                None, None, None, None, None)
+        want_a, want_b = ctx.needs_input_grad[:2]
+        dxa, dxb, *rets = _stream_bwd(ctx.prm, (xa, xb), W, y, coef, gA.contiguous(), ctx.slope, want_a or want_b)
+        return (dxa if want_a else None, dxb if want_b else None, *rets, None, None, None, None, None)
 
 
 class _Cat2(torch.autograd.Function):
@@ -898,9 +812,7 @@ def mlp_block_cat(xa, xb, W, bn, training, slope=1.0):
         return None
     require_gpu(xa, xb, W)
     tick(bn)
-    mom = 0.1 if bn.momentum is None else bn.momentum
-    out = _MLPBlockCat.apply(xa.reshape(-1, ca), xb.reshape(-1, cb), W, bn.weight, bn.bias, bn.running_mean, bn.running_var, mom,
-                             bn.eps, slope)
+    out = _MLPBlockCat.apply(xa.reshape(-1, ca), xb.reshape(-1, cb), W, *_bn_args(bn), slope)
     return out.reshape(xa.shape[:-1] + (W.shape[0],))
 
 
@@ -918,8 +830,6 @@ def mlp_block_ok(x, W, bias, bn, training):
             and _lib.load().crfconv_mlp_backward_supported(m, ci, co) == 1)
 
 
-
-
 def mlp_block(x, W, bn, slope=1.0, fork=False, input_mask=None):
     """lrelu(BatchNorm_train(x W^T), slope) on [..., Ci] rows; `bn`: the torch.nn.BatchNorm1d with the parameters.
     fork=True returns (out, x_alias): hand x_alias to the OTHER consumer of x and its gradient is added inside this block's
@@ -928,13 +838,12 @@ def mlp_block(x, W, bn, slope=1.0, fork=False, input_mask=None):
     require_gpu(x, W)
     shape = x.shape
     tick(bn)
-    mom = 0.1 if bn.momentum is None else bn.momentum
     x2 = x.reshape(-1, shape[-1])
     fn = _MLPSmall if _mlp_small_ok(x2.shape[0], shape[-1], W.shape[0]) else _MLPBlock
-    if fork and x2.requires_grad and torch.is_grad_enabled() and not state.no_fork:
-        out, alias = fn.apply(x2, W, bn.weight, bn.bias, bn.running_mean, bn.running_var, mom, bn.eps, slope, True, input_mask)
+    if _use_fork(fork, x2):
+        out, alias = fn.apply(x2, W, *_bn_args(bn), slope, True, input_mask)
         return out.reshape(shape[:-1] + (W.shape[0],)), alias.reshape(shape)
-    out = fn.apply(x2, W, bn.weight, bn.bias, bn.running_mean, bn.running_var, mom, bn.eps, slope, False, None)
+    out = fn.apply(x2, W, *_bn_args(bn), slope, False, None)
     out = out.reshape(shape[:-1] + (W.shape[0],))
     return (out, x) if fork else out
 
@@ -979,5 +888,5 @@ def run_lin_bn(seq, x):
 
 # names of the sibling modules, imported LAST: every use is inside a function body, so import cycles between the families are harmless
 from .rows import _LRelu  # noqa: E402
-from .defer import _defer_ok, _defer_weight_grad, _mlp_param_outs, _mlp_param_rets, _param_out, _param_ret  # noqa: E402
-from .dense import _gemm, _mfma_matmul, _mfma_ok, bn_act, linear, tick  # noqa: E402
+from .defer import _mlp_param_outs, _mlp_param_rets, _param_out, _param_ret  # noqa: E402
+from .dense import _gemm, _mfma_matmul, _mfma_ok, _weight_grad, bn_act, linear, tick  # noqa: E402

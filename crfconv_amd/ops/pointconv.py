@@ -4,7 +4,7 @@ import ctypes
 import torch
 
 from .. import _lib
-from ..graph import NeighborTable, ptr, require_gpu, stream_ptr
+from ..graph import ptr, require_gpu, stream_ptr
 from ._base import _f32c, _pc_ticket, _ptr_array
 
 # ------------------------------------------------------------------------------ PointConv
@@ -191,14 +191,8 @@ class _PointConv(torch.autograd.Function):
             _lib.call('crfconv_pointconv_bwd_dump', ptr(x), ptr(g), ptr(pos_src), ptr(pos_tgt), ptr(table.idx32), K,
                       m_tgt, d, ptr(A1), ptr(b1), ptr(W2), slope, ptr(coef[0]), ptr(coef[1]), ptr(coef[2]), ptr(h1),
                       ptr(gh2), ptr(rel), st)
-            if _defer_ok((pW2, None)):                                     # g_h2^T h1: partials now, the reduction with all others
-                _defer_weight_grad(gh2, h1, (pW2, None), False)
-                dW2 = None
-            else:
-                dW2 = torch.empty((d, d), dtype=torch.float32, device=dev)   # ... on the MFMA row-reduction kernel
-                wbytes = _lib.load().crfconv_linear_wgrad_workspace(E, d, d)
-                wws = torch.empty(wbytes, dtype=torch.uint8, device=dev)
-                _lib.call('crfconv_linear_wgrad', ptr(gh2), ptr(h1), E, d, d, ptr(dW2), None, ptr(wws), wbytes, st)
+            # g_h2^T h1 on the MFMA row-reduction kernel: now, or its partials now and the reduction with all others
+            dW2 = _weight_grad(gh2, h1, (pW2, None), False)[0]
             gw = _gemm(gh2, W2)                                            # g_h1 before the LeakyReLU mask
             dA1b1 = torch.empty((d, 4), dtype=torch.float64, device=dev)
             abytes = _lib.load().crfconv_pointconv_bwd_a1_workspace(E, d)
@@ -307,6 +301,6 @@ def point_conv(x, pos_src, pos_tgt, table, W1, bn1, W2, bn2, training, momentum=
 
 
 # names of the sibling modules, imported LAST: every use is inside a function body, so import cycles between the families are harmless
-from .defer import _DEFER, _arm_flush, _defer_fold1_bwd, _defer_ok, _defer_reduce64, _defer_weight_grad, _param_out  # noqa: E402
-from .dense import _gemm, tick  # noqa: E402
+from .defer import _DEFER, _arm_flush, _defer_fold1_bwd, _defer_ok, _defer_reduce64, _param_out  # noqa: E402
+from .dense import _gemm, _weight_grad, tick  # noqa: E402
 from .crf import _take_riders  # noqa: E402
