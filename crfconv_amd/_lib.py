@@ -173,6 +173,9 @@ SIGNATURES = {
     'crfconv_sgd_step_guarded': (_i, [_vp, _vp, _vp, _i64, _vp, _i, _i, _vp, _vp]),
     'crfconv_sgd_step_guarded_all': (_i, [_vp, _vp, _vp, _i64, _vp, _i, _i, _vp, _i, _vp, _vp]),
     'crfconv_sgd_guard_publish': (_i, [_vp, _i, _vp, _vp]),
+    'crfconv_adam_workspace': (_sz, [_i64]),
+    'crfconv_adam_coef_floats': (_sz, []),
+    'crfconv_adam_step': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _i, _vp, _vp]),
     'crfconv_spd_inverse': (_i, [_vp, _i, _vp, _vp]),
     'crfconv_spd_inverse_wide': (_i, [_vp, _i, _vp, _vp]),
     'crfconv_neighbor_maxpool_forward': (_i, [_vp, _vp, _i, _i64, _i, _vp, _vp, _vp]),

@@ -5,7 +5,7 @@
         loss = step(new_batch)                                 # batch.load_(new_batch) + replay; `loss` is a device scalar
 
 `optimizer` is any torch.optim optimizer whose step() is capturable as is (torch.optim.SGD with float hyper-parameters: a
-learning-rate change needs a new CapturedStep) or optim.FlatSGD (then pass after_backward=bucket.pack).  `loss_fn(logits,
+learning-rate change needs a new CapturedStep) or optim.FlatSGD / optim.FlatAdam (then pass after_backward=bucket.pack).  `loss_fn(logits,
 batch)` is the caller's, e.g. ``lambda o, d: F.cross_entropy(o, d.y.reshape(-1) - 1, weight=w, ignore_index=-1)``.
 Drop (or detach) losses of earlier EAGER steps of the same model before constructing it: a live loss keeps that step's
 autograd nodes -- the parameters' AccumulateGrad nodes, bound to the stream they were created on -- alive, and the capture
@@ -108,12 +108,15 @@ class CapturedStep:
         # the warm-up steps (allocator, lazily built tables, momentum buffers) must not train: model state is put back afterwards,
         # momentum restarts from zero (mu * 0 + g = g: torch's first step, for dampening = 0)
         import copy
-        supported = isinstance(optimizer, torch.optim.SGD) or type(optimizer).__name__ == 'FlatSGD'
+        from .optim import FlatAdam
+        flat_adam = isinstance(optimizer, FlatAdam)          # its whole state (moments, device step count) is in its state_dict
+        supported = isinstance(optimizer, torch.optim.SGD) or type(optimizer).__name__ == 'FlatSGD' or flat_adam
         if supported and any(float(g.get('dampening', 0.0)) != 0.0 for g in optimizer.param_groups):
             supported = False                                   # (a zeroed momentum buffer gives (1 - d) g, not torch's first step g)
         if not supported and warmup > 0:
-            raise TypeError('CapturedStep: the warm-up steps are undone for SGD-type optimizers without dampening only (torch.optim.SGD, '
-                            'optim.FlatSGD); got %s -- pass warmup=0 and warm the caches up yourself' % type(optimizer).__name__)
+            raise TypeError('CapturedStep: the warm-up steps are undone for SGD-type optimizers without dampening (torch.optim.SGD, '
+                            'optim.FlatSGD) and for optim.FlatAdam / FlatAdamW only; got %s -- pass warmup=0 and warm the caches up '
+                            'yourself' % type(optimizer).__name__)
         keep = [t.detach().clone() for t in list(model.parameters()) + list(model.buffers())]
         opt_state = copy.deepcopy(optimizer.state_dict())       # step counters, schedulers' view of the groups, any other state
         flat_steps = getattr(optimizer, 'steps', None)
@@ -138,6 +141,8 @@ class CapturedStep:
                         optimizer.buf.zero_()
                 if flat_steps is not None:
                     optimizer.steps = flat_steps                  # FlatSGD's own counter (its check_every cadence)
+                if flat_adam:
+                    optimizer.load_state_dict(opt_state)          # moments, amsgrad maximum, device step count t, host counter
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()

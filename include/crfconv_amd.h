@@ -802,6 +802,28 @@ int crfconv_sgd_step_guarded_all(float* param, const float* grad, float* momentu
 /* *slot = 1.0f when any of the words is set, else 0.0f (one tiny launch; capture-safe). */
 int crfconv_sgd_guard_publish(const unsigned* const* fail_words, int n_fail_words, float* slot, crf_stream_t stream);
 
+/* torch.optim.Adam / AdamW step (single-tensor arithmetic, operation for operation) over one flat float32 parameter vector of n
+ * elements, everything that changes between steps read from DEVICE memory so that a captured graph of the step keeps counting:
+ *   g = grad * grad_scale * clip_coef;  decoupled ? p *= 1 - lr * wd : g += wd * p;
+ *   m += (g - m) * (1 - beta1);  v = beta2 * v + (1 - beta2) * g * g;  vmax = max(vmax, v) (max_exp_avg_sq != NULL: amsgrad);
+ *   p -= lr / (1 - beta1^t) * m / (sqrt(v or vmax) / sqrt(1 - beta2^t) + eps)
+ * hyper: 7 doubles {lr, beta1, beta2, eps, weight_decay, grad_scale, max_grad_norm}; t: the int64 step counter, advanced by the call
+ * (bias corrections in float64, once per step); coef: crfconv_adam_coef_floats() floats of scratch the call's launches hand each
+ * other.  clip != 0: global-norm clipping -- *grad_norm (float) receives the norm of grad_scale * grad, a float64 sum folded in a
+ * fixed order (bit-reproducible), clip_coef = min(1, max_grad_norm / (norm + 1e-6)) as torch.nn.utils.clip_grad_norm_ forms it (a
+ * non-finite norm propagates as there); `grad` itself is NOT rewritten.  workspace: crfconv_adam_workspace(n) bytes, 8-byte aligned,
+ * needed for clip != 0 only.  clip == 0: clip_coef = 1, grad_norm / workspace may be NULL.
+ * Guard (fail_words / n_fail_words / reduced_flag as for crfconv_sgd_step_guarded_all): while any word is set the call changes
+ * neither param, exp_avg, exp_avg_sq, max_exp_avg_sq nor t.
+ * Operand vectors that are all 16-byte aligned are read and written as float4 (scalar tail for n % 4); otherwise -- a view at an odd
+ * element offset -- the same arithmetic runs element by element.  2 launches, 3 with clip. */
+size_t crfconv_adam_workspace(int64_t n);
+size_t crfconv_adam_coef_floats(void);
+int crfconv_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq, int64_t n,
+                      const double* hyper, long long* t, float* coef, float* grad_norm, int decoupled, int clip, void* workspace,
+                      size_t workspace_bytes, const unsigned* const* fail_words, int n_fail_words, const float* reduced_flag,
+                      crf_stream_t stream);
+
 /* ---- device-side pieces of the collate (datasets/semantic3d_dataset.py:512-528), csrc/collate.hip
  * crfconv_random_subsets: for each level l < nlevels, out[l][0 .. s[l]) (device int64) = a uniformly random subset of
  *   {0 .. n[l]-1} of size s[l] in ASCENDING order -- `torch.randperm(n)[: n // ratio]` of :517 followed by the sort the
