@@ -97,6 +97,12 @@ SIGNATURES = {
     'crfconv_mlp_backward_workspace': (_sz, [_i64, _i, _i]),
     'crfconv_mlp_backward': (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     'crfconv_linear_forward_cat': (_i, [_vp, _vp, _i, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp]),
+    'crfconv_linear_forward_uv_supported': (_i, [_i, _i]),
+    'crfconv_linear_forward_uv': (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp]),
+    'crfconv_mlp_small_forward_uv_supported': (_i, [_i]),
+    'crfconv_mlp_small_forward_join_uv': (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _f, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    'crfconv_gemm_stats_uv_supported': (_i, [_i64, _i, _i]),
+    'crfconv_gemm_stats_uv': (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp]),
     'crfconv_mlp_dw_jobs': (_i, [_vp, _i, _vp]),
     'crfconv_mlp_dw_jobs_hosting': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     'crfconv_mlp_backward_add': (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
@@ -283,6 +289,14 @@ class MlpBwdJob(ctypes.Structure):
                 ('gY', ctypes.c_void_p), ('dX', ctypes.c_void_p), ('dgamma', ctypes.c_void_p), ('dbeta', ctypes.c_void_p),
                 ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_size_t),
                 ('mask_ref', ctypes.c_void_p), ('mask_slope', ctypes.c_float)]
+
+
+class UvFold(ctypes.Structure):
+    """crf_uv_fold of include/crfconv_amd.h."""
+    _fields_ = [('U', ctypes.c_void_p), ('V', ctypes.c_void_p), ('stats', ctypes.c_void_p), ('shift', ctypes.c_void_p),
+                ('gamma2', ctypes.c_void_p), ('beta2', ctypes.c_void_p), ('n_edges', ctypes.c_double), ('run_mean', ctypes.c_void_p),
+                ('run_var', ctypes.c_void_p), ('momentum', ctypes.c_float), ('eps', ctypes.c_float), ('a2', ctypes.c_void_p),
+                ('b2', ctypes.c_void_p), ('aux2', ctypes.c_void_p), ('out', ctypes.c_void_p)]
 
 
 class Reduce64Job(ctypes.Structure):

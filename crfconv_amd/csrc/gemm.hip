@@ -23,6 +23,7 @@
 // one launch).  bn_bwd_tile_sums_kernel, the PRO form's first launch, lives here too.
 #include "common.hpp"
 #include "gridsync.hpp"
+#include "uv_fold.hpp"
 
 #include <cstdlib>
 
@@ -94,14 +95,20 @@ constexpr int gemm_lds_floats() {
 // STATS form (crfconv_gemm_stats): the epilogue also leaves BatchNorm statistic records of the tile it holds -- one
 // {shift, rows, sum (v - shift), sum (v - shift)^2} tuple per 16-row group and output channel, the layout
 // crfconv_bn_coef_from_records combines (Chan, float64) -- so the statistics pass over Y never runs.
-template <int WM, int WN, int WR, int WC, bool BNK, bool VEC, bool PRO, bool STATS>
+// UV form (crfconv_gemm_stats_uv; K <= GM_UV_MAXK): the A operand is the PointConv combine helper(U, V) of uv_fold.hpp, formed when a
+// chunk is parked (A = U, uv->V = V; coefficients in uvc [2][GM_UV_MAXK], LDS of the caller's) -- lin_out of the ResNet block at the level
+// the tiled product serves; the workgroups of column tile 0 store it to uv->out, workgroup (0, 0) publishes as uv_combine_kernel's does.
+constexpr int GM_UV_MAXK = 128;
+template <int WM, int WN, int WR, int WC, bool BNK, bool VEC, bool PRO, bool STATS, bool UV = false>
 __device__ __forceinline__ void gemm_tile(const float* __restrict__ A, const float* __restrict__ B,
                                           const float* __restrict__ bias, const float* __restrict__ addend,
                                           int M, int N, int K, float* __restrict__ C, const GemmPro& pro,
                                           float* __restrict__ stat_rec, const unsigned bx, const unsigned by,
                                           float* __restrict__ lds /*gemm_lds_floats<...>() floats, 16-byte aligned: the kernel's ONE buffer*/,
-                                          const unsigned gridx = 0 /*PRO with pro.sync: row tiles of the job*/) {
+                                          const unsigned gridx = 0 /*PRO with pro.sync: row tiles of the job*/,
+                                          const UvFold* __restrict__ uv = nullptr, float* __restrict__ uvc = nullptr) {
     static_assert(WR * WC * WAVE == GM_BLOCK, "four wavefronts");
+    static_assert(!UV || (VEC && !PRO), "the combine prologue: aligned widths, not the dX product");
     static_assert(!PRO || (VEC && !BNK), "the prologue form is the dX product of aligned widths");
     constexpr int BM = 16 * WM * WR, BN = 16 * WN * WC;
     constexpr int LDA = GM_BK + 4;                      // [BM][LDA]: 16-byte fragment reads along k, 8 lanes cover the 32 banks
@@ -120,19 +127,22 @@ __device__ __forceinline__ void gemm_tile(const float* __restrict__ A, const flo
     const int m0 = bx * BM, n0 = by * BN;
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
 
-    struct Regs { float4 a[PA], b[PB], y[PRO ? PA : 1]; int kc; };
+    struct Regs { float4 a[PA], b[PB], y[(PRO || UV) ? PA : 1]; int kc; };
     auto fetch = [&](int kc, Regs& r) {
         r.kc = kc;
 #pragma unroll
         for (int i = 0; i < PA; ++i) {
             const int q = threadIdx.x + GM_BLOCK * i;
             r.a[i] = zero4;
-            if constexpr (PRO) r.y[i] = zero4;
+            if constexpr (PRO || UV) r.y[i] = zero4;
             if (NA4 % GM_BLOCK != 0 && q >= NA4) continue;
             const int row = m0 + q / (GM_BK / 4), k = kc + 4 * (q % (GM_BK / 4));
             if (row < M) r.a[i] = gm_ld4<VEC>(A + (int64_t)row * K + k, K - k);
             if constexpr (PRO) {
                 if (row < M) r.y[i] = gm_ld4<VEC>(pro.Y + (int64_t)row * K + k, K - k);
+            }
+            if constexpr (UV) {
+                if (row < M) r.y[i] = gm_ld4<VEC>(uv->V + (int64_t)row * K + k, K - k);
             }
         }
 #pragma unroll
@@ -172,6 +182,13 @@ __device__ __forceinline__ void gemm_tile(const float* __restrict__ A, const flo
                     av.z = ca.z * (g1.z - c2.z - (yv.z - mu.z) * rs.z * c3.z);
                     av.w = ca.w * (g1.w - c2.w - (yv.w - mu.w) * rs.w * c3.w);
                     if (by == 0) *reinterpret_cast<float4*>(pro.gY + (int64_t)row * K + k) = av;
+                }
+            }
+            if constexpr (UV) {
+                const int row = m0 + q / (GM_BK / 4), k = r.kc + 4 * (q % (GM_BK / 4));
+                if (row < M && k < K) {                  // (rows / channels past the end stay zero)
+                    av = uv_out4(*reinterpret_cast<const float4*>(uvc + k), *reinterpret_cast<const float4*>(uvc + GM_UV_MAXK + k), av, r.y[i]);
+                    if (by == 0) *reinterpret_cast<float4*>(uv->out + (int64_t)row * K + k) = av;
                 }
             }
             *reinterpret_cast<float4*>(sA[buf] + (q / (GM_BK / 4)) * LDA + 4 * (q % (GM_BK / 4))) = av;
@@ -272,6 +289,16 @@ __device__ __forceinline__ void gemm_tile(const float* __restrict__ A, const flo
                 sPro[4 * GM_PRO_MAXK + k] = ok ? c2 : __builtin_nanf("");            // a spin that gave up poisons this workgroup's tiles
                 sPro[5 * GM_PRO_MAXK + k] = c3;
             }
+        }
+        __syncthreads();
+    }
+    if constexpr (UV) {                                  // behind the first operand loads' issue: one channel per thread
+        if ((int)threadIdx.x < K) {
+            const int c = threadIdx.x;
+            const UvCoef k = uv_coef(c, K, uv->stats, uv->shift, uv->gamma, uv->beta, uv->n_edges, uv->eps);
+            uvc[c] = k.a;
+            uvc[GM_UV_MAXK + c] = uv_vcoef(k);
+            if (bx == 0 && by == 0) uv_publish(c, K, k, uv->n_edges, uv->run_mean, uv->run_var, uv->momentum, uv->a2, uv->b2, uv->aux2);
         }
         __syncthreads();
     }
@@ -437,6 +464,19 @@ __global__ __launch_bounds__(GM_BLOCK) void gemm_stats_jobs_kernel(const GemmSta
     else
         gemm_tile<1, 1, 2, 2, true, true, false, true>(uni(t.A[j]), uni(t.B[j]), nullptr, nullptr, uni(t.M[j]), uni(t.N[j]), uni(t.K[j]), uni(t.C[j]), GemmPro(),
                                                        uni(t.rec[j]), bx, by, lds);
+}
+// crfconv_gemm_stats (one job, the same tiles) with the UV operand
+__global__ __launch_bounds__(GM_BLOCK) void gemm_stats_uv_kernel(const float* __restrict__ U, const float* __restrict__ B, const int M, const int N,
+                                                                 const int K, float* __restrict__ C, float* __restrict__ rec, const int tiles_x,
+                                                                 const int wide, const UvFold uv) {
+    const unsigned tx = (unsigned)tiles_x;
+    const unsigned bx = (unsigned)uni((int)(blockIdx.x % tx)), by = (unsigned)uni((int)(blockIdx.x / tx));
+    __shared__ __attribute__((aligned(16))) float lds[gemm_lds_floats<1, 2, 2, 2, true, false>()];
+    __shared__ __attribute__((aligned(16))) float s_uv[2 * GM_UV_MAXK];
+    if (wide)
+        gemm_tile<1, 2, 2, 2, true, true, false, true, true>(U, B, nullptr, nullptr, M, N, K, C, GemmPro(), rec, bx, by, lds, 0, &uv, s_uv);
+    else
+        gemm_tile<1, 1, 2, 2, true, true, false, true, true>(U, B, nullptr, nullptr, M, N, K, C, GemmPro(), rec, bx, by, lds, 0, &uv, s_uv);
 }
 struct GemmProJobs {
     const float* A[GG_MAX]; const float* B[GG_MAX]; const float* addend[GG_MAX]; float* C[GG_MAX];
@@ -789,6 +829,26 @@ extern "C" int crfconv_gemm_stats_jobs(const crf_gemm_stats_job* jobs, int njobs
     }
     t.njobs = njobs;
     hipLaunchKernelGGL(crf::gemm_stats_jobs_kernel, dim3((unsigned)tiles), dim3(crf::GM_BLOCK), 0, crf::as_stream(stream), t);
+    CRF_LAUNCH_CHECK();
+    return CRF_OK;
+}
+
+// crfconv_pointconv_combine(f) + crfconv_gemm_stats(f->out, B) in one launch: the A operand out = a2 U + (a2 shift + b2) V is formed while
+// its chunks are staged and stored to f->out by the first column tiles (K <= 128 input channels).
+extern "C" int crfconv_gemm_stats_uv_supported(int64_t M, int N, int K) {
+    return (M >= 1 && M < ((int64_t)1 << 31) && N >= 4 && K >= 4 && N % 4 == 0 && K % 4 == 0 && K <= crf::GM_UV_MAXK) ? 1 : 0;
+}
+extern "C" int crfconv_gemm_stats_uv(const crf_uv_fold* f, const float* B, int64_t M, int N, int K, float* C, float* stat_rec, void* stream) {
+    CRF_REQUIRE(B && C && stat_rec, CRF_ERR_ARG, "null pointer");
+    CRF_REQUIRE(crf::uv_fold_complete(f), CRF_ERR_ARG, "combine record: null pointer, or running statistics not as a pair");
+    CRF_REQUIRE(crfconv_gemm_stats_uv_supported(M, N, K), CRF_ERR_UNSUPPORTED, "gemm_stats_uv %lld x %d x %d: N, K multiples of 4, K <= %d",
+                (long long)M, N, K, crf::GM_UV_MAXK);
+    const crf::UvFold uv = crf::uv_fold_args(f);
+    const int tiles_x = (int)((M + 31) / 32), wide = crf::gm_wide(M, N) ? 1 : 0;
+    const int64_t tiles = (int64_t)tiles_x * ((N + (wide ? 63 : 31)) / (wide ? 64 : 32));
+    CRF_REQUIRE(tiles < ((int64_t)1 << 31), CRF_ERR_UNSUPPORTED, "too many tiles");
+    hipLaunchKernelGGL(crf::gemm_stats_uv_kernel, dim3((unsigned)tiles), dim3(crf::GM_BLOCK), 0, crf::as_stream(stream), f->U, B, (int)M, N, K, C,
+                       stat_rec, tiles_x, wide, uv);
     CRF_LAUNCH_CHECK();
     return CRF_OK;
 }

@@ -16,6 +16,7 @@
 #include "wgrad_body.hpp"
 #include "crf_matrices_body.hpp"
 #include "reduce64_body.hpp"
+#include "uv_fold.hpp"
 
 #include <cstdlib>
 
@@ -887,7 +888,11 @@ constexpr int LF_BLOCK = LF_BLOCK_, LF_WAVES = LF_BLOCK / WAVE;
 // register budget (as run-time branches the two epilogues cost <2, false> and <4, true> one wavefront per SIMD each).
 // 3 (PRO, VEC4) Y = mask(Y + addend; mask_ref, mask_slope), mask(v; ref, s) = ref > 0 ? v : s v -- lrelu_bwd_kernel's (pool.hip): the
 // dX of a block whose input is the output of a ResNet join is handed to that join with the join's LeakyReLU mask already applied.
-constexpr int EPI_NONE = 0, EPI_ADD = 1, EPI_DROPOUT = 2, EPI_ADD_MASK = 3;
+// 4 (not PRO, VEC4, Ci <= 16; a PROLOGUE despite the parameter's name, which is the one free slot of the kernel's template list): the operand is the
+// PointConv combine helper(U, V) of uv_fold.hpp, formed when the fragment is loaded (X = U, uv.V = V) and stored to uv.out by the same lane
+// -- each row group is streamed by ONE workgroup per column group, the first column group stores; workgroup (0, 0) publishes a2 / b2 / aux2
+// and advances BatchNorm-2's running statistics as uv_combine_kernel's workgroup 0 does.  lin_out of a fine-level ResNet block.
+constexpr int EPI_NONE = 0, EPI_ADD = 1, EPI_DROPOUT = 2, EPI_ADD_MASK = 3, EPI_UV = 4;
 // NCH > 0 (round 4; Ci <= 16 NCH, VEC4): the operand fragments of ALL k chunks of a row group are requested at once and those of
 // the wavefront's NEXT row group before the current group's products (NCH <= LF_PF_MAX) -- the rolled loop (NCH = 0) pays one
 // dependent memory round trip per chunk, eight per group at 128 inputs, with two to four wavefronts per SIMD to hide them.
@@ -907,8 +912,11 @@ __global__ __launch_bounds__(LF_BLOCK) void linear_fwd_kernel(const float* __res
                                                               const long long* __restrict__ drop_counter = nullptr,
                                                               unsigned long long drop_seed = 0ull, unsigned drop_threshold = 0u,
                                                               float drop_scale = 1.f,
-                                                              const float* __restrict__ mask_ref = nullptr, float mask_slope = 1.f) {
+                                                              const float* __restrict__ mask_ref = nullptr, float mask_slope = 1.f,
+                                                              const UvFold uv = UvFold()) {
     static_assert(EPI != EPI_ADD_MASK || (PRO && VEC4), "the masked epilogue is the aligned dX product's");
+    static_assert(EPI != EPI_UV || (!PRO && VEC4 && NCH == 1), "the combine prologue is the narrow aligned forward's");
+    constexpr bool UV = EPI == EPI_UV, TWO = PRO || UV;              // TWO: two raw fragments per chunk
     // mask_ref [M, Co] (EPI_ADD_MASK): the saved output of the join in front of this block (this block's own input x)
     // drop_counter (not PRO, one-pointer output): Y = dropout_mask .* (X W^T) * drop_scale with the counter-based mask of
     // common.hpp (element e = row * Co + column) -- the backward of nn.Dropout applied while the gradient of the Linear
@@ -978,6 +986,9 @@ __global__ __launch_bounds__(LF_BLOCK) void linear_fwd_kernel(const float* __res
         if constexpr (PRO) {
             xa = *reinterpret_cast<const float4*>(X + r * Ci + k0);
             xb2 = *reinterpret_cast<const float4*>(Y2 + r * Ci + k0);
+        } else if constexpr (UV) {
+            xa = *reinterpret_cast<const float4*>(X + r * Ci + k0);
+            xb2 = *reinterpret_cast<const float4*>(uv.V + r * Ci + k0);
         } else if (Xb != nullptr) {
             if (k0 < xsplit) xa = *reinterpret_cast<const float4*>(X + r * xsplit + k0);
             else xa = *reinterpret_cast<const float4*>(Xb + r * (Ci - xsplit) + (k0 - xsplit));
@@ -1010,14 +1021,40 @@ __global__ __launch_bounds__(LF_BLOCK) void linear_fwd_kernel(const float* __res
             return gv;
         }
     };
+    // EPI_UV: this lane's four channels 4 g .. 4 g + 3 are the same in every row group (one chunk): coefficients in registers
+    [[maybe_unused]] float4 uva = zero4, uvt = zero4;
+    if constexpr (UV) {
+        if (blockIdx.x == 0 && blockIdx.y == 0 && (int)threadIdx.x < Ci) {
+            const UvCoef k = uv_coef(threadIdx.x, Ci, uv.stats, uv.shift, uv.gamma, uv.beta, uv.n_edges, uv.eps);
+            uv_publish(threadIdx.x, Ci, k, uv.n_edges, uv.run_mean, uv.run_var, uv.momentum, uv.a2, uv.b2, uv.aux2);
+        }
+        if (4 * g < Ci) {
+            float a[4], tv[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const UvCoef k = uv_coef(4 * g + e, Ci, uv.stats, uv.shift, uv.gamma, uv.beta, uv.n_edges, uv.eps);
+                a[e] = k.a;
+                tv[e] = uv_vcoef(k);
+            }
+            uva = make_float4(a[0], a[1], a[2], a[3]);
+            uvt = make_float4(tv[0], tv[1], tv[2], tv[3]);
+        }
+    }
+    // the MFMA operand out = helper(U, V) of row r, stored on the way by the first column group (rows / channels past the end stay zero)
+    [[maybe_unused]] auto uv_operand = [&](int64_t r, bool rv, float4 u, float4 v) -> float4 {
+        if (!rv || 4 * g >= Ci) return zero4;
+        const float4 o = uv_out4(uva, uvt, u, v);
+        if (blockIdx.y == 0) *reinterpret_cast<float4*>(uv.out + r * Ci + 4 * g) = o;
+        return o;
+    };
     // (Issuing the operand loads of four row groups in one burst, or prefetching the next group, measured no faster: the
     // write-heavy shapes run at the ~2.7 TB/s HBM WRITE rate -- 163840 x 8 -> 32 moves 21 MB out in 13 us -- not at a
     // per-wavefront latency limit.)
     constexpr int NCA = NCH > 0 ? NCH : 1;
     constexpr bool PF = NCH > 0 && NCH <= LF_PF_MAX_;                 // next group's fragments in flight too
     const int64_t row_stride = (int64_t)gridDim.x * (LF_BLOCK / WAVE) * 16;
-    [[maybe_unused]] float4 fa[NCA], fb[PRO ? NCA : 1], na[PF ? NCA : 1], nb[(PF && PRO) ? NCA : 1];
-    [[maybe_unused]] auto load_group = [&](int64_t rw0, float4 (&xa)[NCA], float4 (&xb)[PRO ? NCA : 1]) {
+    [[maybe_unused]] float4 fa[NCA], fb[TWO ? NCA : 1], na[PF ? NCA : 1], nb[(PF && TWO) ? NCA : 1];
+    [[maybe_unused]] auto load_group = [&](int64_t rw0, float4 (&xa)[NCA], float4 (&xb)[TWO ? NCA : 1]) {
         const int64_t rq = rw0 + rr;
         const bool ok = rw0 < M && rq < M;
 #pragma unroll
@@ -1025,7 +1062,7 @@ __global__ __launch_bounds__(LF_BLOCK) void linear_fwd_kernel(const float* __res
             float4 t0, t1;
             load_raw(rq, ok, c, t0, t1);
             xa[c] = t0;
-            if constexpr (PRO) xb[c] = t1;
+            if constexpr (TWO) xb[c] = t1;
         }
     };
     if constexpr (PF) load_group(((int64_t)blockIdx.x * (LF_BLOCK / WAVE) + wave) * 16, fa, fb);
@@ -1037,7 +1074,7 @@ __global__ __launch_bounds__(LF_BLOCK) void linear_fwd_kernel(const float* __res
         for (int t = 0; t < TCO; ++t) acc[t] = f32x4{bsel[t][0], bsel[t][1], bsel[t][2], bsel[t][3]};
         if constexpr (NCH > 0) {
             if constexpr (PF) {
-                if constexpr (PRO) load_group(row0 + row_stride, na, nb);
+                if constexpr (TWO) load_group(row0 + row_stride, na, nb);
                 else load_group(row0 + row_stride, na, fb);
             } else {
                 load_group(row0, fa, fb);
@@ -1045,7 +1082,9 @@ __global__ __launch_bounds__(LF_BLOCK) void linear_fwd_kernel(const float* __res
 #pragma unroll
             for (int c = 0; c < NCH; ++c) {
                 const int k0 = 16 * c + 4 * g;
-                const float4 xv = operand(rv, c, fa[c], fb[PRO ? c : 0]);
+                float4 xv;
+                if constexpr (UV) xv = uv_operand(r, rv, fa[c], fb[c]);
+                else xv = operand(rv, c, fa[c], fb[PRO ? c : 0]);
 #pragma unroll
                 for (int t = 0; t < TCO; ++t) {
                     const float4 wv = *reinterpret_cast<const float4*>(sW + (16 * t + rr) * Cip + k0);
@@ -1059,7 +1098,7 @@ __global__ __launch_bounds__(LF_BLOCK) void linear_fwd_kernel(const float* __res
 #pragma unroll
                 for (int c = 0; c < NCH; ++c) {
                     fa[c] = na[c];
-                    if constexpr (PRO) fb[c] = nb[c];
+                    if constexpr (TWO) fb[c] = nb[c];
                 }
             }
         } else {
@@ -1560,6 +1599,31 @@ extern "C" int crfconv_linear_forward_cat(const float* Xa, const float* Xb, int 
                                           int64_t M, int Ci, int Co, float* Y, float* stat_rec, crf_stream_t stream) {
     CRF_REQUIRE(Xb, CRF_ERR_ARG, "null pointer");
     return linear_forward_impl(Xa, Xb, split, W, bias, M, Ci, Co, 0, Y, stat_rec, stream);
+}
+
+// crfconv_pointconv_combine + crfconv_linear_forward in ONE launch for lin_out of a fine-level ResNet block: the operand
+// out = a2 U + (a2 shift + b2) V is formed while it is loaded (linear_fwd_kernel, EPI_UV) and stored to f->out on the way; a2, b2, aux2
+// and BatchNorm-2's running statistics as the combine leaves them.  Only the widths lin_out has at those levels.
+extern "C" int crfconv_linear_forward_uv_supported(int Ci, int Co) { return ((Ci == 8 && Co == 32) || (Ci == 16 && Co == 64)) ? 1 : 0; }
+
+extern "C" int crfconv_linear_forward_uv(const crf_uv_fold* f, const float* W, int64_t M, int Ci, int Co, float* Y, float* stat_rec,
+                                         crf_stream_t stream) {
+    CRF_REQUIRE(W && Y, CRF_ERR_ARG, "null pointer");
+    CRF_REQUIRE(crf::uv_fold_complete(f), CRF_ERR_ARG, "combine record: null pointer, or running statistics not as a pair");
+    CRF_REQUIRE(M > 0, CRF_ERR_ARG, "M must be positive");
+    CRF_REQUIRE(crfconv_linear_forward_uv_supported(Ci, Co), CRF_ERR_UNSUPPORTED, "combine prologue: %d -> %d is not a fine-level lin_out", Ci, Co);
+    const int tco = lf_tco(Ci, Co, false);
+    CRF_REQUIRE(16 * tco == Co && lf_hoist_chunks(Ci, true) == 1, CRF_ERR_UNSUPPORTED, "combine prologue: one column group, one chunk");
+    const dim3 grid((unsigned)crf::lf_blocks(M), 1u), blk(crf::LF_BLOCK);
+    const size_t lds = lf_lds_bytes(Ci, Co, false);
+    hipStream_t st = crf::as_stream(stream);
+    const crf::UvFold uv = crf::uv_fold_args(f);
+#define LFU(T) hipLaunchKernelGGL((crf::linear_fwd_kernel<T, false, true, crf::EPI_UV, 1>), grid, blk, lds, st, f->U, W, (const float*)nullptr, M, Ci, Co, 0, Y, stat_rec, (const float*)nullptr, (const float*)nullptr, 1.f, (const float*)nullptr, 0, (float*)nullptr, 0, (const float*)nullptr, (const long long*)nullptr, 0ull, 0u, 1.f, (const float*)nullptr, 1.f, uv)
+    if (tco == 2) LFU(2);
+    else LFU(4);
+#undef LFU
+    CRF_LAUNCH_CHECK();
+    return CRF_OK;
 }
 
 // BatchNorm coefficients from the records written by crfconv_linear_forward (instead of a statistics pass).

@@ -10,6 +10,7 @@
 // the backward) and the activation are each written once; nothing is re-read.
 #include "common.hpp"
 #include "gridsync.hpp"
+#include "uv_fold.hpp"
 
 namespace crf {
 
@@ -27,16 +28,21 @@ constexpr int64_t SM_MAX_ROWS = SM_MAX_ROWS_;      // (A/B: 10 240 = the third l
 // TCO: 16-channel output tiles per workgroup (tile = 64 rows x 16 TCO channels).  A wavefront issues Ci / 4 x TCO MFMAs, so
 // at Ci = 512 the 64-wide tile is 7 us of matrix pipe per wavefront while most CUs idle (40 workgroups for 1280 x 128
 // outputs): the host picks the narrowest tile that still gives the device >= SM_MIN_BLOCKS workgroups.
-template <int TCO>
-__global__ __launch_bounds__(SM_BLOCK) void mlp_small_fwd_kernel(const float* __restrict__ X, const float* __restrict__ W,
-                                                                 int M, int Ci, int Co, const float* __restrict__ gamma,
-                                                                 const float* __restrict__ beta, float* __restrict__ run_mean,
-                                                                 float* __restrict__ run_var, float momentum, float eps,
-                                                                 float slope, float* __restrict__ Y, float* __restrict__ A,
-                                                                 float* __restrict__ coef, float* __restrict__ rec,
-                                                                 unsigned* __restrict__ sync_ws,
-                                                                 const float* __restrict__ skip, float join_slope) {
-    __shared__ float sWbuf[2][SM_COLS * SM_LD];                // W chunk [64 co][64 k] (+4 pad: conflict-free b128 reads), double-buffered
+// UV (Ci <= SM_UV_MAXK): X is the PointConv combine helper(U, V) of uv_fold.hpp, formed when a fragment is loaded (X = U, uv.V = V) --
+// lin_out of a coarse ResNet block; the workgroups of column tile 0 store it to uv.out (each row exactly once), workgroup (0, 0)
+// publishes a2 / b2 / aux2 and advances BatchNorm-2's running statistics, as uv_combine_kernel's workgroup 0 does.
+constexpr int SM_UV_MAXK = 128;
+template <int TCO, bool UV>
+__device__ __forceinline__ void mlp_small_fwd_body(const float* __restrict__ X, const float* __restrict__ W,
+                                                   int M, int Ci, int Co, const float* __restrict__ gamma,
+                                                   const float* __restrict__ beta, float* __restrict__ run_mean,
+                                                   float* __restrict__ run_var, float momentum, float eps,
+                                                   float slope, float* __restrict__ Y, float* __restrict__ A,
+                                                   float* __restrict__ coef, float* __restrict__ rec,
+                                                   unsigned* __restrict__ sync_ws,
+                                                   const float* __restrict__ skip, float join_slope, const UvFold& uv) {
+    __shared__ float sWbuf[2][SM_COLS * SM_LD];
+    __shared__ __attribute__((aligned(16))) float s_uv[UV ? 2 : 1][UV ? SM_UV_MAXK : 4];      // a2 | a2 shift + b2 per input channel                // W chunk [64 co][64 k] (+4 pad: conflict-free b128 reads), double-buffered
     __shared__ double s_comb[2][SM_BLOCK];
     __shared__ float s_ab[2][SM_COLS];
     __shared__ int s_ok;
@@ -49,6 +55,24 @@ __global__ __launch_bounds__(SM_BLOCK) void mlp_small_fwd_kernel(const float* __
     const bool rv = r < M;
     const float* xrow = X + (int64_t)(rv ? r : 0) * Ci;
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    [[maybe_unused]] const float* vrow = UV ? uv.V + (int64_t)(rv ? r : 0) * Ci : nullptr;
+    if constexpr (UV) {                                         // one channel per thread; every workgroup derives the same values
+        if ((int)threadIdx.x < Ci) {
+            const int c = threadIdx.x;
+            const UvCoef k = uv_coef(c, Ci, uv.stats, uv.shift, uv.gamma, uv.beta, uv.n_edges, uv.eps);
+            s_uv[0][c] = k.a;
+            s_uv[1][c] = uv_vcoef(k);
+            if (blockIdx.x == 0 && blockIdx.y == 0)
+                uv_publish(c, Ci, k, uv.n_edges, uv.run_mean, uv.run_var, uv.momentum, uv.a2, uv.b2, uv.aux2);
+        }
+    }
+    // the operand fragment of channels k0 .. k0 + 3 from the raw (U, V) fragments; column tile 0 stores it
+    [[maybe_unused]] auto form = [&](int k0, float4 u, float4 v) -> float4 {
+        if (!(rv && k0 < Ci)) return zero4;
+        const float4 o = uv_out4(ld4(&s_uv[0][k0]), ld4(&s_uv[1][k0]), u, v);
+        if (blockIdx.y == 0) st4(uv.out + (int64_t)r * Ci + k0, o);
+        return o;
+    };
 
     f32x4s acc[TCO];
 #pragma unroll
@@ -59,16 +83,22 @@ __global__ __launch_bounds__(SM_BLOCK) void mlp_small_fwd_kernel(const float* __
     const int wr = threadIdx.x >> 4, k4 = threadIdx.x & 15;      // this thread stages W rows wr, wr + 16, wr + 32, wr + 48
     const float* wsrc = W + (int64_t)(co_base + wr) * Ci + 4 * k4;
     float4 wreg[TCO], xv[4], xn[4];
+    [[maybe_unused]] float4 vn[UV ? 4 : 1];
 #pragma unroll
     for (int i = 0; i < TCO; ++i) wreg[i] = 4 * k4 < Ci ? ld4(wsrc + (int64_t)16 * i * Ci) : zero4;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         const int k0 = 16 * c + 4 * g;
         xv[c] = (rv && k0 < Ci) ? ld4(xrow + k0) : zero4;
+        if constexpr (UV) vn[c] = (rv && k0 < Ci) ? ld4(vrow + k0) : zero4;
     }
 #pragma unroll
     for (int i = 0; i < TCO; ++i) st4(sWbuf[0] + (wr + 16 * i) * SM_LD + 4 * k4, wreg[i]);
     __syncthreads();
+    if constexpr (UV) {                                         // (the barrier above also covers s_uv)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) xv[c] = form(16 * c + 4 * g, xv[c], vn[c]);
+    }
     int cur = 0;
     for (int kc = 0; kc < Ci; kc += SM_KC) {
         const int kn = kc + SM_KC;
@@ -80,6 +110,7 @@ __global__ __launch_bounds__(SM_BLOCK) void mlp_small_fwd_kernel(const float* __
             for (int c = 0; c < 4; ++c) {
                 const int k0 = kn + 16 * c + 4 * g;
                 xn[c] = (rv && k0 < Ci) ? ld4(xrow + k0) : zero4;
+                if constexpr (UV) vn[c] = (rv && k0 < Ci) ? ld4(vrow + k0) : zero4;
             }
         }
         const float* sWc = sWbuf[cur];
@@ -99,7 +130,10 @@ __global__ __launch_bounds__(SM_BLOCK) void mlp_small_fwd_kernel(const float* __
 #pragma unroll
             for (int i = 0; i < TCO; ++i) st4(sWbuf[cur ^ 1] + (wr + 16 * i) * SM_LD + 4 * k4, wreg[i]);
 #pragma unroll
-            for (int c = 0; c < 4; ++c) xv[c] = xn[c];
+            for (int c = 0; c < 4; ++c) {
+                if constexpr (UV) xv[c] = form(kn + 16 * c + 4 * g, xn[c], vn[c]);
+                else xv[c] = xn[c];
+            }
         }
         __syncthreads();                                        // chunk kn staged; every reader of buffer `cur` is done
         cur ^= 1;
@@ -248,6 +282,31 @@ __global__ __launch_bounds__(SM_BLOCK) void mlp_small_fwd_kernel(const float* __
     fused_exit_reset(sync_ws, nblk, 2, bid);
 }
 
+template <int TCO>
+__global__ __launch_bounds__(SM_BLOCK) void mlp_small_fwd_kernel(const float* __restrict__ X, const float* __restrict__ W,
+                                                                 int M, int Ci, int Co, const float* __restrict__ gamma,
+                                                                 const float* __restrict__ beta, float* __restrict__ run_mean,
+                                                                 float* __restrict__ run_var, float momentum, float eps,
+                                                                 float slope, float* __restrict__ Y, float* __restrict__ A,
+                                                                 float* __restrict__ coef, float* __restrict__ rec,
+                                                                 unsigned* __restrict__ sync_ws,
+                                                                 const float* __restrict__ skip, float join_slope) {
+    mlp_small_fwd_body<TCO, false>(X, W, M, Ci, Co, gamma, beta, run_mean, run_var, momentum, eps, slope, Y, A, coef, rec, sync_ws, skip,
+                                   join_slope, UvFold());
+}
+template <int TCO>
+__global__ __launch_bounds__(SM_BLOCK) void mlp_small_fwd_uv_kernel(const float* __restrict__ U, const float* __restrict__ W,
+                                                                    int M, int Ci, int Co, const float* __restrict__ gamma,
+                                                                    const float* __restrict__ beta, float* __restrict__ run_mean,
+                                                                    float* __restrict__ run_var, float momentum, float eps,
+                                                                    float slope, float* __restrict__ Y, float* __restrict__ A,
+                                                                    float* __restrict__ coef, float* __restrict__ rec,
+                                                                    unsigned* __restrict__ sync_ws,
+                                                                    const float* __restrict__ skip, float join_slope, const UvFold uv) {
+    mlp_small_fwd_body<TCO, true>(U, W, M, Ci, Co, gamma, beta, run_mean, run_var, momentum, eps, slope, Y, A, coef, rec, sync_ws, skip,
+                                  join_slope, uv);
+}
+
 // Workgroups of the forward kernel that can be resident at once on this device (the barrier needs every one of them).
 static int mlp_small_capacity() {
     static int cap = -1;
@@ -255,7 +314,10 @@ static int mlp_small_capacity() {
         int dev = 0, cus = 0, per_cu = 0;
         if (hipGetDevice(&dev) != hipSuccess) return 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+        int per_cu_uv = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mlp_small_fwd_kernel<4>, SM_BLOCK, 0) != hipSuccess) return 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_uv, mlp_small_fwd_uv_kernel<4>, SM_BLOCK, 0) != hipSuccess) return 0;
+        if (per_cu_uv < per_cu) per_cu = per_cu_uv;               // one limit for both forms: the same shapes take either
         if (per_cu > 2) per_cu = 2;                                // stay well inside what the dispatcher really co-schedules
         cap = cus * per_cu;
     }
@@ -305,7 +367,7 @@ extern "C" size_t crfconv_mlp_small_workspace(int64_t M, int Co) {
 static int mlp_small_forward_impl(const float* X, const float* W, int64_t M, int Ci, int Co, const float* gamma,
                                   const float* beta, float* run_mean, float* run_var, float momentum, float eps,
                                   float slope, const float* skip, float join_slope, float* Y, float* A, float* coef, void* ws,
-                                  size_t ws_bytes, void* sync_ws, size_t sync_bytes, crf_stream_t stream) {
+                                  size_t ws_bytes, void* sync_ws, size_t sync_bytes, crf_stream_t stream, const UvFold* uv = nullptr) {
     CRF_REQUIRE(X && W && gamma && beta && Y && A && coef && ws && sync_ws, CRF_ERR_ARG, "null pointer");
     CRF_REQUIRE(mlp_small_shape_ok(M, Ci, Co), CRF_ERR_UNSUPPORTED, "shape m=%lld Ci=%d Co=%d outside the one-launch kernel",
                 (long long)M, Ci, Co);
@@ -319,9 +381,17 @@ static int mlp_small_forward_impl(const float* X, const float* W, int64_t M, int
 #define SMF(T) hipLaunchKernelGGL(mlp_small_fwd_kernel<T>, grid, dim3(SM_BLOCK), 0, as_stream(stream), X, W, (int)M, Ci, Co, gamma, beta, \
                                   run_mean, run_var, momentum, eps, slope, Y, A, coef, reinterpret_cast<float*>(ws),               \
                                   reinterpret_cast<unsigned*>(sync_ws), skip, join_slope)
-    if (tco == 4) SMF(4);
+#define SMU(T) hipLaunchKernelGGL(mlp_small_fwd_uv_kernel<T>, grid, dim3(SM_BLOCK), 0, as_stream(stream), X, W, (int)M, Ci, Co, gamma, beta, \
+                                  run_mean, run_var, momentum, eps, slope, Y, A, coef, reinterpret_cast<float*>(ws),                  \
+                                  reinterpret_cast<unsigned*>(sync_ws), skip, join_slope, *uv)
+    if (uv != nullptr) {
+        if (tco == 4) SMU(4);
+        else if (tco == 2) SMU(2);
+        else SMU(1);
+    } else if (tco == 4) SMF(4);
     else if (tco == 2) SMF(2);
     else SMF(1);
+#undef SMU
 #undef SMF
     CRF_LAUNCH_CHECK();
     return CRF_OK;
@@ -344,4 +414,20 @@ extern "C" int crfconv_mlp_small_forward_join(const float* X, const float* W, in
     CRF_REQUIRE(skip, CRF_ERR_ARG, "null pointer");
     return mlp_small_forward_impl(X, W, M, Ci, Co, gamma, beta, run_mean, run_var, momentum, eps, slope, skip, join_slope, Y, A, coef,
                                   ws, ws_bytes, sync_ws, sync_bytes, stream);
+}
+
+// crfconv_pointconv_combine(f) + crfconv_mlp_small_forward_join(f->out, ..) in one launch: lin_out of a coarse ResNet block forms its
+// operand from the PointConv layer's U and V (Ci <= 128 input channels).
+extern "C" int crfconv_mlp_small_forward_uv_supported(int Ci) { return (Ci >= 16 && Ci % 16 == 0 && Ci <= SM_UV_MAXK) ? 1 : 0; }
+
+extern "C" int crfconv_mlp_small_forward_join_uv(const crf_uv_fold* f, const float* W, int64_t M, int Ci, int Co, const float* gamma,
+                                                 const float* beta, float* run_mean, float* run_var, float momentum, float eps,
+                                                 float slope, const float* skip, float join_slope, float* Y, float* A, float* coef,
+                                                 void* ws, size_t ws_bytes, void* sync_ws, size_t sync_bytes, crf_stream_t stream) {
+    CRF_REQUIRE(skip, CRF_ERR_ARG, "null pointer");
+    CRF_REQUIRE(uv_fold_complete(f), CRF_ERR_ARG, "combine record: null pointer, or running statistics not as a pair");
+    CRF_REQUIRE(crfconv_mlp_small_forward_uv_supported(Ci), CRF_ERR_UNSUPPORTED, "combine prologue: Ci=%d outside 16..%d", Ci, SM_UV_MAXK);
+    const UvFold uv = uv_fold_args(f);
+    return mlp_small_forward_impl(f->U, W, M, Ci, Co, gamma, beta, run_mean, run_var, momentum, eps, slope, skip, join_slope, Y, A, coef,
+                                  ws, ws_bytes, sync_ws, sync_bytes, stream, &uv);
 }

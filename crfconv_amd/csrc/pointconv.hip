@@ -14,6 +14,7 @@
 #include "gridsync.hpp"
 #include "crf_matrices_body.hpp"
 #include "reduce64_body.hpp"
+#include "uv_fold.hpp"
 #include <algorithm>
 
 namespace crf {
@@ -660,36 +661,19 @@ __global__ __launch_bounds__(256) void uv_combine_kernel(const float* __restrict
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int d = 4 * d4;
     const int q = (int)(t % d4);
-    float a[4], b[4], sh[4];
+    float a[4], tv[4];
     const bool publish = blockIdx.x == 0 && threadIdx.x < d4;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         const int c = 4 * q + e;
-        const double m1 = stats[c] / n_edges;
-        const double mean = (double)shift[c] + m1;
-        double var = stats[d + c] / n_edges - m1 * m1;
-        if (var < 0.0) var = 0.0;
-        const double rstd = 1.0 / sqrt(var + (double)eps);
-        const double aa = (double)gamma[c] * rstd;
-        a[e] = (float)aa;
-        b[e] = (float)((double)beta[c] - aa * mean);
-        sh[e] = shift[c];
-        if (publish) {
-            a2_out[c] = a[e];
-            b2_out[c] = b[e];
-            aux2[c] = mean;
-            aux2[d + c] = rstd;
-            if (run_mean != nullptr) {
-                const double unb = n_edges > 1.0 ? var * (n_edges / (n_edges - 1.0)) : var;
-                run_mean[c] = (float)((1.0 - momentum) * run_mean[c] + momentum * mean);
-                run_var[c] = (float)((1.0 - momentum) * run_var[c] + momentum * unb);
-            }
-        }
+        const UvCoef k = uv_coef(c, d, stats, shift, gamma, beta, n_edges, eps);      // uv_fold.hpp: shared with the folded consumers
+        a[e] = k.a;
+        tv[e] = uv_vcoef(k);
+        if (publish) uv_publish(c, d, k, n_edges, run_mean, run_var, momentum, a2_out, b2_out, aux2);
     }
     if (t >= n4) return;
     const float4 u = ld4(U + 4 * t), v = ld4(V + 4 * t);
-    st4(out + 4 * t, make_float4(fmaf(a[0], u.x, fmaf(a[0], sh[0], b[0]) * v.x), fmaf(a[1], u.y, fmaf(a[1], sh[1], b[1]) * v.y),
-                                 fmaf(a[2], u.z, fmaf(a[2], sh[2], b[2]) * v.z), fmaf(a[3], u.w, fmaf(a[3], sh[3], b[3]) * v.w)));
+    st4(out + 4 * t, uv_out4(make_float4(a[0], a[1], a[2], a[3]), make_float4(tv[0], tv[1], tv[2], tv[3]), u, v));
 }
 
 // partial[blk][0][d] = sum_i g_i V_i, partial[blk][1][d] = sum_i g_i U_i over the block's row slice

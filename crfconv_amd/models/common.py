@@ -95,16 +95,19 @@ def mlp_group(pairs, shared=False, input_mask=None):
     return ops.mlp_group(blocks, shared=shared, input_mask=input_mask)
 
 
-def mlp_join(mlp, x, skip, slope=0.01, mask=None):
+def mlp_join(mlp, x, skip, slope=0.01, mask=None, combine=None):
     """leaky_relu(mlp(x) + skip, slope) for an MLP without activation -- the tail of a ResNet block
     (models/point_conv_big.py:84-88).  One fused node (BatchNorm + add + LeakyReLU in a single pass) where it applies
     (training, MFMA-sized rows), else the module followed by ops.add_lrelu.  mask: the ops.JoinMask the fused node shares with the
-    node that writes its output's gradient (left unarmed by the fallback)."""
+    node that writes its output's gradient (left unarmed by the fallback).  combine: the ops.CombineHandle of the PointConv layer whose
+    (possibly unfilled) output x is -- taken by the fused node, else the combine is launched before anything reads x."""
     if (mlp.training and mlp.bn is not None and mlp.activation is None and mlp.lin.bias is None and x.dtype == torch.float32
             and mlp.bn.batch_norm.affine and mlp.lin.out_features % 4 == 0):
-        out = ops.mlp_block_join(x, mlp.lin.weight, mlp.bn.batch_norm, skip, slope, mask=mask)
+        out = ops.mlp_block_join(x, mlp.lin.weight, mlp.bn.batch_norm, skip, slope, mask=mask, combine=combine)
         if out is not None:
             return out
+    if combine is not None:
+        combine.flush()
     return ops.add_lrelu(mlp(x), skip, slope)
 
 

@@ -62,11 +62,15 @@ class PointConv(nn.Module):
         first = self.weight_nn[0]
         return first.lin.weight, first.bn.batch_norm, self._moments(table, p_src, p_tgt), table
 
-    def forward(self, x, pos, neighbor_idx, prefold=None):
+    def forward(self, x, pos, neighbor_idx, prefold=None, defer_combine=False):
+        """defer_combine: returns (y, ops.CombineHandle) -- y may be unfilled until its one reader takes or flushes the handle."""
         table, p_src, p_tgt = self._geometry(pos, neighbor_idx)
         first, second = self.weight_nn[0], self.weight_nn[1]
         y = ops.point_conv(_flat(x), p_src, p_tgt, table, first.lin.weight, first.bn.batch_norm, second.lin.weight,
-                           second.bn.batch_norm, self.training, moments=self._moments(table, p_src, p_tgt), prefold=prefold)
+                           second.bn.batch_norm, self.training, moments=self._moments(table, p_src, p_tgt), prefold=prefold,
+                           defer_combine=defer_combine)
+        if defer_combine:
+            return y[0].reshape(x.shape[0], -1, x.shape[-1]), y[1]
         return y.reshape(x.shape[0], -1, x.shape[-1])
 
 
@@ -105,8 +109,8 @@ class ResNetBBlock(nn.Module):
             (h_in, x), skip = grouped
             if strided:
                 skip = self.max_pooling(skip, neighbor_idx)
-            y = self.point_conv(h_in, pos, neighbor_idx, prefold=prefold)
-            out = mlp_join(self.lin_out, y, skip, 0.01, mask=join_mask)
+            y, comb = self.point_conv(h_in, pos, neighbor_idx, prefold=prefold, defer_combine=True)
+            out = mlp_join(self.lin_out, y, skip, 0.01, mask=join_mask, combine=comb)      # lin_out's product forms y from the layer's U, V
             return (out, x) if return_input_alias else out
         h_in, x = mlp_fork(self.lin_in, x, input_mask)                # x: now the alias whose gradient lin_in's backward adds to its own
         if (strided and self.training and isinstance(sc, MLP) and sc.bn is not None and sc.activation is None
@@ -126,8 +130,8 @@ class ResNetBBlock(nn.Module):
                 skip = sc(x)
             if strided:                                    # strided block: pool the shortcut onto the coarse points
                 skip = self.max_pooling(skip, neighbor_idx)
-        y = self.point_conv(h_in, pos, neighbor_idx, prefold=prefold)
-        out = mlp_join(self.lin_out, y, skip, 0.01, mask=join_mask)        # lin_out + add + F.leaky_relu (default slope), as the reference
+        y, comb = self.point_conv(h_in, pos, neighbor_idx, prefold=prefold, defer_combine=True)
+        out = mlp_join(self.lin_out, y, skip, 0.01, mask=join_mask, combine=comb)      # lin_out + add + F.leaky_relu (default slope), as the reference
         return (out, x) if return_input_alias else out
 
 

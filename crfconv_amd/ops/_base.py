@@ -156,6 +156,15 @@ def check_gridsync(dev=None, reduced_flag=None):
 
 
 
+def _env_families(name):
+    """False (unset), True ('1', '', 'all') or the frozenset of names in a comma-separated environment variable."""
+    v = __import__('os').environ.get(name)
+    if v is None:
+        return False
+    v = v.strip().lower()
+    return True if v in ('', '1', 'all') else frozenset(q.strip() for q in v.split(',') if q.strip())
+
+
 class _State:
     """Switches the tests and bench.py's experiment knobs flip at run time (one object: the operator modules read it, a caller sets
     ``ops.state.<name>``)."""
@@ -165,6 +174,11 @@ class _State:
     # the LeakyReLU mask of a ResNet join's backward applied by the kernel that writes the join's gradient (ops.mlp.JoinMask);
     # CRFCONV_NO_MASK_FOLD=1: every join runs its own mask pass again (A/B runs of bench.py)
     no_mask_fold = __import__('os').environ.get('CRFCONV_NO_MASK_FOLD') is not None
+    # the PointConv combine out = a2 U + (a2 shift + b2) V formed by the Linear kernel of lin_out while it loads its operand
+    # (ops.pointconv.CombineHandle) instead of by an elementwise launch of its own.  True: every join launches the combine again;
+    # a set of consumer families ('fine': the row-streaming Linear, 'small': the one-launch coarse kernel, 'tiled': the tiled product
+    # with statistic records): those only.  CRFCONV_NO_COMBINE_FOLD=1, or a comma-separated list of families (A/B runs of bench.py)
+    no_combine_fold = _env_families('CRFCONV_NO_COMBINE_FOLD')
     # set by check_gridsync after a barrier failure (CRFCONV_NO_ONE_LAUNCH_MLP: from the start): launch-separated forward from then on
     small_mlp_disabled = __import__('os').environ.get('CRFCONV_NO_ONE_LAUNCH_MLP') is not None
     # the two launches of a coarse-level MLP backward (tile sums, dX product) as one whose product workgroups wait for the sums inside

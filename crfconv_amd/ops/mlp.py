@@ -43,12 +43,20 @@ def _use_fork(fork, x):
     return bool(fork and x.requires_grad and torch.is_grad_enabled() and not state.no_fork)
 
 
-def _stream_fwd(x, Wc, gamma, beta, run_mean, run_var, momentum, eps, slope=None, skip=None):
+def _stream_fwd(x, Wc, gamma, beta, run_mean, run_var, momentum, eps, slope=None, skip=None, fold=None):
     """Forward stem of the row-streaming blocks, (y, coef, out): the MFMA Linear with statistic records in its epilogue -- x [m, Ci],
     or the pair (xa, xb) read through two pointers --, then coefficients and apply (+ skip) + LeakyReLU in one launch.
-    slope None: the coefficients only (out = None) -- the dropout and pool nodes apply in a kernel of their own."""
+    slope None: the coefficients only (out = None) -- the dropout and pool nodes apply in a kernel of their own.
+    fold (a taken CombineHandle record): x is the unfilled `out` of a PointConv layer, formed and stored by the Linear's operand load."""
     st = stream_ptr()
-    if isinstance(x, tuple):
+    if fold is not None:
+        m, ci = x.shape
+        co = Wc.shape[0]
+        y = torch.empty((m, co), dtype=torch.float32, device=x.device)
+        nrec = _lib.load().crfconv_linear_forward_stat_records(m)
+        rec = torch.empty((nrec, 4, co), dtype=torch.float32, device=x.device)
+        _lib.call('crfconv_linear_forward_uv', ctypes.byref(fold[0]), ptr(Wc), m, ci, co, ptr(y), ptr(rec), st)
+    elif isinstance(x, tuple):
         xa, xb = x
         m, split = xa.shape
         ci, co = split + xb.shape[1], Wc.shape[0]
@@ -167,10 +175,10 @@ class _MLPBlockJoin(torch.autograd.Function):
     mask (JoinMask): when the node that writes g has folded the mask into its epilogue, g IS g1 and the mask pass does not run."""
 
     @staticmethod
-    def forward(ctx, x, W, gamma, beta, run_mean, run_var, momentum, eps, skip, slope, mask=None):
+    def forward(ctx, x, W, gamma, beta, run_mean, run_var, momentum, eps, skip, slope, mask=None, fold=None):
         x, Wc, skip = x.contiguous(), W.contiguous(), skip.contiguous()
         ctx.mask = mask
-        y, coef, out = _stream_fwd(x, Wc, gamma, beta, run_mean, run_var, momentum, eps, slope, skip)
+        y, coef, out = _stream_fwd(x, Wc, gamma, beta, run_mean, run_var, momentum, eps, slope, skip, fold)
         ctx.prm = (W, gamma, beta)
         ctx.save_for_backward(x, Wc, y, coef, out)
         ctx.slope = float(slope)
@@ -181,7 +189,7 @@ class _MLPBlockJoin(torch.autograd.Function):
         x, W, y, coef, out = ctx.saved_tensors
         g1 = _join_g1(ctx, g.contiguous(), out)
         gskip = g1 if ctx.needs_input_grad[8] else None
-        return (*_stream_bwd(ctx.prm, x, W, y, coef, g1, 1.0, ctx.needs_input_grad[0]), None, None, None, None, gskip, None, None)
+        return (*_stream_bwd(ctx.prm, x, W, y, coef, g1, 1.0, ctx.needs_input_grad[0]), None, None, None, None, gskip, None, None, None)
 
 
 class _MLPBlockDropout(torch.autograd.Function):
@@ -474,10 +482,11 @@ def _small_bwd(gA, y, coef, W, addend, slope, dgamma, dbeta, need_dx, mask=None)
     return gY, (_gemm(gY, W, addend=addend) if need_dx else None)
 
 
-def _small_fwd(x, Wc, gamma, beta, run_mean, run_var, momentum, eps, slope, skip=None, join_slope=1.0):
+def _small_fwd(x, Wc, gamma, beta, run_mean, run_var, momentum, eps, slope, skip=None, join_slope=1.0, fold=None):
     """(y, out, coef) of a coarse-level MLP block: the one-launch kernel of csrc/mlp_small.hip where its workgroups are co-resident
     (crfconv_mlp_small_supported), else -- the rows between that limit and the switch-over to the row-streaming forms -- the tiled
-    product with statistic records in its epilogue, the coefficient launch and one apply pass (with the join's add + LeakyReLU)."""
+    product with statistic records in its epilogue, the coefficient launch and one apply pass (with the join's add + LeakyReLU).
+    fold (join only): as _stream_fwd's -- the product kernel of either form forms x from the PointConv layer's U and V."""
     m, ci = x.shape
     co = Wc.shape[0]
     dev = x.device
@@ -490,7 +499,11 @@ def _small_fwd(x, Wc, gamma, beta, run_mean, run_var, momentum, eps, slope, skip
         nbytes = lib.crfconv_mlp_small_workspace(m, co)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         sync = gridsync_ws(dev)
-        if skip is None:
+        if fold is not None:
+            _lib.call('crfconv_mlp_small_forward_join_uv', ctypes.byref(fold[0]), ptr(Wc), m, ci, co, ptr(g), ptr(b), ptr(run_mean),
+                      ptr(run_var), float(momentum), float(eps), float(slope), ptr(skip), float(join_slope), ptr(y), ptr(out), ptr(coef),
+                      ptr(ws), nbytes, ptr(sync), sync.numel() * 4, stream_ptr())
+        elif skip is None:
             _lib.call('crfconv_mlp_small_forward', ptr(x), ptr(Wc), m, ci, co, ptr(g), ptr(b), ptr(run_mean), ptr(run_var),
                       float(momentum), float(eps), float(slope), ptr(y), ptr(out), ptr(coef), ptr(ws), nbytes, ptr(sync),
                       sync.numel() * 4, stream_ptr())
@@ -502,7 +515,10 @@ def _small_fwd(x, Wc, gamma, beta, run_mean, run_var, momentum, eps, slope, skip
     # product with the BatchNorm statistic records in its epilogue -> coefficients -> apply (+ skip, the join): three launches
     nrec = lib.crfconv_gemm_stat_records(m)
     rec = torch.empty((nrec, co, 4), dtype=torch.float32, device=dev)
-    _lib.call('crfconv_gemm_stats', ptr(x), ptr(Wc), m, co, ci, ptr(y), ptr(rec), stream_ptr())
+    if fold is not None:
+        _lib.call('crfconv_gemm_stats_uv', ctypes.byref(fold[0]), ptr(Wc), m, co, ci, ptr(y), ptr(rec), stream_ptr())
+    else:
+        _lib.call('crfconv_gemm_stats', ptr(x), ptr(Wc), m, co, ci, ptr(y), ptr(rec), stream_ptr())
     _lib.call('crfconv_bn_apply_from_records', ptr(rec), nrec, ptr(y), m, co, ptr(g), ptr(b), ptr(run_mean), ptr(run_var),
               float(momentum), float(eps), ptr(skip), float(slope if skip is None else join_slope), ptr(coef), ptr(out), stream_ptr())
     return y, out, coef
@@ -522,10 +538,10 @@ class _MLPSmallJoin(torch.autograd.Function):
     applies the join's LeakyReLU to the tile it holds in registers (crfconv_mlp_small_forward_join).  mask: as _MLPBlockJoin."""
 
     @staticmethod
-    def forward(ctx, x, W, gamma, beta, run_mean, run_var, momentum, eps, skip, slope, mask=None):
+    def forward(ctx, x, W, gamma, beta, run_mean, run_var, momentum, eps, skip, slope, mask=None, fold=None):
         x, Wc, skip = x.contiguous(), W.contiguous(), skip.contiguous()
         ctx.mask = mask
-        y, out, coef = _small_fwd(x, Wc, gamma, beta, run_mean, run_var, momentum, eps, 1.0, skip, slope)
+        y, out, coef = _small_fwd(x, Wc, gamma, beta, run_mean, run_var, momentum, eps, 1.0, skip, slope, fold)
         ctx.prm = (W, gamma, beta)
         ctx.save_for_backward(x, Wc, y, coef, out)
         ctx.slope = float(slope)
@@ -537,13 +553,25 @@ class _MLPSmallJoin(torch.autograd.Function):
         x, W, y, coef, out = ctx.saved_tensors
         g1 = _join_g1(ctx, g.contiguous(), out)
         gskip = g1 if ctx.needs_input_grad[8] else None
-        return (*_small_tail(ctx, x, W, y, coef, g1, None, 1.0), None, None, None, None, gskip, None, None)
+        return (*_small_tail(ctx, x, W, y, coef, g1, None, 1.0), None, None, None, None, gskip, None, None, None)
 
 
-def mlp_block_join(x, W, bn, skip, slope, mask=None):
+def _join_fold_family(small, m, ci, co):
+    """The consumer family whose product kernel can form a PointConv `out` in its operand load for this join, or None."""
+    lib = _lib.load()
+    if not small:
+        return 'fine' if lib.crfconv_linear_forward_uv_supported(ci, co) == 1 else None
+    if not state.small_mlp_disabled and lib.crfconv_mlp_small_supported(m, ci, co) == 1:
+        return 'small' if lib.crfconv_mlp_small_forward_uv_supported(ci) == 1 else None
+    return 'tiled' if lib.crfconv_gemm_stats_uv_supported(m, co, ci) == 1 else None
+
+
+def mlp_block_join(x, W, bn, skip, slope, mask=None, combine=None):
     """lrelu(BatchNorm_train(x W^T) + skip, slope) as one node where the big-level fused block applies, else None (the
     caller then runs its own lin_out + add_lrelu).  mask: the JoinMask shared with the node that will write the output's total gradient;
-    armed here, so a consumer only folds the mask behind a fused join node."""
+    armed here, so a consumer only folds the mask behind a fused join node.  combine (ops.pointconv.CombineHandle): x is the unfilled
+    output of a PointConv training forward -- the node's product kernel forms it (and stores it) where a folded form takes the widths,
+    else the combine is launched here; on a None return the CALLER flushes the handle."""
     if state.no_join or skip.shape[:-1] != x.shape[:-1] or skip.shape[-1] != W.shape[0] or skip.dtype != torch.float32:
         return None
     m = x.numel() // x.shape[-1]
@@ -552,12 +580,20 @@ def mlp_block_join(x, W, bn, skip, slope, mask=None):
         return None
     require_gpu(x, W, skip)
     tick(bn)
-    fn = _MLPSmallJoin if _mlp_small_ok(m, ci, co) else _MLPBlockJoin      # coarse levels: folded into the one-launch kernel
+    small = _mlp_small_ok(m, ci, co)
+    fn = _MLPSmallJoin if small else _MLPBlockJoin      # coarse levels: folded into the one-launch kernel
+    fold = None
+    if combine is not None and combine.pending:
+        family = _join_fold_family(small, m, ci, co) if combine.feeds(x.reshape(-1, ci)) else None
+        if family is not None and not combine.fold_off(family):
+            fold = combine.take()
+        else:
+            combine.flush()
     if mask is not None and not state.no_mask_fold and torch.is_grad_enabled():
         mask.slope = float(slope)
     else:
         mask = None
-    out = fn.apply(x.reshape(-1, ci), W, *_bn_args(bn), skip.reshape(-1, co), slope, mask)
+    out = fn.apply(x.reshape(-1, ci), W, *_bn_args(bn), skip.reshape(-1, co), slope, mask, fold)
     return out.reshape(x.shape[:-1] + (co,))
 
 

@@ -5,7 +5,7 @@ import torch
 
 from .. import _lib
 from ..graph import ptr, require_gpu, stream_ptr
-from ._base import _f32c, _pc_ticket, _ptr_array
+from ._base import _f32c, _pc_ticket, _ptr_array, state
 
 # ------------------------------------------------------------------------------ PointConv
 class MomentsEntry(tuple):
@@ -56,6 +56,52 @@ def relpos_moments(pos_src, pos_tgt, table, out=None):
     return mean, cov, n, packed, mean32                   # [4]: mean rel in float32 (kernel argument)
 
 
+class CombineHandle:
+    """The last launch of a PointConv training forward, out = a2 U + (a2 shift + b2) V (crfconv_pointconv_combine), not yet issued:
+    `out`, a2, b2 and aux2 are allocated but unfilled.  The ONE forward reader of `out` -- lin_out of the ResNet block, through
+    mlp_block_join -- either takes the handle and forms `out` in the operand load of its own Linear kernel (`take`: the record of
+    arguments; that kernel stores `out`, publishes the coefficients and advances BatchNorm-2's running statistics), or calls `flush`
+    -- the combine launch after all -- before anything reads `out`.  The backward reads the same tensors either way."""
+    __slots__ = ('args', 'keep', 'out')
+
+    def __init__(self):
+        self.args = self.keep = self.out = None
+
+    def arm(self, U, V, stats, shift, g2, be2, n_e, rm2, rv2, mom2, eps2, a2, b2, aux2, out):
+        self.keep = (U, V, stats, shift, g2, be2, rm2, rv2, a2, b2, aux2, out)
+        self.args = (U, V, stats, shift, g2, be2, float(n_e), rm2, rv2, float(mom2), float(eps2), a2, b2, aux2, out)
+        self.out = out
+
+    @property
+    def pending(self):
+        return self.args is not None
+
+    def fold_off(self, family):
+        off = state.no_combine_fold
+        return off is True or (bool(off) and family in off)
+
+    def feeds(self, x):
+        """x [m, d] is `out` itself (the join's operand, seen through the model's reshapes)."""
+        return self.pending and x.data_ptr() == self.out.data_ptr() and tuple(x.shape) == tuple(self.out.shape) and x.is_contiguous()
+
+    def take(self):
+        """(crf_uv_fold record, the tensors it points to): the caller's kernel does the combine's work."""
+        adr = lambda t: None if t is None else t.data_ptr()
+        U, V, stats, shift, g2, be2, n_e, rm2, rv2, mom2, eps2, a2, b2, aux2, out = self.args
+        rec = _lib.UvFold(adr(U), adr(V), adr(stats), adr(shift), adr(g2), adr(be2), n_e, adr(rm2), adr(rv2), mom2, eps2, adr(a2), adr(b2),
+                          adr(aux2), adr(out))
+        keep, self.args, self.keep, self.out = self.keep, None, None, None
+        return rec, keep
+
+    def flush(self):
+        if self.args is None:
+            return
+        U, V, stats, shift, g2, be2, n_e, rm2, rv2, mom2, eps2, a2, b2, aux2, out = self.args
+        _lib.call('crfconv_pointconv_combine', ptr(U), ptr(V), ptr(stats), ptr(shift), ptr(g2), ptr(be2), n_e, ptr(rm2), ptr(rv2), mom2, eps2,
+                  out.shape[0], out.shape[1], ptr(a2), ptr(b2), ptr(aux2), ptr(out), stream_ptr())
+        self.args = self.keep = self.out = None
+
+
 class _PointConv(torch.autograd.Function):
     """out[i,c] = sum_k w_ik[c] x[j,c],  w = BN2(W2 lrelu(BN1(W1 rel))),  rel = p_tgt[i] - p_src[j].
 
@@ -65,7 +111,7 @@ class _PointConv(torch.autograd.Function):
     source-major gather for dx.  Nothing per-edge is ever stored (except for d >= 64, see bwd_dump)."""
 
     @staticmethod
-    def forward(ctx, x, W1, g1, be1, W2, g2, be2, pos_src, pos_tgt, table, mom, bn1_state, bn2_state, slope, mom32=None, prefold=None):
+    def forward(ctx, x, W1, g1, be1, W2, g2, be2, pos_src, pos_tgt, table, mom, bn1_state, bn2_state, slope, mom32=None, prefold=None, handle=None):
         require_gpu(x, W1, W2, pos_src, pos_tgt)
         if x.shape[0] != table.m_src or pos_src.shape[0] != table.m_src or pos_tgt.shape[0] != table.m_tgt:
             raise _lib.CrfConvError('point_conv: x %d / pos_src %d rows for %d sources, pos_tgt %d rows for %d targets'
@@ -112,7 +158,9 @@ class _PointConv(torch.autograd.Function):
         b2 = torch.empty(d, dtype=torch.float32, device=dev)
         aux2 = torch.empty(2 * d, dtype=torch.float64, device=dev)
         out = torch.empty((m_tgt, d), dtype=torch.float32, device=dev)
-        if use2:       # BatchNorm-2 folded from the statistics inside the elementwise combine
+        if use2 and handle is not None:       # the combine is left to the consumer of `out` (CombineHandle)
+            handle.arm(U, V, stats, shift, g2c, be2c, n_e, rm2, rv2, mom2, eps2, a2, b2, aux2, out)
+        elif use2:     # BatchNorm-2 folded from the statistics inside the elementwise combine
             _lib.call('crfconv_pointconv_combine', ptr(U), ptr(V), ptr(stats), ptr(shift), ptr(g2c), ptr(be2c), n_e,
                       ptr(rm2), ptr(rv2), float(mom2), float(eps2), m_tgt, d, ptr(a2), ptr(b2), ptr(aux2), ptr(out), st)
         else:
@@ -223,7 +271,7 @@ class _PointConv(torch.autograd.Function):
             dbe1 = torch.empty(d, dtype=torch.float32, device=dev)
             _lib.call('crfconv_pointconv_fold1_bwd', ptr(W1), ptr(g1), ptr(mom), ptr(aux1), ptr(dA1b1), float(ctx.eps1),
                       1 if ctx.use1 else 0, d, ptr(dW1), ptr(dg1), ptr(dbe1), ptr(dW2_64), ptr(dW2) if dW2_64 is not None else None, st)
-        return (dx, dW1, dg1, dbe1, dW2, coef[3], coef[4], None, None, None, None, None, None, None, None, None)
+        return (dx, dW1, dg1, dbe1, dW2, coef[3], coef[4], None, None, None, None, None, None, None, None, None, None)
 
 
 _PC_D = (4, 8, 16, 32, 64, 128)
@@ -281,12 +329,15 @@ def point_conv_prefold(layers, training, momentum=0.1):
     return out
 
 
-def point_conv(x, pos_src, pos_tgt, table, W1, bn1, W2, bn2, training, momentum=0.1, moments=None, slope=0.1, prefold=None):
+def point_conv(x, pos_src, pos_tgt, table, W1, bn1, W2, bn2, training, momentum=0.1, moments=None, slope=0.1, prefold=None,
+               defer_combine=False):
     """Functional PointConv over flattened clouds.
 
     x [m_src, d]; pos_* [m, 3]; W1 [d, 3], W2 [d, d] Linear weights (no bias);
     bn1 / bn2: torch.nn.BatchNorm1d modules (affine + running statistics, updated in training);
-    prefold: this layer's entry of point_conv_prefold (same W1, bn1, moments, table and mode), or None."""
+    prefold: this layer's entry of point_conv_prefold (same W1, bn1, moments, table and mode), or None.
+    defer_combine: returns (out, CombineHandle) -- in training mode `out` may come back UNFILLED, and the caller hands the handle to
+    the one reader of `out` (mlp_block_join) or calls its flush() before anything reads `out`."""
     d = x.shape[1]
     if d not in _PC_D:
         raise _lib.CrfConvError('PointConv width d=%d not in %s' % (d, _PC_D))
@@ -296,8 +347,11 @@ def point_conv(x, pos_src, pos_tgt, table, W1, bn1, W2, bn2, training, momentum=
         moments = relpos_moments(pos_src, pos_tgt, table)
     mom = moments[3] if len(moments) > 3 else pack_moments(moments)
     mom32 = moments[4] if len(moments) > 4 else None
-    return _PointConv.apply(x, W1, bn1.weight, bn1.bias, W2, bn2.weight, bn2.bias, pos_src, pos_tgt, table, mom,
-                            _bn_state(bn1, training, momentum), _bn_state(bn2, training, momentum), float(slope), mom32, prefold)
+    handle = CombineHandle() if defer_combine else None
+    fold = handle if (handle is not None and state.no_combine_fold is not True) else None
+    out = _PointConv.apply(x, W1, bn1.weight, bn1.bias, W2, bn2.weight, bn2.bias, pos_src, pos_tgt, table, mom,
+                           _bn_state(bn1, training, momentum), _bn_state(bn2, training, momentum), float(slope), mom32, prefold, fold)
+    return (out, handle) if defer_combine else out
 
 
 # names of the sibling modules, imported LAST: every use is inside a function body, so import cycles between the families are harmless

@@ -312,6 +312,15 @@ int crfconv_pointconv_combine(const float* U, const float* V, const double* stat
                               const float* gamma2, const float* beta2, double n_edges, float* run_mean,
                               float* run_var, float momentum, float eps, int64_t m_tgt, int d, float* a2, float* b2,
                               double* aux2, float* out, crf_stream_t stream);
+/* The combine formed by its CONSUMER: lin_out of the ResNet block is the only forward reader of `out`, and the Linear kernels below can
+ * form out = a2 U + (a2 shift + b2) V while they load their operand (same arithmetic, bit for bit: csrc/uv_fold.hpp), store it on the way
+ * and publish a2 / b2 / aux2 / the running statistics as the combine does -- the elementwise pass and its launch disappear.  The
+ * arguments of crfconv_pointconv_combine as one record: */
+typedef struct {
+    const float* U; const float* V; const double* stats; const float* shift; const float* gamma2; const float* beta2;
+    double n_edges; float* run_mean; float* run_var; float momentum; float eps;
+    float* a2; float* b2; double* aux2; float* out;
+} crf_uv_fold;
 int crfconv_pointconv_bwd_reduce_uv(const float* gout, const float* U, const float* V, int64_t m_tgt, int d,
                                     const float* shift, const double* aux2, const float* gamma2, double n_edges,
                                     int use_batch, float* ca, float* cb, float* cc, float* dgamma2, float* dbeta2,
@@ -487,6 +496,13 @@ int crfconv_mlp_small_forward_join(const float* X, const float* W, int64_t M, in
                                    const float* beta, float* run_mean, float* run_var, float momentum, float eps, float slope,
                                    const float* skip, float join_slope, float* Y, float* A, float* coef, void* workspace,
                                    size_t workspace_bytes, void* sync_ws, size_t sync_bytes, crf_stream_t stream);
+/* crfconv_pointconv_combine(f) + crfconv_mlp_small_forward_join(f->out, ..) in one launch: the operand of lin_out is formed from the
+ * PointConv layer's U and V while it is loaded (Ci <= 128; crfconv_mlp_small_forward_uv_supported), column tile 0 stores f->out. */
+int crfconv_mlp_small_forward_uv_supported(int Ci);
+int crfconv_mlp_small_forward_join_uv(const crf_uv_fold* f, const float* W, int64_t M, int Ci, int Co, const float* gamma,
+                                      const float* beta, float* run_mean, float* run_var, float momentum, float eps, float slope,
+                                      const float* skip, float join_slope, float* Y, float* A, float* coef, void* ws, size_t ws_bytes,
+                                      void* sync_ws, size_t sync_bytes, crf_stream_t stream);
 
 /* Backward of one MLP block  A = lrelu(BN_train(X W^T), slope)  (models/common.py:34-40, batch statistics) in two passes
  * over the activations and three launches: pass 1 streams (gA, Y, X) once and leaves the partials of sum g1, sum g1 yh,
@@ -537,6 +553,11 @@ int crfconv_mlp_backward_add_mask(const float* gA, const float* Y, const float* 
  * the forward product is crfconv_linear_forward_cat, the backward writes dXa / dXb separately. */
 int crfconv_linear_forward_cat(const float* Xa, const float* Xb, int split, const float* W, const float* bias, int64_t M,
                                int Ci, int Co, float* Y, float* stat_rec, crf_stream_t stream);
+/* crfconv_pointconv_combine(f) + crfconv_linear_forward(f->out, W) in one launch (row-streaming form; Ci -> Co = 8 -> 32, 16 -> 64: the
+ * fine-level lin_out widths, crfconv_linear_forward_uv_supported). */
+int crfconv_linear_forward_uv_supported(int Ci, int Co);
+int crfconv_linear_forward_uv(const crf_uv_fold* f, const float* W, int64_t M, int Ci, int Co, float* Y, float* stat_rec,
+                              crf_stream_t stream);
 int crfconv_mlp_backward_cat(const float* gA, const float* Y, const float* Xa, const float* Xb, int split, const float* W,
                              const float* coef, float slope, int64_t M, int Ci, int Co, float* dXa, float* dXb, float* dW,
                              float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, unsigned* ticket,
@@ -614,6 +635,10 @@ int crfconv_mlp_small_backward(const float* gA, const float* Y, const float* coe
  * (the Linear + BatchNorm blocks between the one-launch kernel's row limit and the row-streaming forms). */
 size_t crfconv_gemm_stat_records(int64_t M);
 int crfconv_gemm_stats(const float* A, const float* B, int64_t M, int N, int K, float* C, float* stat_rec, crf_stream_t stream);
+/* crfconv_pointconv_combine(f) + crfconv_gemm_stats(f->out, B, ..) in one launch (K <= 128; crfconv_gemm_stats_uv_supported): the tiles,
+ * the summation order and the records are crfconv_gemm_stats's. */
+int crfconv_gemm_stats_uv_supported(int64_t M, int N, int K);
+int crfconv_gemm_stats_uv(const crf_uv_fold* f, const float* B, int64_t M, int N, int K, float* C, float* stat_rec, crf_stream_t stream);
 /* ---- several INDEPENDENT coarse-level MLP blocks per launch (round 5).  A coarse launch is a chain of dependent memory round trips
  * on a grid that covers a fraction of the chip, so two blocks whose inputs are both ready -- unary_nn[i] and pairwise_nn[i] of a CRF
  * layer (models/continuous_crf_conv_big.py:56-60), shortcut and lin_in of a strided ResNet block (models/point_conv_big.py:79-88) --
