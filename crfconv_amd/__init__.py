@@ -59,8 +59,9 @@ _pick_hw_queues()
 
 from . import _lib, data, graph, models, ops, optim, train, utils          # noqa: E402
 from .data import Data, MultiScaleData, multiscale_compute
+from .infer import InferenceNet
 
 _fit_host_threads()
 
 __version__ = '0.1.0'
-__all__ = ['models', 'utils', 'ops', 'optim', 'train', 'graph', 'data', 'Data', 'MultiScaleData', 'multiscale_compute']
+__all__ = ['models', 'utils', 'ops', 'optim', 'train', 'graph', 'data', 'Data', 'MultiScaleData', 'multiscale_compute', 'InferenceNet']

@@ -213,6 +213,9 @@ SIGNATURES = {
     'crfconv_vote_update_repeated': (_i, [_vp, _vp, _vp, _i64, _i, _d, _vp, _i64, _vp, _vp, _vp, _vp]),
     'crfconv_vote_update_batch': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _d, _vp, _i, _vp]),
     'crfconv_vote_confusion': (_i, [_vp, _i64, _i, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    'crfconv_linear_bn_act': (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _f, _i64, _i, _i, _vp, _vp]),
+    'crfconv_gemm_bn_act': (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i64, _i, _i, _i, _vp, _vp]),
+    'crfconv_bn_eval_coef_jobs': (_i, [_vp, _i, _vp]),
 }
 
 
@@ -280,6 +283,12 @@ class BnApplyJob(ctypes.Structure):
                 ('gamma', ctypes.c_void_p), ('beta', ctypes.c_void_p), ('run_mean', ctypes.c_void_p), ('run_var', ctypes.c_void_p),
                 ('momentum', ctypes.c_float), ('eps', ctypes.c_float), ('skip', ctypes.c_void_p), ('slope', ctypes.c_float),
                 ('coef', ctypes.c_void_p), ('y', ctypes.c_void_p)]
+
+
+class BnCoefJob(ctypes.Structure):
+    """crf_bn_coef_job of include/crfconv_amd.h."""
+    _fields_ = [('gamma', ctypes.c_void_p), ('beta', ctypes.c_void_p), ('run_mean', ctypes.c_void_p), ('run_var', ctypes.c_void_p),
+                ('eps', ctypes.c_float), ('C', ctypes.c_int32), ('coef', ctypes.c_void_p)]
 
 
 class MlpBwdJob(ctypes.Structure):

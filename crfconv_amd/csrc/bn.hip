@@ -92,7 +92,18 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restric
     }
 }
 
-// eval mode: coefficients from running statistics
+// eval mode: the coefficient block of channel c from running statistics (one thread per channel)
+__device__ __forceinline__ void bn_coef_eval_channel(const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                     const float* __restrict__ run_mean, const float* __restrict__ run_var,
+                                                     float eps, int C, int c, float* __restrict__ coef) {
+    const double rstd = 1.0 / sqrt((double)run_var[c] + (double)eps);
+    const double a = (double)gamma[c] * rstd;
+    coef[c] = (float)a;
+    coef[C + c] = (float)((double)beta[c] - a * (double)run_mean[c]);
+    coef[2 * C + c] = run_mean[c];
+    coef[3 * C + c] = (float)rstd;
+}
+
 __global__ __launch_bounds__(256) void bn_coef_eval_kernel(const float* __restrict__ gamma,
                                                            const float* __restrict__ beta,
                                                            const float* __restrict__ run_mean,
@@ -100,12 +111,37 @@ __global__ __launch_bounds__(256) void bn_coef_eval_kernel(const float* __restri
                                                            float* __restrict__ coef) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= C) return;
-    const double rstd = 1.0 / sqrt((double)run_var[c] + (double)eps);
-    const double a = (double)gamma[c] * rstd;
-    coef[c] = (float)a;
-    coef[C + c] = (float)((double)beta[c] - a * (double)run_mean[c]);
-    coef[2 * C + c] = run_mean[c];
-    coef[3 * C + c] = (float)rstd;
+    bn_coef_eval_channel(gamma, beta, run_mean, run_var, eps, C, c, coef);
+}
+
+// The eval-mode coefficients of MANY BatchNorms in one launch (an inference forward recomputes those of every layer up front:
+// crfconv_bn_eval_coef_jobs).  The table travels in the kernel arguments (capturable into a hipGraph); workgroup g serves 256
+// channels of one job (group_begin = prefix sum of ceil(C / 256)).
+constexpr int BCJ_MAX = 64;
+struct BnCoefJobTable {
+    const float* gamma[BCJ_MAX];
+    const float* beta[BCJ_MAX];
+    const float* run_mean[BCJ_MAX];
+    const float* run_var[BCJ_MAX];
+    float* coef[BCJ_MAX];
+    float eps[BCJ_MAX];
+    int C[BCJ_MAX];
+    int group_begin[BCJ_MAX + 1];
+    int njobs;
+};
+static_assert(sizeof(BnCoefJobTable) <= 4096, "the job table is a kernel argument");
+
+__global__ __launch_bounds__(256) void bn_coef_eval_jobs_kernel(const BnCoefJobTable t) {
+    const int g = blockIdx.x;
+    int lo = 0, hi = t.njobs;                         // largest j with group_begin[j] <= g
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (t.group_begin[mid] <= g) lo = mid; else hi = mid;
+    }
+    const int C = t.C[lo];
+    const int c = (g - t.group_begin[lo]) * 256 + (int)threadIdx.x;
+    if (c >= C) return;
+    bn_coef_eval_channel(t.gamma[lo], t.beta[lo], t.run_mean[lo], t.run_var[lo], t.eps[lo], C, c, t.coef[lo]);
 }
 
 // y = lrelu(a x + b, slope)   (slope == 1: no activation)
@@ -547,6 +583,37 @@ extern "C" int crfconv_bn_backward(const float* gy, const float* x, const float*
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(ew_grid(n4)), dim3(BN_BLOCK), 0, st, gy, x, coef, bcoef, n4, C / 4, slope,
                        gx);
     CRF_LAUNCH_CHECK();
+    return CRF_OK;
+}
+
+// coef_j [4][C_j] = a | b | mean | rstd from the running statistics of every job's BatchNorm -- what crfconv_bn_forward leaves in
+// eval mode (the same device code), for all layers of a network in one launch (one per 64 jobs).  jobs: host array.
+extern "C" int crfconv_bn_eval_coef_jobs(const crf_bn_coef_job* jobs, int njobs, crf_stream_t stream) {
+    CRF_REQUIRE(jobs || njobs == 0, CRF_ERR_ARG, "null pointer");
+    CRF_REQUIRE(njobs >= 0, CRF_ERR_ARG, "njobs=%d < 0", njobs);
+    hipStream_t st = as_stream(stream);
+    for (int j0 = 0; j0 < njobs; j0 += BCJ_MAX) {
+        BnCoefJobTable t;
+        const int n = njobs - j0 < BCJ_MAX ? njobs - j0 : BCJ_MAX;
+        int64_t total = 0;
+        for (int j = 0; j < n; ++j) {
+            const crf_bn_coef_job& jb = jobs[j0 + j];
+            CRF_REQUIRE(jb.gamma && jb.beta && jb.run_mean && jb.run_var && jb.coef && jb.C > 0, CRF_ERR_ARG, "job %d is malformed", j0 + j);
+            t.gamma[j] = jb.gamma; t.beta[j] = jb.beta; t.run_mean[j] = jb.run_mean; t.run_var[j] = jb.run_var; t.coef[j] = jb.coef;
+            t.eps[j] = jb.eps; t.C[j] = jb.C;
+            t.group_begin[j] = (int)total;
+            total += (jb.C + 255) / 256;
+            CRF_REQUIRE(total < ((int64_t)1 << 30), CRF_ERR_ARG, "too many channels in one batch");
+        }
+        for (int j = n; j <= BCJ_MAX; ++j) t.group_begin[j] = (int)total;
+        for (int j = n; j < BCJ_MAX; ++j) {
+            t.gamma[j] = nullptr; t.beta[j] = nullptr; t.run_mean[j] = nullptr; t.run_var[j] = nullptr; t.coef[j] = nullptr;
+            t.eps[j] = 0.f; t.C[j] = 0;
+        }
+        t.njobs = n;
+        hipLaunchKernelGGL(bn_coef_eval_jobs_kernel, dim3((unsigned)total), dim3(256), 0, st, t);
+        CRF_LAUNCH_CHECK();
+    }
     return CRF_OK;
 }
 

@@ -98,8 +98,11 @@ constexpr int gemm_lds_floats() {
 // UV form (crfconv_gemm_stats_uv; K <= GM_UV_MAXK): the A operand is the PointConv combine helper(U, V) of uv_fold.hpp, formed when a
 // chunk is parked (A = U, uv->V = V; coefficients in uvc [2][GM_UV_MAXK], LDS of the caller's) -- lin_out of the ResNet block at the level
 // the tiled product serves; the workgroups of column tile 0 store it to uv->out, workgroup (0, 0) publishes as uv_combine_kernel's does.
+// BNACT form (crfconv_gemm_bn_act; N % 4 == 0): the eval-mode MLP block in the epilogue -- C = lrelu(add_rn(fmaf(a, v, b), skip), slope),
+// v = the product (+ bias), a | b = rows 0 and 1 of pro.coef [>= 2][N], skip = `addend` (or null), slope = pro.slope (1: no activation):
+// bn_apply_kernel's / bn_apply_add_kernel's arithmetic (bn.hip) on the accumulator instead of on a stored product.
 constexpr int GM_UV_MAXK = 128;
-template <int WM, int WN, int WR, int WC, bool BNK, bool VEC, bool PRO, bool STATS, bool UV = false>
+template <int WM, int WN, int WR, int WC, bool BNK, bool VEC, bool PRO, bool STATS, bool UV = false, bool BNACT = false>
 __device__ __forceinline__ void gemm_tile(const float* __restrict__ A, const float* __restrict__ B,
                                           const float* __restrict__ bias, const float* __restrict__ addend,
                                           int M, int N, int K, float* __restrict__ C, const GemmPro& pro,
@@ -110,6 +113,7 @@ __device__ __forceinline__ void gemm_tile(const float* __restrict__ A, const flo
     static_assert(WR * WC * WAVE == GM_BLOCK, "four wavefronts");
     static_assert(!UV || (VEC && !PRO), "the combine prologue: aligned widths, not the dX product");
     static_assert(!PRO || (VEC && !BNK), "the prologue form is the dX product of aligned widths");
+    static_assert(!BNACT || (!PRO && !STATS && !UV), "the BatchNorm epilogue belongs to the plain form");
     constexpr int BM = 16 * WM * WR, BN = 16 * WN * WC;
     constexpr int LDA = GM_BK + 4;                      // [BM][LDA]: 16-byte fragment reads along k, 8 lanes cover the 32 banks
     constexpr int LDN = GM_BK + 4;                      // BNK: [BN][LDN], read like A
@@ -358,7 +362,20 @@ __device__ __forceinline__ void gemm_tile(const float* __restrict__ A, const flo
             const int n = n0 + 16 * (wc * WN + j) + 4 * g;
             if (n >= N) continue;
             float4 o = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
-            if (addend != nullptr) {
+            if constexpr (BNACT) {
+                const float4 ca = gm_ld4<VEC>(pro.coef + n, N - n), cb = gm_ld4<VEC>(pro.coef + N + n, N - n);
+                o = make_float4(fmaf(ca.x, o.x, cb.x), fmaf(ca.y, o.y, cb.y), fmaf(ca.z, o.z, cb.z), fmaf(ca.w, o.w, cb.w));
+                if (addend != nullptr) {
+                    const float4 k4 = gm_ld4<VEC>(addend + (int64_t)row * N + n, N - n);
+                    o = make_float4(add_rn(o.x, k4.x), add_rn(o.y, k4.y), add_rn(o.z, k4.z), add_rn(o.w, k4.w));
+                }
+                if (pro.slope != 1.f) {
+                    o.x = o.x > 0.f ? o.x : pro.slope * o.x;
+                    o.y = o.y > 0.f ? o.y : pro.slope * o.y;
+                    o.z = o.z > 0.f ? o.z : pro.slope * o.z;
+                    o.w = o.w > 0.f ? o.w : pro.slope * o.w;
+                }
+            } else if (addend != nullptr) {
                 const float4 a4 = gm_ld4<VEC>(addend + (int64_t)row * N + n, N - n);
                 o.x += a4.x; o.y += a4.y; o.z += a4.z; o.w += a4.w;
             }
@@ -409,6 +426,19 @@ __global__ __launch_bounds__(GM_BLOCK) void gemm_kernel(const float* __restrict_
                                                         float* __restrict__ stat_rec = nullptr) {
     __shared__ __attribute__((aligned(16))) float lds[gemm_lds_floats<WM, WN, WR, WC, BNK, PRO>()];
     gemm_tile<WM, WN, WR, WC, BNK, VEC, PRO, STATS>(A, B, bias, addend, M, N, K, C, pro, stat_rec, blockIdx.x, blockIdx.y, lds);
+}
+
+// the plain form with the BNACT epilogue (crfconv_gemm_bn_act): coef [>= 2][N] = a | b, skip [M, N] or null
+template <int WM, int WN, int WR, int WC, bool BNK, bool VEC>
+__global__ __launch_bounds__(GM_BLOCK) void gemm_bn_act_kernel(const float* __restrict__ A, const float* __restrict__ B,
+                                                               const float* __restrict__ bias, const float* __restrict__ skip,
+                                                               int M, int N, int K, float* __restrict__ C,
+                                                               const float* __restrict__ coef, float slope) {
+    __shared__ __attribute__((aligned(16))) float lds[gemm_lds_floats<WM, WN, WR, WC, BNK, false>()];
+    GemmPro pro;
+    pro.coef = coef;
+    pro.slope = slope;
+    gemm_tile<WM, WN, WR, WC, BNK, VEC, false, false, false, true>(A, B, bias, skip, M, N, K, C, pro, nullptr, blockIdx.x, blockIdx.y, lds);
 }
 
 // SEVERAL products C_j = A_j B_j (B [K, N], aligned widths, 32 x 32 tiles) in one launch: the tiles of the jobs are laid end to
@@ -889,26 +919,63 @@ extern "C" int crfconv_gemm_supported(int64_t M, int N, int K) {
     return (M >= 1 && M < (int64_t)1 << 31 && N >= 1 && K >= 1 && N < (1 << 24) && K < (1 << 24)) ? 1 : 0;
 }
 
+// tile shapes (rows x columns per workgroup): 0 = 64 x 64, 1 = 32 x 64, 2 = 64 x 32, 3 = 32 x 32 -- the largest that still gives the
+// grid `min_blocks` workgroups.  Measured on the shapes of the training step (scratch/gemm_bench.py, graph replays): 32 x 32 is the
+// fastest or within 0.5 us of it from 640 x 64 to 163 840 x 32 -- these launches are latency-bound, many short wavefronts win
+static int gemm_shape(int64_t M, int N) {
+    constexpr int min_blocks = 4096;
+    auto blocks = [&](int bm, int bn) { return ((M + bm - 1) / bm) * (int64_t)((N + bn - 1) / bn); };
+    if (N > 32 && blocks(64, 64) >= min_blocks) return 0;
+    if (N > 32 && blocks(32, 64) >= min_blocks) return 1;
+    if (blocks(64, 32) >= min_blocks) return 2;
+    return 3;
+}
+
 // C [M, N] = A [M, K] · B + bias + addend.  b_is_nk != 0: B is [N, K] row-major (the F.linear weight: C = A Bᵀ),
 // else [K, N] row-major (C = A B: dX = gY · W with W [Co, Ci]).  bias [N] and addend [M, N] may be NULL; addend may alias C.
 extern "C" int crfconv_gemm(const float* A, const float* B, const float* bias, const float* addend, int64_t M, int N, int K,
                             int b_is_nk, float* C, void* stream) {
     CRF_REQUIRE(A != nullptr && B != nullptr && C != nullptr, CRF_ERR_ARG, "null operand");
     CRF_REQUIRE(crfconv_gemm_supported(M, N, K), CRF_ERR_UNSUPPORTED, "gemm %lld x %d x %d: shape out of range", (long long)M, N, K);
-    // tile shapes (rows x columns per workgroup): 64 x 64, 32 x 64, 64 x 32, 32 x 32 -- the largest that still gives the
-    // grid `min_blocks` workgroups.  Measured on the shapes of the training step (scratch/gemm_bench.py, graph replays): 32 x 32 is the
-    // fastest or within 0.5 us of it from 640 x 64 to 163 840 x 32 -- these launches are latency-bound, many short wavefronts win
-    constexpr int min_blocks = 4096;
-    auto blocks = [&](int bm, int bn) { return ((M + bm - 1) / bm) * (int64_t)((N + bn - 1) / bn); };
-    int shape = 3;
-    if (N > 32 && blocks(64, 64) >= min_blocks) shape = 0;
-    else if (N > 32 && blocks(32, 64) >= min_blocks) shape = 1;
-    else if (blocks(64, 32) >= min_blocks) shape = 2;
+    const int shape = gemm_shape(M, N);
     hipStream_t st = crf::as_stream(stream);
     const dim3 blk(crf::GM_BLOCK);
     const bool vec = N % 4 == 0 && K % 4 == 0;           // 16-byte accesses; odd widths (13-class logits) go element by element
 #define GM2(WM, WN, WR, WC, NK, V) \
     hipLaunchKernelGGL((crf::gemm_kernel<WM, WN, WR, WC, NK, V>), grid, blk, 0, st, A, B, bias, addend, (int)M, N, K, C)
+#define GM(WM, WN, WR, WC)                                                                                                    \
+    do {                                                                                                                      \
+        const dim3 grid((unsigned)((M + 16 * WM * WR - 1) / (16 * WM * WR)), (unsigned)((N + 16 * WN * WC - 1) / (16 * WN * WC))); \
+        if (b_is_nk) { if (vec) GM2(WM, WN, WR, WC, true, true); else GM2(WM, WN, WR, WC, true, false); }                    \
+        else { if (vec) GM2(WM, WN, WR, WC, false, true); else GM2(WM, WN, WR, WC, false, false); }                           \
+    } while (0)
+    switch (shape) {
+        case 0: GM(2, 2, 2, 2); break;       // 64 x 64
+        case 1: GM(1, 2, 2, 2); break;       // 32 x 64
+        case 2: GM(1, 2, 4, 1); break;       // 64 x 32
+        default: GM(1, 1, 2, 2); break;      // 32 x 32
+    }
+#undef GM
+#undef GM2
+    CRF_LAUNCH_CHECK();
+    return CRF_OK;
+}
+
+// The eval-mode MLP block as ONE launch on the tiled product: C = lrelu(add_rn(fmaf(a, A · B (+ bias), b), skip), slope) with
+// coef = the BatchNorm's coefficient rows a | b ([>= 2][N]: crfconv_bn_eval_coef_jobs, crfconv_bn_forward); skip [M, N] may be NULL,
+// slope 1 = no activation.  The tile shape crfconv_gemm picks for (M, N, K), the same summation order: bit-identical to that product
+// followed by crfconv_bn_apply (and crfconv_add_lrelu with a skip).  N % 4 == 0.
+extern "C" int crfconv_gemm_bn_act(const float* A, const float* B, const float* bias, const float* coef, const float* skip, float slope,
+                                   int64_t M, int N, int K, int b_is_nk, float* C, void* stream) {
+    CRF_REQUIRE(A != nullptr && B != nullptr && C != nullptr && coef != nullptr, CRF_ERR_ARG, "null operand");
+    CRF_REQUIRE(crfconv_gemm_supported(M, N, K), CRF_ERR_UNSUPPORTED, "gemm %lld x %d x %d: shape out of range", (long long)M, N, K);
+    CRF_REQUIRE(N % 4 == 0, CRF_ERR_UNSUPPORTED, "N=%d must be a multiple of 4", N);
+    const int shape = gemm_shape(M, N);
+    hipStream_t st = crf::as_stream(stream);
+    const dim3 blk(crf::GM_BLOCK);
+    const bool vec = K % 4 == 0;
+#define GM2(WM, WN, WR, WC, NK, V) \
+    hipLaunchKernelGGL((crf::gemm_bn_act_kernel<WM, WN, WR, WC, NK, V>), grid, blk, 0, st, A, B, bias, skip, (int)M, N, K, C, coef, slope)
 #define GM(WM, WN, WR, WC)                                                                                                    \
     do {                                                                                                                      \
         const dim3 grid((unsigned)((M + 16 * WM * WR - 1) / (16 * WM * WR)), (unsigned)((N + 16 * WN * WC - 1) / (16 * WN * WC))); \

@@ -892,7 +892,10 @@ constexpr int LF_BLOCK = LF_BLOCK_, LF_WAVES = LF_BLOCK / WAVE;
 // PointConv combine helper(U, V) of uv_fold.hpp, formed when the fragment is loaded (X = U, uv.V = V) and stored to uv.out by the same lane
 // -- each row group is streamed by ONE workgroup per column group, the first column group stores; workgroup (0, 0) publishes a2 / b2 / aux2
 // and advances BatchNorm-2's running statistics as uv_combine_kernel's workgroup 0 does.  lin_out of a fine-level ResNet block.
-constexpr int EPI_NONE = 0, EPI_ADD = 1, EPI_DROPOUT = 2, EPI_ADD_MASK = 3, EPI_UV = 4;
+// 5 (not PRO; Co % 4 == 0): the eval-mode MLP block in the product's epilogue -- Y = lrelu(add_rn(fmaf(a, y, b), skip), slope) with
+// pro = the BatchNorm's [>= 2][Co] coefficient rows a | b, addend = skip [M, Co] (or null: no residual) and slope (1: no activation):
+// bn_apply_kernel's / bn_apply_add_kernel's arithmetic (bn.hip) on the accumulator instead of on a stored y.  No statistic records.
+constexpr int EPI_NONE = 0, EPI_ADD = 1, EPI_DROPOUT = 2, EPI_ADD_MASK = 3, EPI_UV = 4, EPI_BN_ACT = 5;
 // NCH > 0 (round 4; Ci <= 16 NCH, VEC4): the operand fragments of ALL k chunks of a row group are requested at once and those of
 // the wavefront's NEXT row group before the current group's products (NCH <= LF_PF_MAX) -- the rolled loop (NCH = 0) pays one
 // dependent memory round trip per chunk, eight per group at 128 inputs, with two to four wavefronts per SIMD to hide them.
@@ -916,7 +919,9 @@ __global__ __launch_bounds__(LF_BLOCK) void linear_fwd_kernel(const float* __res
                                                               const UvFold uv = UvFold()) {
     static_assert(EPI != EPI_ADD_MASK || (PRO && VEC4), "the masked epilogue is the aligned dX product's");
     static_assert(EPI != EPI_UV || (!PRO && VEC4 && NCH == 1), "the combine prologue is the narrow aligned forward's");
+    static_assert(EPI != EPI_BN_ACT || !PRO, "the BatchNorm epilogue is the forward product's");
     constexpr bool UV = EPI == EPI_UV, TWO = PRO || UV;              // TWO: two raw fragments per chunk
+    constexpr bool BNA = EPI == EPI_BN_ACT;
     // mask_ref [M, Co] (EPI_ADD_MASK): the saved output of the join in front of this block (this block's own input x)
     // drop_counter (not PRO, one-pointer output): Y = dropout_mask .* (X W^T) * drop_scale with the counter-based mask of
     // common.hpp (element e = row * Co + column) -- the backward of nn.Dropout applied while the gradient of the Linear
@@ -968,6 +973,35 @@ __global__ __launch_bounds__(LF_BLOCK) void linear_fwd_kernel(const float* __res
             const int co = co_base + 16 * t + 4 * g + e;
             bsel[t][e] = (bias != nullptr && co < Co) ? bias[co] : 0.f;
         }
+    // EPI_BN_ACT: the coefficients of the four channels this lane STORES in pass t (the same in every row group): through the staging
+    // tile a lane stores float4 number lane + 64 t of the [16][16 TCO] tile, else its own accumulator columns
+    [[maybe_unused]] float4 bna[BNA ? TCO : 1], bnb[BNA ? TCO : 1];
+    if constexpr (BNA) {
+#pragma unroll
+        for (int t = 0; t < TCO; ++t) {
+            const int co = TCO >= 2 ? co_base + 4 * ((lane + WAVE * t) % (4 * TCO)) : co_base + 16 * t + 4 * g;
+            bna[t] = bnb[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (co < Co) {
+                bna[t] = *reinterpret_cast<const float4*>(pro + co);
+                bnb[t] = *reinterpret_cast<const float4*>(pro + Co + co);
+            }
+        }
+    }
+    // out = lrelu(add_rn(fmaf(a, y, b), skip), slope) on four channels
+    [[maybe_unused]] auto bn_act4 = [&](float4 y, const float4 a, const float4 b, const float* skp) -> float4 {
+        float4 o = make_float4(fmaf(a.x, y.x, b.x), fmaf(a.y, y.y, b.y), fmaf(a.z, y.z, b.z), fmaf(a.w, y.w, b.w));
+        if (skp != nullptr) {
+            const float4 k = *reinterpret_cast<const float4*>(skp);
+            o = make_float4(add_rn(o.x, k.x), add_rn(o.y, k.y), add_rn(o.z, k.z), add_rn(o.w, k.w));
+        }
+        if (slope != 1.f) {
+            o.x = o.x > 0.f ? o.x : slope * o.x;
+            o.y = o.y > 0.f ? o.y : slope * o.y;
+            o.z = o.z > 0.f ? o.z : slope * o.z;
+            o.w = o.w > 0.f ? o.w : slope * o.w;
+        }
+        return o;
+    };
     float s1[TCO][4], s2[TCO][4], sh[TCO][4];
 #pragma unroll
     for (int t = 0; t < TCO; ++t)
@@ -1158,6 +1192,7 @@ __global__ __launch_bounds__(LF_BLOCK) void linear_fwd_kernel(const float* __res
                         o4.z = r4.z > 0.f ? o4.z : mask_slope * o4.z;
                         o4.w = r4.w > 0.f ? o4.w : mask_slope * o4.w;
                     }
+                    if constexpr (BNA) o4 = bn_act4(o4, bna[i], bnb[i], addend != nullptr ? addend + orow * Co + co : nullptr);
                     if constexpr (EPI == EPI_DROPOUT) {
                         {
                             const unsigned long long ctr = (unsigned long long)drop_counter[0];
@@ -1205,6 +1240,13 @@ __global__ __launch_bounds__(LF_BLOCK) void linear_fwd_kernel(const float* __res
                     }
                 }
             }
+            if constexpr (BNA) {
+                if (rv && co < Co) {
+                    const float4 o4 = bn_act4(make_float4(acc[t][0], acc[t][1], acc[t][2], acc[t][3]), bna[t], bnb[t],
+                                              addend != nullptr ? addend + r * Co + co : nullptr);
+                    acc[t] = f32x4{o4.x, o4.y, o4.z, o4.w};
+                }
+            }
             if constexpr (EPI == EPI_DROPOUT) {
                 if (rv) {
                     const unsigned long long ctr = (unsigned long long)drop_counter[0];
@@ -1232,7 +1274,7 @@ __global__ __launch_bounds__(LF_BLOCK) void linear_fwd_kernel(const float* __res
             }
         }
         }
-        if (stat_partial != nullptr) {
+        if (!BNA && stat_partial != nullptr) {
             if (!have_shift) {   // shift = this wave's first row (lane with rr == 0 of each co group)
 #pragma unroll
                 for (int t = 0; t < TCO; ++t)
@@ -1252,7 +1294,7 @@ __global__ __launch_bounds__(LF_BLOCK) void linear_fwd_kernel(const float* __res
             }
         }
     }
-    if (stat_partial != nullptr) {
+    if (!BNA && stat_partial != nullptr) {
         // one record {shift, n, sum, sumsq} per BLOCK and channel: the 16 row-lanes fold by shuffles, the 4 waves
         // through LDS, re-based on wave 0's shift (sum (v - s0) = a + n d, sum (v - s0)^2 = b + 2 d a + n d^2)
         __syncthreads();                                 // sW is dead: reuse it as [4 waves][4][16*TCO]
@@ -1539,9 +1581,16 @@ struct LinearDropout {
     float scale = 1.f;
 };
 
+// the eval-mode block's epilogue (EPI_BN_ACT): coef = the BatchNorm's coefficient rows a | b, skip [M, Co] or null, slope (1: none)
+struct LinearBnAct {
+    const float* coef = nullptr;
+    const float* skip = nullptr;
+    float slope = 1.f;
+};
+
 static int linear_forward_impl(const float* X, const float* Xb, int xsplit, const float* W, const float* bias, int64_t M,
                                int Ci, int Co, int transpose_w, float* Y, float* stat_rec, crf_stream_t stream,
-                               LinearDropout drop = LinearDropout()) {
+                               LinearDropout drop = LinearDropout(), LinearBnAct bn = LinearBnAct()) {
     CRF_REQUIRE(X && W && Y, CRF_ERR_ARG, "null pointer");
     CRF_REQUIRE(M > 0, CRF_ERR_ARG, "M must be positive");
     CRF_REQUIRE(crfconv_linear_forward_supported(Ci, Co), CRF_ERR_UNSUPPORTED, "weight slab %dx%d does not fit LDS", Co, Ci);
@@ -1555,10 +1604,10 @@ static int linear_forward_impl(const float* X, const float* Xb, int xsplit, cons
     hipStream_t st = crf::as_stream(stream);
     const bool vec4 = (Ci % 4) == 0 && (Co % 4) == 0;
     const int nch = lf_hoist_chunks(Ci, vec4);       // 1 / 2 / 4 / 8 chunks: the hoisted loop; 0: the rolled one
-#define LF4(T, V, E, N) hipLaunchKernelGGL((crf::linear_fwd_kernel<T, false, V, E, N>), grid, blk, lds, st, X, W, bias, M, Ci, Co, transpose_w, Y, stat_rec, (const float*)nullptr, (const float*)nullptr, 1.f, Xb, xsplit, (float*)nullptr, 0, (const float*)nullptr, drop.counter, drop.seed, drop.threshold, drop.scale)
+#define LF4(T, V, E, N) hipLaunchKernelGGL((crf::linear_fwd_kernel<T, false, V, E, N>), grid, blk, lds, st, X, W, bias, M, Ci, Co, transpose_w, Y, stat_rec, (const float*)nullptr, bn.coef, bn.slope, Xb, xsplit, (float*)nullptr, 0, bn.skip, drop.counter, drop.seed, drop.threshold, drop.scale)
 #define LF3(T, V, E) do { if (V && nch == 1) LF4(T, V, E, 1); else if (V && nch == 2) LF4(T, V, E, 2); else if (V && nch == 4) LF4(T, V, E, 4); else if (V && nch == 8) LF4(T, V, E, 8); else LF4(T, V, E, 0); } while (0)
-#define LF2(T, V) do { if (drop.counter != nullptr) LF4(T, V, crf::EPI_DROPOUT, 0); else LF3(T, V, crf::EPI_NONE); } while (0)
-#define LF(T) do { if (vec4) LF2(T, true); else if (drop.counter != nullptr) LF4(T, false, crf::EPI_DROPOUT, 0); else LF4(T, false, crf::EPI_NONE, 0); } while (0)
+#define LF2(T, V) do { if (bn.coef != nullptr) LF3(T, V, crf::EPI_BN_ACT); else if (drop.counter != nullptr) LF4(T, V, crf::EPI_DROPOUT, 0); else LF3(T, V, crf::EPI_NONE); } while (0)
+#define LF(T) do { if (vec4) LF2(T, true); else if (bn.coef != nullptr) LF4(T, false, crf::EPI_BN_ACT, 0); else if (drop.counter != nullptr) LF4(T, false, crf::EPI_DROPOUT, 0); else LF4(T, false, crf::EPI_NONE, 0); } while (0)
     switch (tco) {
         case 1: LF(1); break;
         case 2: LF(2); break;
@@ -1599,6 +1648,21 @@ extern "C" int crfconv_linear_forward_cat(const float* Xa, const float* Xb, int 
                                           int64_t M, int Ci, int Co, float* Y, float* stat_rec, crf_stream_t stream) {
     CRF_REQUIRE(Xb, CRF_ERR_ARG, "null pointer");
     return linear_forward_impl(Xa, Xb, split, W, bias, M, Ci, Co, 0, Y, stat_rec, stream);
+}
+
+// The eval-mode MLP block as ONE launch: Y = lrelu(add_rn(fmaf(a, [X | Xb] W^T (+ bias), b), skip), slope) with coef = the BatchNorm's
+// coefficient rows a | b (crfconv_bn_eval_coef_jobs, crfconv_bn_forward); Xb (with split) and skip may be NULL, slope 1 = no activation.
+// Grid, LDS and summation order of crfconv_linear_forward / _cat: bit-identical to that product followed by crfconv_bn_apply
+// (and crfconv_add_lrelu with a skip).  Co % 4 == 0.
+extern "C" int crfconv_linear_bn_act(const float* X, const float* Xb, int split, const float* W, const float* bias, const float* coef,
+                                     const float* skip, float slope, int64_t M, int Ci, int Co, float* Y, crf_stream_t stream) {
+    CRF_REQUIRE(coef, CRF_ERR_ARG, "null pointer");
+    CRF_REQUIRE(Co % 4 == 0, CRF_ERR_UNSUPPORTED, "Co=%d must be a multiple of 4", Co);
+    LinearBnAct bn;
+    bn.coef = coef;
+    bn.skip = skip;
+    bn.slope = slope;
+    return linear_forward_impl(X, Xb, Xb ? split : 0, W, bias, M, Ci, Co, 0, Y, nullptr, stream, LinearDropout(), bn);
 }
 
 // crfconv_pointconv_combine + crfconv_linear_forward in ONE launch for lin_out of a fine-level ResNet block: the operand

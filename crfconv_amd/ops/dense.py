@@ -250,5 +250,94 @@ def bn_act(x, bn, training, slope=1.0, records=None):
     return y.reshape(shape)
 
 
+# ------------------------------------------------------------------------------ inference: the eval-mode MLP block as one launch
+def bn_eval_coefs(bns, out=None):
+    """(flat, views): the eval-mode coefficient blocks [4, C] = a | b | mean | rstd of the BatchNorm1d modules `bns`, computed from
+    their running statistics by ONE launch per 64 modules (crfconv_bn_eval_coef_jobs: what bn_act leaves as `coef` in eval mode,
+    the same device code) into one flat float32 device buffer; views[i] is the block of bns[i].  out: a buffer of at least
+    4 * sum(C) floats to fill instead of a new one."""
+    bns = list(bns)
+    if not bns:
+        raise _lib.CrfConvError('bn_eval_coefs: no BatchNorm given')
+    for bn in bns:
+        if not (bn.affine and bn.running_mean is not None and bn.running_var is not None):
+            raise _lib.CrfConvError('bn_eval_coefs: affine BatchNorm with running statistics only')
+        require_gpu(bn.weight, bn.bias, bn.running_mean, bn.running_var)
+        for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var):
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise _lib.CrfConvError('bn_eval_coefs: contiguous float32 parameters and buffers only (got %s)' % t.dtype)
+    dev = bns[0].weight.device
+    total = 4 * sum(bn.num_features for bn in bns)
+    if out is None:
+        out = torch.empty(total, dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or out.device != dev or out.numel() < total or not out.is_contiguous():
+        raise _lib.CrfConvError('bn_eval_coefs: `out` must be a contiguous float32 buffer of >= %d elements on %s' % (total, dev))
+    jobs = (_lib.BnCoefJob * len(bns))()
+    views, off = [], 0
+    for j, bn in enumerate(bns):
+        C = bn.num_features
+        view = out[off:off + 4 * C].view(4, C)
+        jb = jobs[j]
+        jb.gamma, jb.beta, jb.run_mean, jb.run_var = ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean), ptr(bn.running_var)
+        jb.eps, jb.C, jb.coef = float(bn.eps), C, ptr(view)
+        views.append(view)
+        off += 4 * C
+    _lib.call('crfconv_bn_eval_coef_jobs', ctypes.cast(jobs, ctypes.c_void_p), len(bns), stream_ptr())
+    return out, views
+
+
+def linear_bn_act(x, W, coef, slope=1.0, skip=None, xb=None, bias=None):
+    """lrelu(BN_eval([x | xb] W^T (+ bias)) (+ skip), slope) on [..., Ci] rows as ONE launch: the product kernels with BatchNorm, the
+    residual add and the activation in their epilogue (crfconv_linear_bn_act / crfconv_gemm_bn_act).  Inference only -- the result
+    has no grad_fn.  coef: the BatchNorm's [4, Co] (or [2, Co]) coefficient block (bn_eval_coefs); slope 1: no activation; skip
+    [..., Co]: the ResNet join; xb [..., Cb]: the operand is the column concatenation, left implicit where the row-streaming
+    kernel runs and built by cat2 in front of the tiled one.  The kernel is chosen as linear() chooses; the result is
+    bit-identical to linear -> bn_act(eval) (-> add_lrelu).  float32 CUDA tensors, Co % 4 == 0."""
+    tensors = [t for t in (x, W, coef, skip, xb, bias) if t is not None]
+    require_gpu(*tensors)
+    for t in tensors:
+        if t.dtype != torch.float32:
+            raise _lib.CrfConvError('linear_bn_act: float32 only (got %s): the path computes in the reference\'s arithmetic' % t.dtype)
+    co = W.shape[0]
+    ca = x.shape[-1]
+    cb = 0 if xb is None else xb.shape[-1]
+    if xb is not None and xb.shape[:-1] != x.shape[:-1]:
+        raise _lib.CrfConvError('linear_bn_act: x %s and xb %s differ in their leading shape' % (tuple(x.shape), tuple(xb.shape)))
+    if W.dim() != 2 or W.shape[1] != ca + cb:
+        raise _lib.CrfConvError('linear_bn_act: W %s does not take %d input channels' % (tuple(W.shape), ca + cb))
+    if co % 4:
+        raise _lib.CrfConvError('linear_bn_act: %d output channels (a multiple of 4 is needed)' % co)
+    if coef.shape[-1] != co or coef.numel() < 2 * co:
+        raise _lib.CrfConvError('linear_bn_act: coefficient block %s for %d channels' % (tuple(coef.shape), co))
+    if skip is not None and (skip.shape[-1] != co or skip.shape[:-1] != x.shape[:-1]):
+        raise _lib.CrfConvError('linear_bn_act: skip %s for an output of %s' % (tuple(skip.shape), tuple(x.shape[:-1]) + (co,)))
+    if bias is not None and bias.numel() != co:
+        raise _lib.CrfConvError('linear_bn_act: bias of %d elements for %d channels' % (bias.numel(), co))
+    from .mlp import cat2
+    lead = x.shape[:-1]
+    with torch.no_grad():
+        x2 = x.detach().reshape(-1, ca).contiguous()
+        m = x2.shape[0]
+        y = torch.empty((m, co), dtype=torch.float32, device=x.device)
+        if m == 0:
+            return y.reshape(lead + (co,))
+        Wc, cf = W.detach().contiguous(), coef.detach().contiguous()
+        b = None if bias is None else bias.detach().contiguous()
+        sk = None if skip is None else skip.detach().reshape(-1, co).contiguous()
+        xb2 = None if xb is None else xb.detach().reshape(-1, cb).contiguous()
+        streaming = _mfma_ok(m, ca + cb, co)
+        if xb2 is not None and not (streaming and ca % 4 == 0 and cb % 4 == 0):
+            x2, xb2 = cat2(x2, xb2), None
+        if streaming:
+            _lib.call('crfconv_linear_bn_act', ptr(x2), ptr(xb2), ca if xb2 is not None else 0, ptr(Wc), ptr(b), ptr(cf), ptr(sk),
+                      float(slope), m, ca + cb, co, ptr(y), stream_ptr())
+        else:
+            if not _lib.load().crfconv_gemm_supported(m, co, ca + cb):
+                raise _lib.CrfConvError('product %d x %d x %d is outside the tiled kernel\'s range (crfconv_gemm_supported)' % (m, co, ca + cb))
+            _lib.call('crfconv_gemm_bn_act', ptr(x2), ptr(Wc), ptr(b), ptr(cf), ptr(sk), float(slope), m, co, ca + cb, 1, ptr(y),
+                      stream_ptr())
+    return y.reshape(lead + (co,))
+
+
 # names of the sibling modules, imported LAST: every use is inside a function body, so import cycles between the families are harmless
 from .defer import _defer_ok, _defer_weight_grad  # noqa: E402

@@ -553,6 +553,23 @@ int crfconv_mlp_backward_add_mask(const float* gA, const float* Y, const float* 
  * the forward product is crfconv_linear_forward_cat, the backward writes dXa / dXb separately. */
 int crfconv_linear_forward_cat(const float* Xa, const float* Xb, int split, const float* W, const float* bias, int64_t M,
                                int Ci, int Co, float* Y, float* stat_rec, crf_stream_t stream);
+/* ---- inference: the eval-mode MLP block (Linear -> BatchNorm with running statistics -> LeakyReLU, models/common.py:26-40, and the
+ * ResNet join behind lin_out, models/point_conv_big.py:84-88) as ONE launch: the product kernels with the BatchNorm in the epilogue,
+ *   Y = lrelu(add_rn(fmaf(a, y, b), skip), slope),   y = the product (+ bias),
+ * coef = rows a | b of the BatchNorm's [4, C] coefficient block, skip [M, Co] (NULL: no residual), slope 1 = no activation.
+ * Same grid, LDS, tiles and summation order as the product alone, the arithmetic of crfconv_bn_apply / crfconv_bn_apply_add: results are
+ * bit-identical to crfconv_linear_forward(_cat) / crfconv_gemm -> crfconv_bn_forward(eval) (-> crfconv_add_lrelu).  Co (N) % 4 == 0.
+ *   crfconv_linear_bn_act : the row-streaming kernel; Xb != NULL: the operand is [X | Xb] split at column `split` (both % 4 == 0)
+ *   crfconv_gemm_bn_act   : the tiled kernel
+ *   crfconv_bn_eval_coef_jobs : the [4, C] coefficient blocks of many BatchNorms from their running statistics, one launch per 64 jobs
+ *                               (jobs: host array; the device code of crfconv_bn_forward's eval branch) */
+int crfconv_linear_bn_act(const float* X, const float* Xb, int split, const float* W, const float* bias, const float* coef,
+                          const float* skip, float slope, int64_t M, int Ci, int Co, float* Y, crf_stream_t stream);
+int crfconv_gemm_bn_act(const float* A, const float* B, const float* bias, const float* coef, const float* skip, float slope,
+                        int64_t M, int N, int K, int b_is_nk, float* C, crf_stream_t stream);
+typedef struct { const float* gamma; const float* beta; const float* run_mean; const float* run_var; float eps; int C; float* coef;
+} crf_bn_coef_job;
+int crfconv_bn_eval_coef_jobs(const crf_bn_coef_job* jobs, int njobs, crf_stream_t stream);
 /* crfconv_pointconv_combine(f) + crfconv_linear_forward(f->out, W) in one launch (row-streaming form; Ci -> Co = 8 -> 32, 16 -> 64: the
  * fine-level lin_out widths, crfconv_linear_forward_uv_supported). */
 int crfconv_linear_forward_uv_supported(int Ci, int Co);
