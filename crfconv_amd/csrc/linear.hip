@@ -543,7 +543,7 @@ extern "C" int crfconv_reduce_jobs(const crf_reduce_job* jobs, int njobs, crf_st
     return CRF_OK;
 }
 
-extern "C" int crfconv_reduce_jobs_f64(const crf_reduce64_job* jobs, int njobs, crf_stream_t stream);      // pointconv.hip
+// crfconv_reduce_jobs_f64 lives in pointconv.hip; the header declares it.
 // Both kinds of sums of a backward pass in ONE launch when each fits one table (96 float jobs, 32 float64 jobs): same results as the
 // two calls.  Larger batches: the two calls.
 extern "C" int crfconv_reduce_jobs_both(const crf_reduce_job* jobs, int njobs, const crf_reduce64_job* jobs64, int njobs64,
@@ -1861,7 +1861,7 @@ extern "C" int crfconv_mlp_backward_add(const float* gA, const float* Y, const f
 // mask(v; ref, s) = ref > 0 ? v : s v -- what crfconv_add_lrelu_backward(dX, X, ...) would make of crfconv_mlp_backward_add's dX in a
 // pass of its own (same float operations: bit-identical).  dX is then the join's g1.  Ci % 4 == 0.  dX_add == NULL (the alias had no
 // gradient): the plain product, then that pass in place.
-extern "C" int crfconv_add_lrelu_backward(const float* gout, const float* out, int64_t n, float slope, float* gin, crf_stream_t stream);
+// crfconv_add_lrelu_backward lives in pool.hip; the header declares it.
 extern "C" int crfconv_mlp_backward_add_mask(const float* gA, const float* Y, const float* X, const float* W, const float* coef,
                                              float slope, int64_t M, int Ci, int Co, const float* dX_add, float mask_slope, float* dX,
                                              float* dW, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,

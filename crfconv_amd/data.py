@@ -96,12 +96,11 @@ class MultiScaleData(Data):
                 if getattr(a, '_crf_tables', None):          # a table was derived from it: same buffers, new content
                     tables.extend((a, key[0]) for key in list(a._crf_tables))
         if pairs:
-            import ctypes
             from . import _lib
             from .graph import stream_ptr
             jobs = (_lib.CopyJob * len(pairs))(*[_lib.CopyJob(src.data_ptr(), dst.data_ptr(), dst.numel() * dst.element_size())
                                                  for dst, src in pairs])
-            _lib.call('crfconv_copy_jobs', ctypes.cast(jobs, ctypes.c_void_p), len(pairs), stream_ptr())
+            _lib.call('crfconv_copy_jobs', jobs, len(pairs), stream_ptr())
             for dst, _ in pairs:                           # written by a custom kernel: the version counters (table / moments
                 torch.autograd.graph.increment_version(dst)    # memos compare them) must say so
         from .graph import batched_reverse
@@ -180,9 +179,8 @@ def random_subsets_device(sizes, counts, seed, counter, outs, ranks=None):
         for t, c in zip(ranks, sizes):
             if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= c):
                 raise _lib.CrfConvError('random_subsets_device: ranks must be contiguous int32 device tensors of the level sizes')
-        r = ctypes.cast((ctypes.c_void_p * L)(*[t.data_ptr() for t in ranks]), ctypes.c_void_p)
-    _lib.call('crfconv_random_subsets', ctypes.cast(n, ctypes.c_void_p), ctypes.cast(s, ctypes.c_void_p),
-              ctypes.cast(o, ctypes.c_void_p), r, L, int(seed) & 0xFFFFFFFFFFFFFFFF, counter.data_ptr(), stream_ptr())
+        r = (ctypes.c_void_p * L)(*[t.data_ptr() for t in ranks])
+    _lib.call('crfconv_random_subsets', n, s, o, r, L, int(seed) & 0xFFFFFFFFFFFFFFFF, counter.data_ptr(), stream_ptr())
 
 
 _UP_WS = {}
@@ -267,8 +265,7 @@ def pick_rows(tensors, index, per_cloud):
         src = (ctypes.c_void_p * n)(*[t.data_ptr() for _, t in part])
         dst = (ctypes.c_void_p * n)(*[d.data_ptr() for d in dsts])
         rb = (ctypes.c_int * n)(*[t[0, 0].numel() * t.element_size() for _, t in part])
-        _lib.call('crfconv_gather_rows_batched', ctypes.cast(src, ctypes.c_void_p), ctypes.cast(dst, ctypes.c_void_p),
-                  ctypes.cast(rb, ctypes.c_void_p), n, ptr(index), 1 if per_cloud else 0, B, N, S, stream_ptr())
+        _lib.call('crfconv_gather_rows_batched', src, dst, rb, n, ptr(index), 1 if per_cloud else 0, B, N, S, stream_ptr())
         for (i, _), d in zip(part, dsts):
             out[i] = d
     return out

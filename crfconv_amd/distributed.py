@@ -33,12 +33,11 @@ def init_from_env(backend=None, use_gpu=True):
 
 def _copy_batched(dsts, srcs):
     """dsts[i].copy_(srcs[i]) for contiguous CUDA tensors of equal dtype: one library launch (crfconv_copy_jobs, graph.hip)."""
-    import ctypes
     from . import _lib
     from .graph import stream_ptr
     jobs = (_lib.CopyJob * len(dsts))(*[_lib.CopyJob(s_.data_ptr(), d.data_ptr(), d.numel() * d.element_size())
                                         for d, s_ in zip(dsts, srcs)])
-    _lib.call('crfconv_copy_jobs', ctypes.cast(jobs, ctypes.c_void_p), len(dsts), stream_ptr())
+    _lib.call('crfconv_copy_jobs', jobs, len(dsts), stream_ptr())
 
 
 class FlatGradAllReduce:
@@ -102,7 +101,7 @@ class FlatGradAllReduce:
         from .graph import ptr, stream_ptr
         words = ops.fail_word_ptrs(self.flat.device)
         arr = (ctypes.c_void_p * max(len(words), 1))(*words)
-        _lib.call('crfconv_sgd_guard_publish', ctypes.cast(arr, ctypes.c_void_p), len(words), ptr(self.guard), stream_ptr())
+        _lib.call('crfconv_sgd_guard_publish', arr, len(words), ptr(self.guard), stream_ptr())
 
     def _world(self):
         return dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1

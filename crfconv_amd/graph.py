@@ -17,7 +17,8 @@ _vp = _lib.ctypes.c_void_p
 
 def ptr(t):
     """The device address of `t` for a C-ABI pointer argument (None = NULL).  A plain int: every entry point has its ctypes argtypes
-    set (_lib.SIGNATURES), which take it as a pointer -- a c_void_p object per argument cost ~2 000 constructions per eager step."""
+    set (_lib.SIGNATURES, read from include/crfconv_amd.h), which take it as a pointer -- a c_void_p object per argument cost ~2 000
+    constructions per eager step.  Host arrays of job records or pointers are passed as the ctypes array itself."""
     return None if t is None else t.data_ptr()
 
 
@@ -239,29 +240,26 @@ class batched_reverse:
         moments, _BATCH['moments'] = _BATCH['moments'], []
         if exc_type is not None:
             return False
-        import ctypes
         lib = _lib.load()
         adr = lambda t: None if t is None else t.data_ptr()
         for i in range(0, len(narrow), 32):
             part = narrow[i:i + 32]
             arr = (_lib.NarrowJob * len(part))(*[_lib.NarrowJob(idx64.data_ptr(), t.B, t.n_tgt, t.K, t.n_src, 1, t.idx32.data_ptr(),
                                                                 adr(t.idx16), t._bad.data_ptr()) for t, idx64, _ in part])
-            _lib.call('crfconv_index_narrow_batched', ctypes.cast(arr, ctypes.c_void_p), len(part), stream_ptr())
+            _lib.call('crfconv_index_narrow_batched', arr, len(part), stream_ptr())
         for i in range(0, len(jobs), 32):
             part = jobs[i:i + 32]
             arr = (_lib.RevJob * len(part))(*[_lib.RevJob(t.idx32.data_ptr(), t.m_tgt * t.K, t.m_src, rp.data_ptr(), re.data_ptr())
                                               for t, rp, re in part])
-            p = ctypes.cast(arr, ctypes.c_void_p)
-            nbytes = lib.crfconv_reverse_csr_batched_workspace(p, len(part))
+            nbytes = lib.crfconv_reverse_csr_batched_workspace(arr, len(part))
             ws = torch.empty(nbytes, dtype=torch.uint8, device=part[0][0].idx32.device)
-            _lib.call('crfconv_reverse_csr_batched', p, len(part), ptr(ws), nbytes, stream_ptr())
+            _lib.call('crfconv_reverse_csr_batched', arr, len(part), ptr(ws), nbytes, stream_ptr())
         for i in range(0, len(moments), 16):
             part = moments[i:i + 16]
             arr = (_lib.MomentsJob * len(part))(*[entry.batch_job(t) for entry, t in part])
-            p = ctypes.cast(arr, ctypes.c_void_p)
-            nbytes = lib.crfconv_pointconv_moments_batched_workspace(p, len(part))
+            nbytes = lib.crfconv_pointconv_moments_batched_workspace(arr, len(part))
             ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=part[0][1].idx32.device)
-            _lib.call('crfconv_pointconv_moments_batched', p, len(part), ptr(ws), nbytes, stream_ptr())
+            _lib.call('crfconv_pointconv_moments_batched', arr, len(part), ptr(ws), nbytes, stream_ptr())
             for entry, _ in part:
                 entry.mark_fresh()
         checks = [t for t, _, check in narrow if check]

@@ -185,11 +185,11 @@ def _flush_mlp_dw():
         if mats and state.dw_hosts_mats:
             arguments, install, _ = mats.pop(0)
             arrays, keep = arguments()
-            _lib.call('crfconv_mlp_dw_jobs_hosting', ctypes.cast(table, ctypes.c_void_p), len(jobs), *arrays, st)
+            _lib.call('crfconv_mlp_dw_jobs_hosting', table, len(jobs), *arrays, st)
             del keep
             install()
         else:
-            _lib.call('crfconv_mlp_dw_jobs', ctypes.cast(table, ctypes.c_void_p), len(jobs), st)
+            _lib.call('crfconv_mlp_dw_jobs', table, len(jobs), st)
         for _, _, (prm, gr, direct) in jobs:
             _install_grad(prm, gr, direct)
     for arguments, install, _ in mats:
@@ -220,7 +220,7 @@ def _flush_fold1_bwd():
     if not folds:
         return
     table = (_lib.Fold1BwdJob * len(folds))(*[f[0] for f in folds])
-    _lib.call('crfconv_pointconv_fold1_bwd_batched', ctypes.cast(table, ctypes.c_void_p), len(folds), stream_ptr())
+    _lib.call('crfconv_pointconv_fold1_bwd_batched', table, len(folds), stream_ptr())
     for _, _, installs in folds:
         for prm, gr, direct in installs:
             _install_grad(prm, gr, direct)
@@ -252,7 +252,7 @@ def _flush_pc_wide():
                                        c[0].data_ptr(), c[1].data_ptr(), c[2].data_ptr(), pw.data_ptr(), pa.data_ptr()))
             keep_m.append((w, pw, pa, nb))
         arr = (_lib.PcWideJob * len(jobs))(*jobs)
-        _lib.call('crfconv_pointconv_wide_params_jobs', ctypes.cast(arr, ctypes.c_void_p), len(jobs), st)
+        _lib.call('crfconv_pointconv_wide_params_jobs', arr, len(jobs), st)
         for w, pw, pa, nb in keep_m:
             d = w['d']
             _DEFER['jobs'].append((w['pW2'], None, pw, nb, d, d))          # dW2 = sum of the [d, d] slabs, installed with every other weight gradient
@@ -276,13 +276,13 @@ def _flush_pc_wide():
         a1s.append(_lib.PcA1Job(gw.data_ptr(), h1.data_ptr(), rel.data_ptr(), E, d, float(w['slope']), aws.data_ptr(), abytes))
         keep.append((w, h1, gh2, rel, gw, aws))
     arr = (_lib.PcDumpJob * len(dumps))(*dumps)
-    _lib.call('crfconv_pointconv_bwd_dump_jobs', ctypes.cast(arr, ctypes.c_void_p), len(dumps), st)
+    _lib.call('crfconv_pointconv_bwd_dump_jobs', arr, len(dumps), st)
     for w, h1, gh2, rel, gw, aws in keep:
         _defer_weight_grad(gh2, h1, (w['pW2'], None), False)          # (late mode implies the parameter is deferrable)
     arr = (_lib.GemmJob * len(gemms))(*gemms)
-    _lib.call('crfconv_gemm_jobs', ctypes.cast(arr, ctypes.c_void_p), len(gemms), st)
+    _lib.call('crfconv_gemm_jobs', arr, len(gemms), st)
     arr = (_lib.PcA1Job * len(a1s))(*a1s)
-    _lib.call('crfconv_pointconv_bwd_a1_jobs', ctypes.cast(arr, ctypes.c_void_p), len(a1s), st)
+    _lib.call('crfconv_pointconv_bwd_a1_jobs', arr, len(a1s), st)
     for w, h1, gh2, rel, gw, aws in keep:
         d, E = w['d'], w['m_tgt'] * w['K']
         _defer_reduce64((aws.data_ptr() + 255) & ~255, False, lib.crfconv_pointconv_bwd_a1_nblk(E, d), 4 * d, w['dA1b1'], (aws, gw, h1, rel))
@@ -296,14 +296,14 @@ def _flush_weight_grads():
         # longest jobs first: their workgroups start first (the backward queues the fine levels -- the long jobs -- last)
         partials.sort(key=lambda e: -(e[0].M * e[0].Co * e[0].Ci))
         arr = (_lib.WgradJob * len(partials))(*[j for j, _ in partials])
-        _lib.call('crfconv_linear_wgrad_partial_jobs', ctypes.cast(arr, ctypes.c_void_p), len(partials), stream_ptr())
+        _lib.call('crfconv_linear_wgrad_partial_jobs', arr, len(partials), stream_ptr())
     arr64, n64, keep64 = _take_red64()
     tns, _DEFER['tn'] = _DEFER.get('tn', []), []
     late_calls, _DEFER['late_calls'] = _DEFER.get('late_calls', []), []
     st = stream_ptr()
     if not jobs and not tns:
         if n64:
-            _lib.call('crfconv_reduce_jobs_f64', ctypes.cast(arr64, ctypes.c_void_p), n64, st)
+            _lib.call('crfconv_reduce_jobs_f64', arr64, n64, st)
         _flush_fold1_bwd()
         _flush_mlp_dw()
         for fn, _ in late_calls:
@@ -348,7 +348,7 @@ def _flush_weight_grads():
             installs.append((b, tb, db))
             n += 1
     # every sum of the pass -- the float weight-gradient slabs and the PointConv layers' float64 slabs -- in ONE launch
-    _lib.call('crfconv_reduce_jobs_both', ctypes.cast(table, ctypes.c_void_p), n, None if not n64 else ctypes.cast(arr64, ctypes.c_void_p), n64, st)
+    _lib.call('crfconv_reduce_jobs_both', table, n, None if not n64 else arr64, n64, st)
     del keep64
     _flush_fold1_bwd()                                  # reads the float64 sums
     _flush_mlp_dw()

@@ -1,5 +1,4 @@
 """Per-point Linear and the weight gradient of a plain product, BatchNorm step counters, BatchNorm (+ LeakyReLU)."""
-import ctypes
 
 import torch
 
@@ -282,7 +281,7 @@ def bn_eval_coefs(bns, out=None):
         jb.eps, jb.C, jb.coef = float(bn.eps), C, ptr(view)
         views.append(view)
         off += 4 * C
-    _lib.call('crfconv_bn_eval_coef_jobs', ctypes.cast(jobs, ctypes.c_void_p), len(bns), stream_ptr())
+    _lib.call('crfconv_bn_eval_coef_jobs', jobs, len(bns), stream_ptr())
     return out, views
 
 

@@ -437,9 +437,9 @@ def _small_bwd_jobs(jobs, n, dev, st):
     its tile-sum workgroups (crfconv_mlp_small_backward_jobs_one_launch), or -- state.small_bwd_one_launch off, or after a wait inside
     a one-launch kernel has ever given up (check_gridsync) -- the two launches.  Bit-identical results."""
     if state.small_bwd_one_launch and not state.small_mlp_disabled:
-        _lib.call('crfconv_mlp_small_backward_jobs_one_launch', ctypes.cast(jobs, ctypes.c_void_p), n, ptr(_ticket(dev)), ptr(gridsync_ws(dev)), st)
+        _lib.call('crfconv_mlp_small_backward_jobs_one_launch', jobs, n, ptr(_ticket(dev)), ptr(gridsync_ws(dev)), st)
     else:
-        _lib.call('crfconv_mlp_small_backward_jobs', ctypes.cast(jobs, ctypes.c_void_p), n, ptr(_ticket(dev)), st)
+        _lib.call('crfconv_mlp_small_backward_jobs', jobs, n, ptr(_ticket(dev)), st)
 
 
 def _mlp_bwd_jobs(blocks):
@@ -684,8 +684,8 @@ class _MLPSmallGroup(torch.autograd.Function):
             if fork:
                 outs.append(x_in)
             tmp.append((rec, g, b))                    # alive until the launches below are queued
-        _lib.call('crfconv_gemm_stats_jobs', ctypes.cast(gs, ctypes.c_void_p), n, st)
-        _lib.call('crfconv_bn_apply_from_records_jobs', ctypes.cast(ba, ctypes.c_void_p), n, st)
+        _lib.call('crfconv_gemm_stats_jobs', gs, n, st)
+        _lib.call('crfconv_bn_apply_from_records_jobs', ba, n, st)
         del tmp
         ctx.n, ctx.prm, ctx.slopes, ctx.forks, ctx.shared = n, prm, slopes, forks, bool(shared)
         ctx.mask_slope = _take_mask(mask, bool(shared) and n >= 2 and forks[0] and ctx.needs_input_grad[2])

@@ -325,7 +325,7 @@ def point_conv_prefold(layers, training, momentum=0.1):
         out.append(pre)
         o += d
     table_ = (_lib.Fold1Job * len(jobs))(*jobs)
-    _lib.call('crfconv_pointconv_fold1_batched', ctypes.cast(table_, ctypes.c_void_p), len(jobs), stream_ptr())
+    _lib.call('crfconv_pointconv_fold1_batched', table_, len(jobs), stream_ptr())
     return out
 
 

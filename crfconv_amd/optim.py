@@ -122,7 +122,7 @@ class FlatSGD(torch.optim.Optimizer):
         arr, nwords = _guard_words(self.flat.device)
         guard = getattr(self.bucket, 'guard', None)
         _lib.call('crfconv_sgd_step_guarded_all', ptr(self.flat), ptr(self.bucket.flat), ptr(self.buf), self.flat.numel(),
-                  ptr(self._hyper), 1 if g['nesterov'] else 0, 1 if first else 0, ctypes.cast(arr, ctypes.c_void_p), nwords,
+                  ptr(self._hyper), 1 if g['nesterov'] else 0, 1 if first else 0, arr, nwords,
                   ptr(guard), stream_ptr())   # zero buffer: mu * 0 + g = g
         self.steps += 1
         if not capturing and self.check_every > 0 and self.steps % self.check_every == 0:
@@ -253,7 +253,7 @@ class FlatAdam(torch.optim.Optimizer):
         _lib.call('crfconv_adam_step', ptr(self.flat), ptr(self.bucket.flat), ptr(self.exp_avg), ptr(self.exp_avg_sq),
                   ptr(self.max_exp_avg_sq), self.flat.numel(), ptr(self._hyper), ptr(self.t), ptr(self._coef), ptr(self.grad_norm),
                   1 if g['decoupled_weight_decay'] else 0, 1 if clip else 0, ptr(self._ws), self._ws.numel() * 8 if clip else 0,
-                  ctypes.cast(arr, ctypes.c_void_p), nwords, ptr(getattr(self.bucket, 'guard', None)), stream_ptr())
+                  arr, nwords, ptr(getattr(self.bucket, 'guard', None)), stream_ptr())
         if not capturing:                                    # (a captured step is counted by the device word alone)
             self.steps += 1
             if self.check_every > 0 and self.steps % self.check_every == 0:

@@ -20,6 +20,18 @@
  * message (thread-local).  Device entry points only enqueue work on `stream`; they never
  * allocate or synchronise unless their comment says so (workspace is caller-provided), so they
  * can be captured into a hipGraph.
+ *
+ * This file is MACHINE-READ: crfconv_amd/_lib.py derives the ctypes signature of every function and one ctypes.Structure per
+ * record from it at import (parse_header), and refuses text outside this dialect:
+ *   - comments of both kinds, preprocessor lines, the extern "C" guard;
+ *   - typedef void* crf_stream_t;
+ *   - one anonymous enum (read over);
+ *   - typedef struct [tag] { ... } crf_name;  fields are scalars or pointers, several declarators per type allowed
+ *     (float deg_lo, deg_hi;);
+ *   - prototypes whose parameters are named scalars, pointers of any depth and constness, or crf_stream_t; they return a scalar
+ *     or const char*.
+ * Scalars: int, unsigned, int32_t, uint32_t, int64_t, uint64_t, size_t, float, double.  Every pointer and crf_stream_t is a void*
+ * to Python.  No arrays, bit fields, nested or by-value records, function pointers or macros that expand to declarations.
  */
 #ifndef CRFCONV_AMD_H
 #define CRFCONV_AMD_H
