@@ -1,6 +1,8 @@
 // The forward of the CRF layers' two loop-invariant matrices as a device function over caller-provided LDS, so that its workgroups can
-// run as a launch of their own (linear.hip: crf_matrices_kernel / crf_matrices_batched_kernel) or ride along in a long launch whose
-// inputs do not depend on them (pointconv.hip: the first PointConv's statistics pass, crfconv_pointconv_uvstats_hosting).
+// run as a launch of their own (crf_matrices.hip: crf_matrices_kernel / crf_matrices_batched_kernel) or ride along in a long launch whose
+// inputs do not depend on them (pointconv.hip: the first PointConv's statistics pass, crfconv_pointconv_uvstats_hosting).  The same for
+// the backward: crf_matrices_bwd_slab and its job table (crf_matrices_bwd_jobs) serve crf_matrices.hip's own launches and the
+// end-of-pass dW launch that carries the slabs (mlp_bwd.hip: mlp_dw_jobs_hosting_kernel).
 #pragma once
 #include "common.hpp"
 
@@ -109,4 +111,59 @@ struct CrfMatJobs {
     int slab_base[CM_MAX + 1];                     // backward: prefix of ceil(H / CMB_ROWS) -- first workgroup of each layer
 };
 
+// dc from dQ and dP (either may be NULL = zero).  With D = dQ - dP (P = I - Q), M = I + c^T c:
+//   dM = -Q^T D Q^T,   dc = c (dM + dM^T) = -c (S + S^T),   S = Q^T D Q^T.
+// Q is symmetric (the inverse of a symmetric matrix; its float rounding included, to ~1e-8), so S + S^T = Q (D + D^T) Q and
+//   dc = -((c Q) (D + D^T)) Q
+// is a chain of three products in which every ROW of the result depends on the same row of c only: a workgroup takes a slab
+// of CMB_ROWS rows through all three products without ever meeting another workgroup (H / CMB_ROWS workgroups per layer,
+// float64 accumulation, operands as float in LDS).  The one-workgroup form (T = Q^T D, S = T Q^T, c (S + S^T): three full
+// H^3 float64 products on 1024 threads of ONE CU, 35 us for the four layers of PointConvBig) was instruction-bound.
+constexpr int CMB_ROWS = 8, CMB_BLOCK = CMB_ROWS * 64;
+__device__ __forceinline__ void crf_matrices_bwd_slab(const float* __restrict__ cmat, const float* __restrict__ Q,
+                                                      const float* __restrict__ dQ, const float* __restrict__ dP,
+                                                      int H, int row0, float* __restrict__ dc) {
+    __shared__ float s_q[64 * 65], s_d[64 * 65];
+    __shared__ double s_t[2][CMB_ROWS][65];
+    for (int e = threadIdx.x; e < H * H; e += (int)blockDim.x) {              // (a rider in a launch of larger workgroups: mlp_dw_jobs_hosting_kernel)
+        const int r = e / H, c = e % H;
+        s_q[r * 65 + c] = Q[e];
+        s_d[r * 65 + c] = (dQ ? dQ[e] : 0.f) - (dP ? dP[e] : 0.f);            // D
+    }
+    const int r = (threadIdx.x >> 6) & (CMB_ROWS - 1), j = threadIdx.x & 63, row = row0 + r;
+    const bool live = (int)threadIdx.x < CMB_BLOCK && row < H && j < H;
+    if (live) s_t[0][r][j] = (double)cmat[row * H + j];
+    __syncthreads();
+    double acc = 0.0;
+    if (live)
+        for (int k = 0; k < H; ++k) acc += s_t[0][r][k] * (double)s_q[k * 65 + j];                 // (c Q)[row][j]
+    if (live) s_t[1][r][j] = acc;
+    __syncthreads();
+    acc = 0.0;
+    if (live)
+        for (int k = 0; k < H; ++k) acc += s_t[1][r][k] * ((double)s_d[k * 65 + j] + (double)s_d[j * 65 + k]);   // . (D + D^T)
+    if (live) s_t[0][r][j] = acc;
+    __syncthreads();
+    acc = 0.0;
+    if (live) {
+        for (int k = 0; k < H; ++k) acc += s_t[0][r][k] * (double)s_q[k * 65 + j];                 // . Q
+        dc[row * H + j] = (float)(-acc);
+    }
+}
+
 }  // namespace crf
+
+// host side: the backward's job table from the entry points' arrays, checked (nslab = workgroups of the slabs)
+static int crf_matrices_bwd_jobs(const float* const* c, const float* const* Q, const float* const* gQ, const float* const* gP, const int* H, int n,
+                                 float* const* dc, crf::CrfMatJobs& j, int& nslab) {
+    CRF_REQUIRE(c && Q && gQ && gP && H && dc && n >= 1 && n <= crf::CM_MAX, CRF_ERR_ARG, "null pointer or n=%d outside [1, %d]", n, crf::CM_MAX);
+    j = crf::CrfMatJobs();
+    for (int i = 0; i < n; ++i) {
+        CRF_REQUIRE(c[i] && Q[i] && dc[i] && H[i] >= 1 && H[i] <= 64, CRF_ERR_ARG, "job %d: null pointer or H=%d outside [1, 64]", i, H[i]);
+        j.c[i] = c[i]; j.Q_in[i] = Q[i]; j.gQ[i] = gQ[i]; j.gP[i] = gP[i]; j.dc[i] = dc[i]; j.H[i] = H[i];
+        j.slab_base[i + 1] = j.slab_base[i] + (H[i] + crf::CMB_ROWS - 1) / crf::CMB_ROWS;
+    }
+    nslab = j.slab_base[n];
+    for (int i = n; i < crf::CM_MAX; ++i) j.slab_base[i + 1] = 0x7fffffff;      // (never reached by a block index)
+    return CRF_OK;
+}

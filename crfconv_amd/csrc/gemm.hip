@@ -1,6 +1,6 @@
 // Small dense products of the per-point layers on the coarse levels:  C [M, N] = A [M, K] · B (+ bias [N]) (+ addend [M, N])
 //
-// The shapes the row-streaming kernels of linear.hip do not take: the coarse-level forward (models/common.py:30,35 -- MLP.lin
+// The shapes the row-streaming kernels of linear_fwd.hpp do not take: the coarse-level forward (models/common.py:30,35 -- MLP.lin
 // at 640 .. 10 240 rows, up to 512 channels) and every dX = gY · W of the MLP / ResNet-block backward (autograd of the same
 // lines), plus the per-edge g_h1 = g_h2 · W2 of the wide PointConv layers (models/point_conv_big.py:45-47).  M is small
 // (10^2 .. 10^5), K and N are 32 .. 512: a few hundred MFLOP each, bounded by dependent memory round trips and by how many

@@ -7,7 +7,7 @@
 // linear_fwd_kernel, so y is bit-identical in every pass) and keeps everything 128-wide in registers:
 //
 //   forward   head_stats_kernel                           BatchNorm statistic records of y (the tuples of linear_fwd_kernel), nothing stored
-//             crfconv_bn_coef_from_nrecords (linear.hip)  coefficients + running statistics
+//             crfconv_bn_coef_from_nrecords (bn_records.hip)  coefficients + running statistics
 //             head_fwd_kernel                             y -> lrelu(a y + b) -> mask -> logits = h W2^T + b2; one mask WORD per
 //                                                         (row, lane group) = the 32 channels a lane holds (2.6 MB instead of h)
 //   backward  head_bwd_p1_kernel    y, gh = g W2 recomputed in the TRANSPOSED accumulator layout (rows in registers, channels on
@@ -578,7 +578,7 @@ __host__ __device__ inline HeadOffsets head_offsets(int Ci) {
 
 // ------------------------------------------------------------------------------------------------------------ dX
 // dX [M, Ci] = gY W1,  gY = alpha lrelu'(a y + b) mask scale gh + bet y + del with the coefficients of the fused MLP backward
-// (linear.hip, mlp_channel_part) derived here from the totals s1, s2.
+// (mlp_bwd.hip, mlp_channel_part) derived here from the totals s1, s2.
 template <int NCH>
 __global__ __launch_bounds__(HD_BLOCK, 2) void head_bwd_dx_kernel(const float* __restrict__ G, const float* __restrict__ X,
                                                                   const float* __restrict__ W1, const float* __restrict__ W2,

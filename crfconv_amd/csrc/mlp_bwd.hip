@@ -1,0 +1,570 @@
+// The fused backward of one MLP block, Linear -> BatchNorm -> LeakyReLU, in two passes over the activations (the derivation
+// stands above mlp_channel_part): the streaming pass mlp_bwd_p1_kernel, its finalize, the batched end-of-pass dW launches
+// (mlp_dw_jobs_kernel, and the form that carries the CRF matrices' backward slabs of crf_matrices_body.hpp), and the dX product,
+// which is linear_fwd_kernel<.., PRO = true> of linear_fwd.hpp -- this unit instantiates those forms.
+#include "common.hpp"
+#include "gridsync.hpp"
+#include "wgrad_body.hpp"
+#include "crf_matrices_body.hpp"
+#include "linear_fwd.hpp"
+
+namespace crf {
+
+// ====================================================================== backward of Linear -> BatchNorm -> LeakyReLU
+// (models/common.py:34-40, training mode) in TWO passes over the activations instead of four.  With
+//   g1 = gA * lrelu'(a y + b),   yh = (y - mean) rstd,   dbeta = sum g1,   dgamma = sum g1 yh,
+//   gY = a (g1 - dbeta / M - yh dgamma / M),   dX = gY W,   dW = gY^T X
+// the weight gradient expands to   dW = diag(a) [ G1^T X - (dbeta / M) (1^T X) - diag(dgamma / M) Yh^T X ]:
+// G1^T X, Yh^T X, 1^T X, sum g1 and sum g1 yh are all plain row reductions, so ONE streaming pass over (gA, Y, X)
+// produces every partial (mlp_bwd_p1_kernel: two MFMA accumulator sets sharing the X fragment); a small finalize turns
+// them into dgamma, dbeta, dW and the per-channel coefficients of gY; and dX = gY W is one more pass in which gY is
+// formed in registers from (gA, Y) while loading the operand (linear_fwd_kernel<.., true>).  The step-by-step form
+// (bn_bwd_reduce -> finalize -> bn_bwd_apply -> dX -> wgrad) reads or writes nine [M, C] arrays; this one six, with
+// three launches instead of five, and gY never reaches memory.  (Two launches where the last workgroup of the first pass does the
+// finalize's channel part: crfconv_mlp_backward's ticket.)
+
+// dgamma, dbeta of channel c and the coefficients of  gY = alpha * lrelu'(a y + b) * gA + bet * y + del  (bcoef [5][Co] =
+// a | b | alpha | bet | del) from the two channel sums s1 = sum g1, s2 = sum g1 yh
+__device__ __forceinline__ void mlp_channel_part(int c, double s1, double s2, const float* __restrict__ coef, int64_t M, int Co,
+                                                 float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ bcoef) {
+    dbeta[c] = (float)s1;
+    dgamma[c] = (float)s2;
+    const double a = coef[c], mu = coef[2 * Co + c], rs = coef[3 * Co + c];
+    const double c2 = s1 / (double)M, c3 = s2 / (double)M;
+    bcoef[c] = coef[c];
+    bcoef[Co + c] = coef[Co + c];
+    bcoef[2 * Co + c] = (float)a;
+    bcoef[3 * Co + c] = (float)(-a * c3 * rs);
+    bcoef[4 * Co + c] = (float)(-a * c2 + a * c3 * rs * mu);
+}
+
+template <int TCO, int TCI>
+__global__ __launch_bounds__(WG_BLOCK) void mlp_bwd_p1_kernel(const float* __restrict__ GA, const float* __restrict__ Y,
+                                                              const float* __restrict__ X,
+                                                              const float* __restrict__ X2, int split /*X = [X | X2] at column split (X2 may be null)*/,
+                                                              const float* __restrict__ coef /*[4][Co]: a, b, mean, rstd*/,
+                                                              float slope, int64_t M, int Co, int Ci, int rows_per_block,
+                                                              float* __restrict__ PA /*[nblk][Co][Ci]*/,
+                                                              float* __restrict__ PB /*[nblk][Co][Ci]*/,
+                                                              float* __restrict__ PG /*[nblk][2][Co]*/,
+                                                              float* __restrict__ PX /*[nblk][Ci]*/,
+                                                              unsigned* __restrict__ ticket /*null: mlp_bwd_finalize_kernel does the channel part*/,
+                                                              float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                              float* __restrict__ bcoef) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int co_base = blockIdx.y * 16 * TCO, ci_base = blockIdx.z * 16 * TCI;
+    const int kk = lane >> 4, cc = lane & 15;
+    f32x4 accA[TCO][TCI], accB[TCO][TCI];
+#pragma unroll
+    for (int a = 0; a < TCO; ++a)
+#pragma unroll
+        for (int b = 0; b < TCI; ++b) { accA[a][b] = f32x4{0.f, 0.f, 0.f, 0.f}; accB[a][b] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    float ca[TCO], cb[TCO], cm[TCO], cr[TCO], sg[TCO], sgy[TCO], sx[TCI];
+#pragma unroll
+    for (int a = 0; a < TCO; ++a) {
+        const int co = co_base + 16 * a + cc;
+        const bool ok = co < Co;
+        ca[a] = ok ? coef[co] : 0.f;
+        cb[a] = ok ? coef[Co + co] : 0.f;
+        cm[a] = ok ? coef[2 * Co + co] : 0.f;
+        cr[a] = ok ? coef[3 * Co + co] : 0.f;
+        sg[a] = 0.f;
+        sgy[a] = 0.f;
+    }
+#pragma unroll
+    for (int b = 0; b < TCI; ++b) sx[b] = 0.f;
+
+    const int64_t row_begin = (int64_t)blockIdx.x * rows_per_block;
+    const int64_t row_end = row_begin + rows_per_block < M ? row_begin + rows_per_block : M;
+#ifndef P1_PREFETCH_
+#define P1_PREFETCH_ 0
+#endif
+    struct Frag { float gv[4][TCO], yv[4][TCO], bv[4][TCI]; };
+    auto load = [&](int64_t r0, Frag& f) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int64_t r = r0 + 4 * u + kk;
+            const bool rv = r < row_end;
+#pragma unroll
+            for (int a = 0; a < TCO; ++a) {
+                const int co = co_base + 16 * a + cc;
+                const bool ok = rv && co < Co;
+                f.gv[u][a] = ok ? GA[r * Co + co] : 0.f;
+                f.yv[u][a] = ok ? Y[r * Co + co] : cm[a];          // yh = 0 on padding
+            }
+#pragma unroll
+            for (int b = 0; b < TCI; ++b) {
+                const int ci = ci_base + 16 * b + cc;
+                float xv = 0.f;
+                if (rv && ci < Ci) xv = (X2 == nullptr || ci < split) ? X[r * (X2 ? split : Ci) + ci] : X2[r * (Ci - split) + (ci - split)];
+                f.bv[u][b] = xv;
+            }
+        }
+    };
+    auto compute = [&](const Frag& f) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+#pragma unroll
+            for (int b = 0; b < TCI; ++b) sx[b] += f.bv[u][b];
+#pragma unroll
+            for (int a = 0; a < TCO; ++a) {
+                const float g1 = f.gv[u][a] * (fmaf(ca[a], f.yv[u][a], cb[a]) > 0.f ? 1.f : slope);
+                const float yh = (f.yv[u][a] - cm[a]) * cr[a];
+                sg[a] += g1;
+                sgy[a] = fmaf(g1, yh, sgy[a]);
+#pragma unroll
+                for (int b = 0; b < TCI; ++b) {
+                    accA[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(g1, f.bv[u][b], accA[a][b], 0, 0, 0);
+                    accB[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(yh, f.bv[u][b], accB[a][b], 0, 0, 0);
+                }
+            }
+        }
+    };
+    if constexpr (P1_PREFETCH_ != 0) {
+        // the next 16-row group's fragments are requested before this group's products (rows past the slice load nothing)
+        Frag cur, nxt;
+        load(row_begin + 16 * wave, cur);
+        for (int64_t r0 = row_begin + 16 * wave; r0 < row_end; r0 += 16 * WG_WAVES) {
+            load(r0 + 16 * WG_WAVES, nxt);
+            compute(cur);
+            cur = nxt;
+        }
+    } else {
+        for (int64_t r0 = row_begin + 16 * wave; r0 < row_end; r0 += 16 * WG_WAVES) {
+            Frag f;
+            load(r0, f);
+            compute(f);
+        }
+    }
+    // C/D layout of 16x16x4: col = lane & 15 (j = ci), row = 4 * (lane >> 4) + reg (i = co)
+    __shared__ __attribute__((aligned(16))) float s_red[WG_WAVES][TCO * TCI * 256];
+    __shared__ float s_v[WG_WAVES][(2 * TCO + TCI) * 16];
+    const int64_t pb = (int64_t)blockIdx.x;
+    for (int pass = 0; pass < 2; ++pass) {
+        if (pass) __syncthreads();
+#pragma unroll
+        for (int a = 0; a < TCO; ++a)
+#pragma unroll
+            for (int b = 0; b < TCI; ++b)
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+                    s_red[wave][(a * TCI + b) * 256 + (4 * kk + g) * 16 + cc] = pass ? accB[a][b][g] : accA[a][b][g];
+        if (pass == 0) {
+            // per-channel sums: lanes with the same cc over the 4 k-groups
+#pragma unroll
+            for (int a = 0; a < TCO; ++a) {
+                float t1 = sg[a], t2 = sgy[a];
+                t1 += __shfl_xor(t1, 16, WAVE); t1 += __shfl_xor(t1, 32, WAVE);
+                t2 += __shfl_xor(t2, 16, WAVE); t2 += __shfl_xor(t2, 32, WAVE);
+                if (kk == 0) { s_v[wave][a * 16 + cc] = t1; s_v[wave][(TCO + a) * 16 + cc] = t2; }
+            }
+#pragma unroll
+            for (int b = 0; b < TCI; ++b) {
+                float t1 = sx[b];
+                t1 += __shfl_xor(t1, 16, WAVE); t1 += __shfl_xor(t1, 32, WAVE);
+                if (kk == 0) s_v[wave][(2 * TCO + b) * 16 + cc] = t1;
+            }
+        }
+        __syncthreads();
+        float* dst = pass ? PB : PA;
+        for (int t = threadIdx.x; t < TCO * TCI * 256; t += WG_BLOCK) {
+            float v = 0.f;
+#pragma unroll
+            for (int w = 0; w < WG_WAVES; ++w) v += s_red[w][t];
+            const int tile = t >> 8, a = tile / TCI, b = tile % TCI, i = (t >> 4) & 15, j = t & 15;
+            const int co = co_base + 16 * a + i, ci = ci_base + 16 * b + j;
+            if (co < Co && ci < Ci) dst[(pb * Co + co) * Ci + ci] = v;
+        }
+    }
+    const __amdgpu_buffer_rsrc_t pgr = make_rsrc(PG, (int)gridDim.x * 2 * Co * 4);
+    for (int t = threadIdx.x; t < (2 * TCO + TCI) * 16; t += WG_BLOCK) {
+        float v = 0.f;
+#pragma unroll
+        for (int w = 0; w < WG_WAVES; ++w) v += s_v[w][t];
+        const int grp = t >> 4, c16 = t & 15;
+        if (grp < 2 * TCO) {                                   // sum g1 | sum g1 yh: slabs of ci-slab 0 only
+            const int which = grp / TCO, co = co_base + 16 * (grp % TCO) + c16;
+            if (blockIdx.z == 0 && co < Co) st1_sc1(pgr, (((int)pb * 2 + which) * Co + co) * 4, v);   // write-through: summed in this launch
+        } else {                                               // column sums of X: slabs of co-slab 0 only
+            const int ci = ci_base + 16 * (grp - 2 * TCO) + c16;
+            if (blockIdx.y == 0 && ci < Ci) PX[pb * Ci + ci] = v;
+        }
+    }
+    // The channel part of the finalize (dgamma, dbeta, the coefficients of gY for the dX pass) by the LAST workgroup of this launch
+    // to finish (gridsync.hpp): the launch between the two passes of the block's backward disappears.  2 Co <= WG_BLOCK slots.
+    constexpr bool ALIAS = TCO * TCI >= 3;                     // the 10 KB of sums inside s_red (everybody has left it by then)
+    __shared__ double s_own[ALIAS ? 1 : 5 * WG_BLOCK];
+    __shared__ int s_flag;
+    if (ticket == nullptr || !last_workgroup(ticket, gridDim.x * gridDim.y * gridDim.z, &s_flag)) return;
+    double* s_buf = ALIAS ? reinterpret_cast<double*>(&s_red[0][0]) : s_own;
+    double* s_tot = s_buf + 4 * WG_BLOCK;
+    sum_partial_rows_f64<WG_BLOCK>(pgr, (int)gridDim.x, 2 * Co, s_buf, s_tot);
+    if ((int)threadIdx.x < Co) mlp_channel_part(threadIdx.x, s_tot[threadIdx.x], s_tot[Co + threadIdx.x], coef, M, Co, dgamma, dbeta, bcoef);
+}
+
+// dW slots [64 block, 64 block + 64) of one MLP block's backward from its partial slabs (see mlp_bwd_finalize_kernel): shared by
+// the per-layer finalize launch and the batched launch over all layers of a backward pass (mlp_dw_jobs_kernel).
+constexpr int MF_BLOCK = 1024, MF_WAVES = MF_BLOCK / WAVE;
+__device__ __forceinline__ void mlp_dw_slots(const float* __restrict__ PA, const float* __restrict__ PB,
+                                             const float* __restrict__ PG, const float* __restrict__ PX, int nblk,
+                                             const float* __restrict__ coef, int64_t M, int Co, int Ci, int block,
+                                             float* __restrict__ dW) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    // 64 slots per workgroup; the sixteen wavefronts split the slabs (b = w, w + 16, ..), four slabs of each of the five
+    // streams in flight per lane: a 512-slab reduction is eight dependent round trips (the 256-thread form
+    // measured 16.5 us per layer, more than the pass that produced the slabs)
+    __shared__ float s_part[MF_WAVES][5][64];
+    const int nslots = Co * Ci;
+    const int slot = block * 64 + lane;
+    const bool ok = slot < nslots;
+    const int sl = ok ? slot : nslots - 1;
+    const int co = sl / Ci, ci = sl - co * Ci;
+    float a0 = 0.f, b0 = 0.f, x0 = 0.f, g1 = 0.f, g2 = 0.f;
+    // four slabs of each stream in flight (20 loads per lane; eight spill at the 128-register budget of a 1024-thread block)
+    const int64_t sa = (int64_t)MF_WAVES * Co * Ci, sx = (int64_t)MF_WAVES * Ci, sg = (int64_t)MF_WAVES * 2 * Co;
+    const float* pa = PA + ((int64_t)w * Co + co) * Ci + ci;
+    const float* pb = PB + ((int64_t)w * Co + co) * Ci + ci;
+    const float* px = PX + (int64_t)w * Ci + ci;
+    const float* pg = PG + (int64_t)w * 2 * Co + co;
+#pragma unroll 1
+    for (int b = w; b < nblk; b += 4 * MF_WAVES) {
+        float va[4], vb[4], vx[4], vg[4], vh[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const bool in = b + MF_WAVES * u < nblk;
+            va[u] = in ? pa[u * sa] : 0.f;
+            vb[u] = in ? pb[u * sa] : 0.f;
+            vx[u] = in ? px[u * sx] : 0.f;
+            vg[u] = in ? pg[u * sg] : 0.f;
+            vh[u] = in ? pg[u * sg + Co] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { a0 += va[u]; b0 += vb[u]; x0 += vx[u]; g1 += vg[u]; g2 += vh[u]; }
+        pa += 4 * sa; pb += 4 * sa; px += 4 * sx; pg += 4 * sg;
+    }
+    s_part[w][0][lane] = a0; s_part[w][1][lane] = b0; s_part[w][2][lane] = x0;
+    s_part[w][3][lane] = g1; s_part[w][4][lane] = g2;
+    __syncthreads();
+    if (w == 0 && ok) {
+        double A = 0.0, B = 0.0, Xs = 0.0, G1 = 0.0, G2 = 0.0;
+        for (int k = 0; k < MF_WAVES; ++k) {
+            A += s_part[k][0][lane]; B += s_part[k][1][lane]; Xs += s_part[k][2][lane];
+            G1 += s_part[k][3][lane]; G2 += s_part[k][4][lane];
+        }
+        const double a = coef[co], c2 = G1 / (double)M, c3 = G2 / (double)M;
+        dW[slot] = (float)(a * (A - c2 * Xs - c3 * B));
+    }
+}
+
+// Finalize of the pass above, ONE launch of two kinds of workgroups:
+//   blockIdx.x <  nw : 64 slots (co, ci) of dW = a [ sum A - c2 sum sx - c3 sum B ],  c2 = dbeta / M, c3 = dgamma / M
+//                      (each workgroup re-derives c2 / c3 of the one or two co rows it touches: no ordering between the
+//                      two kinds of workgroups is needed)
+//   blockIdx.x >= nw : four channels each: dgamma, dbeta and the coefficients of
+//                      gY = alpha * lrelu'(a y + b) * gA + bet * y + del   (bcoef [5][Co] = a | b | alpha | bet | del)
+__global__ __launch_bounds__(MF_BLOCK) void mlp_bwd_finalize_kernel(const float* __restrict__ PA, const float* __restrict__ PB,
+                                                                    const float* __restrict__ PG, const float* __restrict__ PX,
+                                                                    int nblk, const float* __restrict__ coef, int64_t M, int Co,
+                                                                    int Ci, int nw, float* __restrict__ dW,
+                                                                    float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                                    float* __restrict__ bcoef) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if ((int)blockIdx.x >= nw) {                               // one wavefront per channel
+        const int c = ((int)blockIdx.x - nw) * MF_WAVES + w;
+        if (c >= Co) return;
+        double s1 = 0.0, s2 = 0.0;
+        // eight slabs of both sums in flight per lane (nblk <= 512: ONE round trip; the rolled loop was eight dependent ones --
+        // this launch sits between the two passes of every MLP block's backward)
+        for (int b0 = lane; b0 < nblk; b0 += 8 * WAVE) {
+            float v1[8], v2[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int b = b0 + u * WAVE;
+                const bool in = b < nblk;
+                v1[u] = in ? PG[((int64_t)b * 2 + 0) * Co + c] : 0.f;
+                v2[u] = in ? PG[((int64_t)b * 2 + 1) * Co + c] : 0.f;
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) { s1 += (double)v1[u]; s2 += (double)v2[u]; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            s1 += __shfl_xor(s1, o, WAVE);
+            s2 += __shfl_xor(s2, o, WAVE);
+        }
+        if (lane == 0) mlp_channel_part(c, s1, s2, coef, M, Co, dgamma, dbeta, bcoef);
+        return;
+    }
+    mlp_dw_slots(PA, PB, PG, PX, nblk, coef, M, Co, Ci, (int)blockIdx.x, dW);
+}
+
+// The dW parts of ALL MLP blocks of a backward pass in ONE launch: nothing inside the pass reads a weight gradient, so the
+// per-layer finalize launch only does its channel part (dgamma, dbeta, the dX coefficients) and the slab reductions --
+// 32 launches of ~8 dependent round trips each -- run side by side at the end.  group_begin = prefix sum of ceil(Co Ci / 64).
+constexpr int MDW_MAX = 40;
+struct MlpDwTable {
+    const float* PA[MDW_MAX];
+    const float* PB[MDW_MAX];
+    const float* PG[MDW_MAX];
+    const float* PX[MDW_MAX];
+    const float* coef[MDW_MAX];
+    float* dW[MDW_MAX];
+    long long M[MDW_MAX];
+    int nblk[MDW_MAX], Co[MDW_MAX], Ci[MDW_MAX];
+    int group_begin[MDW_MAX + 1];
+    int njobs;
+};
+__global__ __launch_bounds__(MF_BLOCK) void mlp_dw_jobs_kernel(const MlpDwTable t) {
+    const int g = blockIdx.x;
+    int lo = 0, hi = t.njobs;                          // largest j with group_begin[j] <= g
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (t.group_begin[mid] <= g) lo = mid; else hi = mid;
+    }
+    mlp_dw_slots(t.PA[lo], t.PB[lo], t.PG[lo], t.PX[lo], t.nblk[lo], t.coef[lo], (int64_t)t.M[lo], t.Co[lo], t.Ci[lo],
+                 g - t.group_begin[lo], t.dW[lo]);
+}
+
+// mlp_dw_jobs_kernel CARRYING the slabs of crf_matrices_bwd_batched_kernel as its first n_side workgroups (round 6): both are
+// end-of-pass parameter work that nothing waits for; on its own the matrices' backward is a 13 us chain of three dependent float64
+// products on 15 workgroups.  A rider uses the first CMB_BLOCK threads of its (MF_BLOCK-thread) workgroup.
+static_assert(MF_BLOCK >= CMB_BLOCK, "a rider fits the host's workgroup");
+__global__ __launch_bounds__(MF_BLOCK) void mlp_dw_jobs_hosting_kernel(const MlpDwTable t, const CrfMatJobs j, const int n_side) {
+    if ((int)blockIdx.x < n_side) {
+        int b = 0;
+        while (b + 1 < CM_MAX && (int)blockIdx.x >= j.slab_base[b + 1]) ++b;
+        crf_matrices_bwd_slab(j.c[b], j.Q_in[b], j.gQ[b], j.gP[b], j.H[b], ((int)blockIdx.x - j.slab_base[b]) * CMB_ROWS, j.dc[b]);
+        return;
+    }
+    const int g = (int)blockIdx.x - n_side;
+    int lo = 0, hi = t.njobs;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (t.group_begin[mid] <= g) lo = mid; else hi = mid;
+    }
+    mlp_dw_slots(t.PA[lo], t.PB[lo], t.PG[lo], t.PX[lo], t.nblk[lo], t.coef[lo], (int64_t)t.M[lo], t.Co[lo], t.Ci[lo],
+                 g - t.group_begin[lo], t.dW[lo]);
+}
+
+// ---------------------------------------------------------------------- host side: plans, workspace layout, entry points
+struct MlpPlan {
+    int tco, tci, gy, gz, nblk, rows_per_block;
+};
+static MlpPlan mlp_plan(int64_t M, int Co, int Ci) {
+    MlpPlan p;
+    const int t_co = (Co + 15) / 16, t_ci = (Ci + 15) / 16;
+    p.tco = t_co >= 4 ? 4 : (t_co >= 2 ? 2 : 1);
+    p.tci = t_ci >= 4 ? 4 : (t_ci >= 2 ? 2 : 1);
+    if (p.tco * p.tci == 16) p.tci = 2;              // two accumulator sets: at most 8 tiles (64 registers) each
+    p.gy = (t_co + p.tco - 1) / p.tco;
+    p.gz = (t_ci + p.tci - 1) / p.tci;
+#ifndef MLP_P1_TARGET_
+#define MLP_P1_TARGET_ 512
+#endif
+    constexpr int target = MLP_P1_TARGET_;           // slices x column slabs per launch (256 / 1024 measured slower: DESIGN 9 C4)
+    int64_t slices = target / ((int64_t)p.gy * p.gz);
+    if (slices < 32) slices = 32;
+    int64_t rows = (M + slices - 1) / slices;
+    if (rows < 64) rows = 64;
+    rows = (rows + 63) / 64 * 64;
+    p.rows_per_block = (int)rows;
+    p.nblk = (int)((M + rows - 1) / rows);
+    return p;
+}
+static size_t mlp_ws_layout(int64_t M, int Co, int Ci, size_t off[5]) {
+    const MlpPlan p = mlp_plan(M, Co, Ci);
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    size_t o = 0;
+    off[0] = o; o = up(o + sizeof(float) * (size_t)p.nblk * Co * Ci);      // PA
+    off[1] = o; o = up(o + sizeof(float) * (size_t)p.nblk * Co * Ci);      // PB
+    off[2] = o; o = up(o + sizeof(float) * (size_t)p.nblk * 2 * Co);       // PG
+    off[3] = o; o = up(o + sizeof(float) * (size_t)p.nblk * Ci);           // PX
+    off[4] = o; o = up(o + sizeof(float) * 5 * (size_t)Co);                // prologue coefficients
+    return o;
+}
+}  // namespace crf
+
+using namespace crf;
+
+extern "C" size_t crfconv_ticket_bytes(void) { return sizeof(unsigned) * crf::LW_TICKET_WORDS; }
+
+extern "C" int crfconv_mlp_backward_supported(int64_t M, int Ci, int Co) {
+    if (!(M > 0 && Co % 4 == 0 && Ci >= 1 && Co >= 4 && Co <= 1024 && Ci <= 1024)) return 0;
+    // dX runs on linear_fwd_kernel<., true> with k = Co inputs and Ci outputs: its LDS must fit 64 KB
+    return lf_lds_bytes(Co, Ci, true) <= 64 * 1024 ? 1 : 0;
+}
+
+extern "C" size_t crfconv_mlp_backward_workspace(int64_t M, int Ci, int Co) {
+    if (M <= 0 || Co <= 0 || Ci <= 0) return 0;
+    size_t off[5];
+    return crf::mlp_ws_layout(M, Co, Ci, off) + 256;
+}
+
+static int mlp_backward_impl(const float* gA, const float* Y, const float* X, const float* Xb, int xsplit, const float* W,
+                             const float* coef, float slope, int64_t M, int Ci, int Co, float* dX, float* dXb, float* dW,
+                             float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, unsigned* ticket,
+                             crf_stream_t stream, const float* dX_add = nullptr, const float* mask_ref = nullptr,
+                             float mask_slope = 1.f) {
+    CRF_REQUIRE(gA && Y && X && W && coef && dgamma && dbeta && workspace, CRF_ERR_ARG, "null pointer");
+    CRF_REQUIRE(mask_ref == nullptr || (dX_add != nullptr && dX != nullptr && Ci % 4 == 0 && Co % 4 == 0), CRF_ERR_ARG,
+                "the masked dX takes an addend and widths that are multiples of 4 (Ci=%d Co=%d)", Ci, Co);
+    CRF_REQUIRE(dX_add == nullptr || dXb == nullptr, CRF_ERR_ARG, "dX_add is for the one-operand form");
+    CRF_REQUIRE(crfconv_mlp_backward_supported(M, Ci, Co) == 1, CRF_ERR_UNSUPPORTED, "shape M=%lld Ci=%d Co=%d not supported",
+                (long long)M, Ci, Co);
+    CRF_REQUIRE(workspace_bytes >= crfconv_mlp_backward_workspace(M, Ci, Co), CRF_ERR_WORKSPACE, "workspace too small");
+    hipStream_t st = crf::as_stream(stream);
+    char* base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
+    size_t off[5];
+    crf::mlp_ws_layout(M, Co, Ci, off);
+    float* PA = reinterpret_cast<float*>(base + off[0]);
+    float* PB = reinterpret_cast<float*>(base + off[1]);
+    float* PG = reinterpret_cast<float*>(base + off[2]);
+    float* PX = reinterpret_cast<float*>(base + off[3]);
+    float* pro = reinterpret_cast<float*>(base + off[4]);
+    const crf::MlpPlan p = crf::mlp_plan(M, Co, Ci);
+    // the last workgroup of pass 1 does the channel part when its 2 Co sums fit one thread each in groups of whole quads
+    if (!(2 * Co <= crf::WG_BLOCK && crf::WG_BLOCK % (Co / 2) == 0 && (int64_t)p.nblk * 2 * Co * 4 < ((int64_t)1 << 31))) ticket = nullptr;
+    {
+        const dim3 grid((unsigned)p.nblk, (unsigned)p.gy, (unsigned)p.gz), blk(crf::WG_BLOCK);
+#define P1(TA, TB) hipLaunchKernelGGL((crf::mlp_bwd_p1_kernel<TA, TB>), grid, blk, 0, st, gA, Y, X, Xb, xsplit, coef, slope, M, Co, Ci, p.rows_per_block, PA, PB, PG, PX, ticket, dgamma, dbeta, pro)
+        switch (p.tco * 10 + p.tci) {
+            case 11: P1(1, 1); break;
+            case 12: P1(1, 2); break;
+            case 14: P1(1, 4); break;
+            case 21: P1(2, 1); break;
+            case 22: P1(2, 2); break;
+            case 24: P1(2, 4); break;
+            case 41: P1(4, 1); break;
+            default: P1(4, 2); break;
+        }
+#undef P1
+        CRF_LAUNCH_CHECK();
+    }
+    // dW == NULL: the channel part only; the caller finishes dW later from the workspace (crfconv_mlp_dw_jobs)
+    const int nw = dW != nullptr ? (int)crf::cdiv((int64_t)Co * Ci, 64) : 0;
+    const int nc = ticket != nullptr ? 0 : (Co + crf::MF_WAVES - 1) / crf::MF_WAVES;      // channel workgroups (none: done inside pass 1)
+    if (nw + nc > 0) {
+        hipLaunchKernelGGL(crf::mlp_bwd_finalize_kernel, dim3((unsigned)(nw + nc)), dim3(crf::MF_BLOCK), 0, st, PA, PB, PG, PX, p.nblk, coef, M, Co,
+                           Ci, nw, dW, dgamma, dbeta, pro);
+        CRF_LAUNCH_CHECK();
+    }
+    if (dX != nullptr) {
+        // dX [M, Ci] = gY [M, Co] W [Co, Ci]: the forward kernel with k = Co, outputs = Ci, W read transposed
+        crf::LfArgs a;
+        a.X = gA; a.W = W; a.M = M; a.Ci = Co; a.Co = Ci; a.transpose_w = 1; a.Y = dX;
+        a.Y2 = Y; a.pro = pro; a.slope = slope;
+        a.Yb = dXb; a.ysplit = xsplit;
+        a.addend = dX_add; a.mask_ref = mask_ref; a.mask_slope = mask_slope;
+        return crf::lf_launch<true>(a, mask_ref != nullptr ? crf::EPI_ADD_MASK : (dX_add != nullptr ? crf::EPI_ADD : crf::EPI_NONE), stream);
+    }
+    return CRF_OK;
+}
+
+extern "C" int crfconv_mlp_backward(const float* gA, const float* Y, const float* X, const float* W, const float* coef,
+                                    float slope, int64_t M, int Ci, int Co, float* dX, float* dW, float* dgamma,
+                                    float* dbeta, void* workspace, size_t workspace_bytes, unsigned* ticket,
+                                    crf_stream_t stream) {
+    return mlp_backward_impl(gA, Y, X, nullptr, 0, W, coef, slope, M, Ci, Co, dX, nullptr, dW, dgamma, dbeta, workspace,
+                             workspace_bytes, ticket, stream);
+}
+
+// dX = (the block's input gradient) + dX_add [M, Ci]: the block's input has a second consumer (the shortcut of a ResNet block)
+// whose gradient is already known -- the sum autograd would form in a pass of its own is made while dX is written.
+extern "C" int crfconv_mlp_backward_add(const float* gA, const float* Y, const float* X, const float* W, const float* coef,
+                                        float slope, int64_t M, int Ci, int Co, const float* dX_add, float* dX, float* dW,
+                                        float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
+                                        unsigned* ticket, crf_stream_t stream) {
+    CRF_REQUIRE(dX != nullptr || dX_add == nullptr, CRF_ERR_ARG, "dX_add without dX");
+    return mlp_backward_impl(gA, Y, X, nullptr, 0, W, coef, slope, M, Ci, Co, dX, nullptr, dW, dgamma, dbeta, workspace,
+                             workspace_bytes, ticket, stream, dX_add);
+}
+
+// The same with the LeakyReLU mask of the ResNet join that PRODUCED the block's input x folded in: dX = mask(gY W + dX_add; X, mask_slope),
+// mask(v; ref, s) = ref > 0 ? v : s v -- what crfconv_add_lrelu_backward(dX, X, ...) would make of crfconv_mlp_backward_add's dX in a
+// pass of its own (same float operations: bit-identical).  dX is then the join's g1.  Ci % 4 == 0.  dX_add == NULL (the alias had no
+// gradient): the plain product, then that pass in place.
+// crfconv_add_lrelu_backward lives in pool.hip; the header declares it.
+extern "C" int crfconv_mlp_backward_add_mask(const float* gA, const float* Y, const float* X, const float* W, const float* coef,
+                                             float slope, int64_t M, int Ci, int Co, const float* dX_add, float mask_slope, float* dX,
+                                             float* dW, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
+                                             unsigned* ticket, crf_stream_t stream) {
+    CRF_REQUIRE(dX != nullptr && Ci % 4 == 0, CRF_ERR_ARG, "the masked form writes dX, Ci=%d a multiple of 4", Ci);
+    if (dX_add == nullptr) {
+        if (int rc = mlp_backward_impl(gA, Y, X, nullptr, 0, W, coef, slope, M, Ci, Co, dX, nullptr, dW, dgamma, dbeta, workspace,
+                                       workspace_bytes, ticket, stream))
+            return rc;
+        return crfconv_add_lrelu_backward(dX, X, M * Ci, mask_slope, dX, stream);
+    }
+    return mlp_backward_impl(gA, Y, X, nullptr, 0, W, coef, slope, M, Ci, Co, dX, nullptr, dW, dgamma, dbeta, workspace,
+                             workspace_bytes, ticket, stream, dX_add, X, mask_slope);
+}
+
+// The block's input was the column concatenation [Xa | Xb]: dXa [M, split], dXb [M, Ci - split] (both or neither NULL).
+extern "C" int crfconv_mlp_backward_cat(const float* gA, const float* Y, const float* Xa, const float* Xb, int split,
+                                        const float* W, const float* coef, float slope, int64_t M, int Ci, int Co,
+                                        float* dXa, float* dXb, float* dW, float* dgamma, float* dbeta, void* workspace,
+                                        size_t workspace_bytes, unsigned* ticket, crf_stream_t stream) {
+    CRF_REQUIRE(Xb && split > 0 && split < Ci && split % 4 == 0 && Ci % 4 == 0 && ((dXa == nullptr) == (dXb == nullptr)),
+                CRF_ERR_ARG, "two-operand form: split=%d Ci=%d must be multiples of 4, dXa / dXb both or neither", split, Ci);
+    return mlp_backward_impl(gA, Y, Xa, Xb, split, W, coef, slope, M, Ci, Co, dXa, dXb, dW, dgamma, dbeta, workspace,
+                             workspace_bytes, ticket, stream);
+}
+
+// dW of any number of MLP blocks whose crfconv_mlp_backward(_add / _cat) call was given dW = NULL, from the workspaces those
+// calls left behind (untouched since), in ONE launch.
+static int mlp_dw_jobs_impl(const crf_mlp_dw_job* jobs, int njobs, const crf::CrfMatJobs* side, int nside, crf_stream_t stream) {
+    CRF_REQUIRE(jobs || njobs == 0, CRF_ERR_ARG, "null pointer");
+    CRF_REQUIRE(njobs >= 0, CRF_ERR_ARG, "njobs=%d < 0", njobs);
+    hipStream_t st = crf::as_stream(stream);
+    for (int j0 = 0; j0 < njobs; j0 += crf::MDW_MAX) {
+        crf::MlpDwTable t;
+        const int n = njobs - j0 < crf::MDW_MAX ? njobs - j0 : crf::MDW_MAX;
+        int64_t total = 0;
+        for (int j = 0; j < crf::MDW_MAX; ++j) {
+            const crf_mlp_dw_job& jb = jobs[j0 + (j < n ? j : 0)];
+            if (j < n) {
+                CRF_REQUIRE(jb.workspace && jb.coef && jb.dW, CRF_ERR_ARG, "job %d: null pointer", j0 + j);
+                CRF_REQUIRE(crfconv_mlp_backward_supported(jb.M, jb.Ci, jb.Co) == 1, CRF_ERR_UNSUPPORTED,
+                            "job %d: shape M=%lld Ci=%d Co=%d not supported", j0 + j, (long long)jb.M, jb.Ci, jb.Co);
+            }
+            const char* base = reinterpret_cast<const char*>((reinterpret_cast<uintptr_t>(jb.workspace) + 255) & ~(uintptr_t)255);
+            size_t off[5];
+            crf::mlp_ws_layout(jb.M, jb.Co, jb.Ci, off);
+            t.PA[j] = reinterpret_cast<const float*>(base + off[0]);
+            t.PB[j] = reinterpret_cast<const float*>(base + off[1]);
+            t.PG[j] = reinterpret_cast<const float*>(base + off[2]);
+            t.PX[j] = reinterpret_cast<const float*>(base + off[3]);
+            t.coef[j] = jb.coef;
+            t.dW[j] = jb.dW;
+            t.M[j] = (long long)jb.M;
+            t.nblk[j] = crf::mlp_plan(jb.M, jb.Co, jb.Ci).nblk;
+            t.Co[j] = jb.Co;
+            t.Ci[j] = jb.Ci;
+            t.group_begin[j] = (int)total;
+            if (j < n) total += crf::cdiv((int64_t)jb.Co * jb.Ci, 64);
+            CRF_REQUIRE(total < ((int64_t)1 << 30), CRF_ERR_ARG, "too many slots in one batch");
+        }
+        t.group_begin[crf::MDW_MAX] = (int)total;
+        t.njobs = n;
+        if (side != nullptr && j0 == 0)
+            hipLaunchKernelGGL(crf::mlp_dw_jobs_hosting_kernel, dim3((unsigned)(total + nside)), dim3(crf::MF_BLOCK), 0, st, t, *side, nside);
+        else
+            hipLaunchKernelGGL(crf::mlp_dw_jobs_kernel, dim3((unsigned)total), dim3(crf::MF_BLOCK), 0, st, t);
+        CRF_LAUNCH_CHECK();
+    }
+    return CRF_OK;
+}
+extern "C" int crfconv_mlp_dw_jobs(const crf_mlp_dw_job* jobs, int njobs, crf_stream_t stream) {
+    return mlp_dw_jobs_impl(jobs, njobs, nullptr, 0, stream);
+}
+// crfconv_mlp_dw_jobs whose (first) launch also CARRIES crfconv_crf_matrices_backward_batched(c, Q, gQ, gP, H, n, dc) as its first
+// workgroups: results of both are those of the two separate calls.
+extern "C" int crfconv_mlp_dw_jobs_hosting(const crf_mlp_dw_job* jobs, int njobs, const float* const* c, const float* const* Q,
+                                           const float* const* gQ, const float* const* gP, const int* H, int n, float* const* dc,
+                                           crf_stream_t stream) {
+    CRF_REQUIRE(njobs >= 1, CRF_ERR_ARG, "a hosting launch needs at least one job of its own (got %d)", njobs);
+    crf::CrfMatJobs j;
+    int nslab = 0;
+    if (int rc = crf_matrices_bwd_jobs(c, Q, gQ, gP, H, n, dc, j, nslab)) return rc;
+    return mlp_dw_jobs_impl(jobs, njobs, &j, nslab, stream);
+}

@@ -200,7 +200,7 @@ class _SpdInverse(torch.autograd.Function):
 
 
 class _CrfMatrices(torch.autograd.Function):
-    """c [H, H] -> Q = (I + c^T c)^-1, P = c^T c Q = I - Q: one workgroup forward, one backward (csrc/linear.hip)."""
+    """c [H, H] -> Q = (I + c^T c)^-1, P = c^T c Q = I - Q: one workgroup forward, one backward (csrc/crf_matrices.hip)."""
 
     @staticmethod
     def forward(ctx, c):
@@ -458,7 +458,7 @@ def crf_meanfield(z, y, c, table, steps, k0=1, matrices=None):
     if H > _CRF_WIDE_H[-1]:
         raise _lib.CrfConvError('mean field: H = %d exceeds the widest kernel (%d)' % (H, _CRF_WIDE_H[-1]))
     if H > _CRF_H[-1]:
-        # Q = (I + c^T c)^-1 and P = I - Q (H x H, once per call: csrc/linear.hip spd_inverse_wide_kernel); zero-padded channels stay zero
+        # Q = (I + c^T c)^-1 and P = I - Q (H x H, once per call: csrc/crf_matrices.hip spd_inverse_wide_kernel); zero-padded channels stay zero
         Hp = _next_supported(H, _CRF_WIDE_H)
         Q, P = _CrfMatricesWide.apply(c)
         if Hp != H:

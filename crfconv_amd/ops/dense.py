@@ -32,7 +32,7 @@ def _gemm(A, B, bias=None, addend=None, nk=False):
 
 def _gemm_tn(A, B):
     """A^T B for [m, Ca] / [m, Cb] row operands (a reduction over the long dimension): the MFMA row-reduction kernel of
-    linear.hip (crfconv_linear_wgrad), fixed summation order."""
+    wgrad.hip (crfconv_linear_wgrad), fixed summation order."""
     m, ca = A.shape
     cb = B.shape[1]
     if m == 0:
@@ -78,7 +78,7 @@ def _mfma_matmul(x, W, b, transpose_w, want_stats=False):
 
 class _Linear(torch.autograd.Function):
     """y = x W^T (+ b) on [m, Ci] rows.  Large-m, <= 128-channel layers run on the MFMA kernels of linear.hip
-    (forward with fused BatchNorm statistics, dX, and the dW / db row reduction); small or very wide ones go to
+    and wgrad.hip (forward with fused BatchNorm statistics, dX, and the dW / db row reduction); small or very wide ones go to
     the vendor GEMM for forward / dX (plain library GEMMs)."""
 
     @staticmethod

@@ -48,7 +48,7 @@ def _signed_zero_ref(M, C, g):
 
 @pytest.mark.parametrize('with_add', [True, False])
 @pytest.mark.parametrize('mslope', [0.01, 0.1])
-@pytest.mark.parametrize('ci,co', [(32, 8), (64, 16), (128, 32), (24, 8)])
+@pytest.mark.parametrize('ci,co', [(32, 8), (64, 16), (128, 32), (24, 8), (16, 64)])      # (16, 64): one 16-column output tile per workgroup
 def test_fine_dx_masked_epilogue_equals_product_then_mask_pass(ci, co, mslope, with_add):
     """crfconv_mlp_backward_add_mask against crfconv_mlp_backward_add followed by crfconv_add_lrelu_backward(dX, x): 4100 rows (a partial
     16-row group, several workgroups), the widths of the fine-level lin_in blocks, with the alias gradient and without."""
@@ -89,6 +89,44 @@ def test_fine_dx_masked_epilogue_equals_product_then_mask_pass(ci, co, mslope, w
     for name, a, b in zip(('dX', 'dW', 'dgamma', 'dbeta'), got, ref):
         assert torch.equal(a, b), (name, float((a - b).abs().max()))
     assert torch.equal(got[0], torch.where(x > 0, ref[4], mslope * ref[4])) and not torch.equal(got[0], ref[4])      # -0.0 and +0.0: slope side
+
+
+@pytest.mark.parametrize('ci,co', [(6, 32), (22, 8)])
+def test_fine_dx_add_epilogue_on_unaligned_inputs_equals_product_then_add(ci, co):
+    """crfconv_mlp_backward_add on a block whose input width is no multiple of 4 -- the element-wise dX product, which the masked form
+    above refuses -- against crfconv_mlp_backward followed by dX + add: 133 rows (several workgroups, a partial last 16-row group), one
+    and two 16-column output tiles per workgroup."""
+    from crfconv_amd import _lib, ops
+    from crfconv_amd.ops import ptr, stream_ptr
+    lib = _lib.load()
+    M = 133
+    g = torch.Generator().manual_seed(ci * 131 + co)
+    x = torch.randn(M, ci, generator=g).to(DEV)
+    W = (torch.randn(co, ci, generator=g) / ci ** 0.5).to(DEV)
+    gA = torch.randn(M, co, generator=g).to(DEV)
+    add = torch.randn(M, ci, generator=g).to(DEV)
+    gamma, beta = (torch.rand(co, generator=g) + 0.5).to(DEV), torch.randn(co, generator=g).to(DEV)
+    rm, rv = torch.zeros(co, device=DEV), torch.ones(co, device=DEV)
+    y, rec = ops._mfma_matmul(x, W, None, False, True)
+    coef = torch.empty(4 * co, device=DEV)
+    out = torch.empty_like(y)
+    _lib.call('crfconv_bn_apply_from_records', ptr(rec), rec.shape[0], ptr(y), M, co, ptr(gamma), ptr(beta), ptr(rm), ptr(rv), 0.1, 1e-5,
+              None, 0.1, ptr(coef), ptr(out), stream_ptr())
+    assert lib.crfconv_mlp_backward_supported(M, ci, co) == 1
+    nbytes = lib.crfconv_mlp_backward_workspace(M, ci, co)
+
+    def run(name, *addend):
+        dX = torch.full((M, ci), float('nan'), device=DEV)
+        dW, dg, db = torch.empty(co, ci, device=DEV), torch.empty(co, device=DEV), torch.empty(co, device=DEV)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
+        _lib.call(name, ptr(gA), ptr(y), ptr(x), ptr(W), ptr(coef), 0.1, M, ci, co, *addend, ptr(dX), ptr(dW), ptr(dg), ptr(db), ptr(ws),
+                  nbytes, ops._mlp_ticket(DEV), stream_ptr())
+        return dX, dW, dg, db
+    ref, got = run('crfconv_mlp_backward'), run('crfconv_mlp_backward_add', ptr(add))
+    assert torch.isfinite(got[0]).all()
+    assert torch.equal(got[0], ref[0] + add), float((got[0] - (ref[0] + add)).abs().max())
+    for name, a, b in zip(('dW', 'dgamma', 'dbeta'), got[1:], ref[1:]):
+        assert torch.equal(a, b), (name, float((a - b).abs().max()))
 
 
 @pytest.mark.parametrize('one_launch', [True, False])

@@ -1243,6 +1243,8 @@ def test_linear_wgrad_mfma(M, Ci, Co, bias):
 @pytest.mark.parametrize('M,Ci,Co,slope,need_dx', [(163840, 32, 8, 0.1, True), (163840, 6, 32, 0.1, False), (40960, 64, 16, 1.0, True),
                                                    (163840, 32, 128, 0.1, True), (10240, 128, 32, 0.1, True), (4100, 24, 64, 0.1, True),
                                                    (40963, 16, 64, 1.0, True), (10240, 32, 128, 1.0, True),
+                                                   # 6 inputs WITH an input gradient: the element-wise (unaligned) dX product; 12 289 rows stream at both switch-overs
+                                                   (12289, 6, 32, 0.1, True),
                                                    # wide layers of the 2 560-point level: narrower weight slabs (32 / 16 channels per workgroup)
                                                    (10240, 256, 128, 0.1, True), (10240, 128, 256, 1.0, True), (4100, 512, 64, 0.1, True), (4100, 64, 512, 0.1, True),
                                                    # coarse levels: the one-launch forward of csrc/mlp_small.hip (grid barrier)
@@ -1250,7 +1252,7 @@ def test_linear_wgrad_mfma(M, Ci, Co, bias):
                                                    (1280, 128, 512, 1.0, True), (4095, 512, 512, 0.1, True), (1000, 80, 192, 0.2, True),
                                                    (64, 16, 64, 0.1, True), (37, 144, 64, 1.0, False)])
 def test_mlp_block_fused_backward(M, Ci, Co, slope, need_dx, min_rows, monkeypatch):
-    """ops.mlp_block (Linear -> train-mode BatchNorm -> LeakyReLU as one node, csrc/linear.hip: mlp_bwd_p1 / finalize /
+    """ops.mlp_block (Linear -> train-mode BatchNorm -> LeakyReLU as one node, csrc/mlp_bwd.hip: mlp_bwd_p1 / finalize /
     dX with the BatchNorm-backward prologue) against float64 torch.  As in test_fused_batchnorm_lrelu the LeakyReLU
     branch of elements within rounding of 0 is taken from the kernel's own output."""
     from crfconv_amd import ops
@@ -1381,6 +1383,26 @@ def test_classifier_dropout_backward_folded_into_last_linear():
     assert_close(b2.grad, res[0][4], 1e-6, 'deferred db2')
     assert torch.equal(x.grad, res[0][1])
     assert ops.mlp_dropout_linear(x[:100], W, bn, slope, 0.5, W2, b2) is None      # below the MFMA row count: caller's path
+
+
+@pytest.mark.parametrize('Ci,Co', [(8, 16), (16, 32)])
+def test_linear_forward_dropout_equals_product_then_mask(Ci, Co):
+    """crfconv_linear_forward_dropout at widths the classifier above does not have (one and two 16-column output tiles per workgroup,
+    every access a 16-byte one) against crfconv_linear_forward followed by the host twin of the mask: 133 rows (several workgroups, a
+    partial last 16-row group); the kept elements are the product times 1 / (1 - p) = 2 exactly, so bit for bit."""
+    from crfconv_amd import _lib, ops
+    from crfconv_amd.ops import ptr, stream_ptr
+    M, p, seed, ctr = 133, 0.5, 0x1234567, 3
+    g = torch.Generator().manual_seed(Ci * 131 + Co)
+    x = torch.randn(M, Ci, generator=g).to(DEV)
+    W = (torch.randn(Ci, Co, generator=g) / Ci ** 0.5).to(DEV)                  # read transposed, as the dX product of the last Linear is
+    counter = torch.full((1,), ctr, dtype=torch.int64, device=DEV)
+    got = torch.full((M, Co), float('nan'), device=DEV)
+    _lib.call('crfconv_linear_forward_dropout', ptr(x), ptr(W), M, Ci, Co, 1, p, seed, ptr(counter), ptr(got), stream_ptr())
+    keep = torch.from_numpy(ops.dropout_keep_mask(seed, ctr, M * Co, p).reshape(M, Co)).to(DEV)
+    assert 0.4 < float(keep.float().mean()) < 0.6
+    y = ops._mfma_matmul(x, W, None, True)[0]
+    assert torch.equal(got, torch.where(keep, 2.0 * y, torch.zeros_like(y))), float((got - 2.0 * y * keep).abs().max())
 
 
 @pytest.mark.parametrize('M,Ci,C2,bias', [(40960, 32, 13, True), (20001, 32, 13, True), (12288, 16, 8, False), (16400, 16, 16, True)])

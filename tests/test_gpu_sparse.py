@@ -409,7 +409,7 @@ def test_discrete_crf_networks_run_and_train():
 
 def test_no_vendor_or_framework_math_kernel_on_the_sparse_and_discrete_paths(golden):
     """the products, inverses and BatchNorms of the sparse CRF layers (incl. the wide H = 128 stage: own Gauss-Jordan
-    inverse, csrc/linear.hip spd_inverse_wide_kernel), of the sparse PointConv twin and of the discrete CRF layer run on this library's
+    inverse, csrc/crf_matrices.hip spd_inverse_wide_kernel), of the sparse PointConv twin and of the discrete CRF layer run on this library's
     kernels -- no rocBLAS / Tensile product (`Cijk_*`), no vendor solver, no MIOpen, no framework BatchNorm / GEMM / inverse kernel in a
     profiled forward + backward.  (Element-wise glue -- softmax / log of the discrete layer, index arithmetic of the edge lists -- is
     the framework's, as in the reference.)"""
