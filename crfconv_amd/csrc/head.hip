@@ -165,7 +165,10 @@ __global__ __launch_bounds__(HD_BLOCK) void head_stats_kernel(const float* __res
 // ------------------------------------------------------------------------------------------------------------ forward
 // logits [M, C2] = dropout(lrelu(a (x W1^T) + b, slope)) W2^T + b2;  mask_bits [ceil(M / 16)][64]: bit 4 t + e of word
 // (group, lane (rr, g)) = element (row 16 group + rr, channel 16 t + 4 g + e) was kept.
-template <int NCH>
+// EVAL: the eval-mode classifier, logits = lrelu(a (x W1^T) + b, slope) W2^T + b2 -- no counter read, no hash, no mask word, no
+// scale; seed, counter, threshold, scale, mask_bits and counter_used are not touched.  At p = 0 the training form keeps every
+// element and multiplies by 1.f, so both forms perform the same float32 operations in the same order: bit-identical logits.
+template <int NCH, bool EVAL>
 __global__ __launch_bounds__(HD_BLOCK, 2) void head_fwd_kernel(const float* __restrict__ X, const float* __restrict__ W1,
                                                                const float* __restrict__ coef, float slope, unsigned long long seed,
                                                                const long long* __restrict__ counter, unsigned threshold, float scale,
@@ -183,9 +186,12 @@ __global__ __launch_bounds__(HD_BLOCK, 2) void head_fwd_kernel(const float* __re
         st4(sW2 + r * HD_LD + 4 * k4, r < C2 ? ld4(W2 + (int64_t)r * HD_CO + 4 * k4) : f4zero());
     }
     for (int t = threadIdx.x; t < 2 * HD_CO; t += HD_BLOCK) sAB[t] = coef[t];
-    const unsigned long long ctr = (unsigned long long)counter[0];
-    if (counter_used != nullptr && blockIdx.x == 0 && threadIdx.x == 0) counter_used[0] = (long long)ctr;
-    const unsigned long long keys = dropout_keys(seed, ctr);
+    unsigned long long keys = 0ull;
+    if constexpr (!EVAL) {
+        const unsigned long long ctr = (unsigned long long)counter[0];
+        if (counter_used != nullptr && blockIdx.x == 0 && threadIdx.x == 0) counter_used[0] = (long long)ctr;
+        keys = dropout_keys(seed, ctr);
+    }
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, rr = lane & 15, g = lane >> 4;
     float bias2[4];
@@ -235,9 +241,13 @@ __global__ __launch_bounds__(HD_BLOCK, 2) void head_fwd_kernel(const float* __re
             for (int e = 0; e < 4; ++e) {
                 float u = fmaf(av[e], acc[t][e], bv[e]);
                 u = u > 0.f ? u : slope * u;
-                const bool keep = dropout_keep_keyed(keys, ebase + (unsigned long long)(16 * t + e), threshold);
-                bits |= (keep ? 1u : 0u) << (4 * t + e);
-                h[e] = keep ? u * scale : 0.f;
+                if constexpr (EVAL) {
+                    h[e] = u;
+                } else {
+                    const bool keep = dropout_keep_keyed(keys, ebase + (unsigned long long)(16 * t + e), threshold);
+                    bits |= (keep ? 1u : 0u) << (4 * t + e);
+                    h[e] = keep ? u * scale : 0.f;
+                }
             }
             const float4 w2 = ld4(sW2 + rr * HD_LD + 16 * t + 4 * g);
             lg = HD_MFMA(w2.x, h[0], lg);
@@ -245,7 +255,7 @@ __global__ __launch_bounds__(HD_BLOCK, 2) void head_fwd_kernel(const float* __re
             lg = HD_MFMA(w2.z, h[2], lg);
             lg = HD_MFMA(w2.w, h[3], lg);
         }
-        mask_bits[grp * 64 + lane] = bits;
+        if constexpr (!EVAL) mask_bits[grp * 64 + lane] = bits;
         // lane holds logits[row rr][class 4 g + e]: through a per-wave tile, so that the sixteen rows leave as one contiguous run
         st4(tile + rr * 16 + 4 * g, make_float4(lg[0], lg[1], lg[2], lg[3]));
         __builtin_amdgcn_wave_barrier();
@@ -783,12 +793,18 @@ extern "C" int crfconv_head_stats(const float* X, const float* W1, int64_t M, in
 extern "C" int crfconv_head_forward(const float* X, const float* W1, const float* coef, float slope, float p, uint64_t seed,
                                     const int64_t* counter, const float* W2, const float* b2, int64_t M, int Ci, int Co, int C2,
                                     float* logits, uint32_t* mask_bits, int64_t* counter_used, crf_stream_t stream) {
-    CRF_REQUIRE(X && W1 && coef && counter && W2 && logits && mask_bits, CRF_ERR_ARG, "null pointer");
+    const bool eval = mask_bits == nullptr;          // the eval form: no dropout, hence no counter, no seed, no mask
+    CRF_REQUIRE(X && W1 && coef && W2 && logits && (eval || counter), CRF_ERR_ARG, "null pointer");
     CRF_REQUIRE(crfconv_head_supported(M, Ci, Co, C2), CRF_ERR_UNSUPPORTED, "classifier head %d -> %d -> %d not supported", Ci, Co, C2);
     CRF_REQUIRE(p >= 0.f && p < 1.f, CRF_ERR_ARG, "dropout probability %g outside [0, 1)", (double)p);
+    CRF_REQUIRE(!eval || p == 0.f, CRF_ERR_ARG, "mask_bits is NULL (the eval form) with dropout probability %g: p != 0 needs a mask buffer", (double)p);
     const dim3 grid((unsigned)hd_grid(M)), blk(HD_BLOCK);
-#define HD_FWD(N) hipLaunchKernelGGL(head_fwd_kernel<N>, grid, blk, 0, as_stream(stream), X, W1, coef, slope, (unsigned long long)seed, reinterpret_cast<const long long*>(counter), dropout_threshold(p), 1.f / (1.f - p), W2, b2, M, C2, logits, reinterpret_cast<unsigned*>(mask_bits), reinterpret_cast<long long*>(counter_used))
-    if (Ci == 16) HD_FWD(1); else HD_FWD(2);
+#define HD_FWD(N, E) hipLaunchKernelGGL((head_fwd_kernel<N, E>), grid, blk, 0, as_stream(stream), X, W1, coef, slope, (unsigned long long)seed, reinterpret_cast<const long long*>(counter), dropout_threshold(p), 1.f / (1.f - p), W2, b2, M, C2, logits, reinterpret_cast<unsigned*>(mask_bits), reinterpret_cast<long long*>(counter_used))
+    if (eval) {
+        if (Ci == 16) HD_FWD(1, true); else HD_FWD(2, true);
+    } else {
+        if (Ci == 16) HD_FWD(1, false); else HD_FWD(2, false);
+    }
 #undef HD_FWD
     CRF_LAUNCH_CHECK();
     return CRF_OK;

@@ -7,7 +7,11 @@ runs the same forward with the product kernels' BatchNorm epilogue (``ops.linear
 all blocks from ONE launch at the start of the forward (``ops.bn_eval_coefs``).  Same kernels, same summation order, the same
 float32 operations in the same order behind the accumulator: the logits are bit-identical to ``model.eval()(data)``.
 
-Opt-in: ``model = InferenceNet(model)`` after ``model.eval()``; what ``model.eval()(data)`` does is untouched.  Nothing is cached
+``InferenceNet(model, fused_head=True)`` also runs the classifier -- MLP 32 -> 128, Dropout, Linear 128 -> classes -- as one launch that
+never stores the [M, 128] activation (``ops.head_eval``); those logits are held to the float64 oracle's bound, not to bit-identity.
+
+Opt-in: ``model = InferenceNet(model)`` after ``model.eval()``; what ``model.eval()(data)`` computes is untouched (under ``no_grad`` the
+model replays this wrapper's default form by itself: train.GraphedInference).  Nothing is cached
 across calls -- weights and running statistics are read where they live, at every call and at every replay of a captured graph."""
 import torch
 import torch.nn as nn
@@ -40,6 +44,18 @@ def _fused_form(mlp):
             and (mlp.activation is None or isinstance(mlp.activation, nn.LeakyReLU)) and mlp.lin.out_features % 4 == 0)
 
 
+def why_not(model):
+    """None where InferenceNet takes `model`, else the TypeError's text: a PointConvBig whose decoders are all CRF layers or all
+    Upsampling stages."""
+    accepted = 'InferenceNet takes a PointConvBig (models.point_conv_big.PointConvResNet) whose decoders are all CRF layers or all Upsampling stages'
+    if not isinstance(model, PointConvResNet):
+        return '%s; got %s' % (accepted, type(model).__name__)
+    kinds = {type(d) for d in _decoders(model)}
+    if kinds != {CRFConv} and kinds != {Upsampling}:
+        return '%s; got decoders %s' % (accepted, sorted(k.__name__ for k in kinds))
+    return None
+
+
 class InferenceNet(nn.Module):
     """``InferenceNet(model)(data)`` = ``model.eval()(data)`` under ``no_grad``, bit for bit, with one launch per MLP block.
 
@@ -48,14 +64,16 @@ class InferenceNet(nn.Module):
     mode raises.  A model with module hooks runs ``model(data)`` itself, so that the hooks fire.  Works as the ``net`` of
     ``sampling.SceneVoter`` and ``sampling.vote_scene`` and inside a caller's ``torch.cuda.graph``."""
 
-    def __init__(self, model):
+    def __init__(self, model, fused_head=False):
+        """fused_head: the classifier (MLP 32 -> 128, Dropout, Linear 128 -> classes) as ONE launch that keeps the 128 channels in
+        registers (``ops.head_eval``) where the head kernel takes its shape -- at most 16 classes; anything else runs the two
+        launches of the default.  Its logits may differ from the default's in the last bits (another summation order than the
+        product kernels'): the contract is the logits bound against the float64 oracle, not bit-identity with ``model.eval()``."""
         super().__init__()
-        accepted = 'InferenceNet takes a PointConvBig (models.point_conv_big.PointConvResNet) whose decoders are all CRF layers or all Upsampling stages'
-        if not isinstance(model, PointConvResNet):
-            raise TypeError('%s; got %s' % (accepted, type(model).__name__))
-        kinds = {type(d) for d in _decoders(model)}
-        if kinds != {CRFConv} and kinds != {Upsampling}:
-            raise TypeError('%s; got decoders %s' % (accepted, sorted(k.__name__ for k in kinds)))
+        self.fused_head = bool(fused_head)
+        refusal = why_not(model)
+        if refusal is not None:
+            raise TypeError(refusal)
         self.model = model
         self.training = model.training                     # wrapped behind model.eval(): the wrapper starts in the model's mode
         self._coef_buf = {}                                # device -> the flat coefficient buffer, allocated once
@@ -158,5 +176,13 @@ class InferenceNet(nn.Module):
             else:
                 h = self._up(coefs, d, h, skips[lvl], ms[lvl].up_idx)
         head, drop, last = model.classifier[0], model.classifier[1], model.classifier[2]
+        coef = coefs.get(id(head)) if isinstance(head, MLP) else None
+        if (self.fused_head and coef is not None and type(drop) is nn.Dropout
+                and type(last) is nn.Linear and h.shape[-1] == head.lin.in_features and last.in_features == head.lin.out_features
+                and _lib.load().crfconv_head_supported(h.numel() // h.shape[-1], head.lin.in_features, head.lin.out_features,
+                                                       last.out_features)):
+            # MLP -> Dropout (the identity here) -> Linear as one launch: no [M, 128] tensor
+            slope = 1.0 if head.activation is None else head.activation.negative_slope
+            return ops.head_eval(h, head.lin.weight, coef, slope, last.weight, last.bias).reshape(-1, model.C)
         h = drop(self._mlp(coefs, head, h))
         return ops.linear(h, last.weight, last.bias).reshape(-1, model.C)

@@ -117,16 +117,19 @@ class Base(nn.Module):
     def save(self, filename):
         torch.save(self.state_dict(), filename)
 
-    # A self-capturing model (train.autograph_forward) keeps its private graph runner in its instance dictionary, outside the module
-    # tree.  The runner's graphs hold device addresses: a copy of the model starts without it, and whatever moves or casts the
-    # parameters (to(), float(), cuda()) drops it -- the next training call captures again.
+    # A self-capturing model (train.autograph_forward, train.autograph_eval_forward) keeps its private graph runners -- one for training
+    # mode, one for eval mode under no_grad -- in its instance dictionary, outside the module tree.  Their graphs hold device addresses: a
+    # copy of the model starts without them, and whatever moves or casts the parameters (to(), float(), cuda()) drops them -- the next
+    # call captures again.
     def __getstate__(self):
         state = dict(super().__getstate__())
         state.pop('_autograph', None)
+        state.pop('_autograph_eval', None)
         return state
 
     def _apply(self, fn, *args, **kwargs):
         self.__dict__.pop('_autograph', None)
+        self.__dict__.pop('_autograph_eval', None)
         return super()._apply(fn, *args, **kwargs)
 
     def load(self, filename):

@@ -177,15 +177,19 @@ class PointConvResNet(Base):
     phase_hook = None
 
     def forward(self, data):
+        from .. import train
         if self.training:
-            from .. import train
             if train.autograph_wanted(data):                # the reference loop unwrapped: the step as two hipGraph replays (train.py)
                 out = train.autograph_forward(self, data)
                 if out is not None:
                     return out
+            elif not torch.is_grad_enabled():
+                train.count_eager(self, 'eval', 'training')   # no_grad in training mode stays eager: BatchNorm statistics advance
             with ops.advance_counters(self):              # every BatchNorm below runs exactly once per forward
                 return self._forward(data)
-        return self._forward(data)
+        # eval mode under no_grad (the reference's validation and test loops): one hipGraph replay of the fused eval forward
+        out = train.autograph_eval_forward(self, data)
+        return self._forward(data) if out is None else out
 
     def _forward(self, data):
         ms = data.multiscale

@@ -338,5 +338,43 @@ def linear_bn_act(x, W, coef, slope=1.0, skip=None, xb=None, bias=None):
     return y.reshape(lead + (co,))
 
 
+def head_eval(x, W1, coef, slope, W2, b2=None):
+    """logits [..., C2] = lrelu(BN_eval(x W1^T), slope) W2^T (+ b2) on [..., Ci] rows as ONE launch that never stores the [M, 128]
+    activation: the eval form of the classifier head kernel (crfconv_head_forward with a NULL mask; csrc/head.hip), bit-identical
+    to that entry point at p = 0 with a mask buffer.  Inference only -- the result has no grad_fn.  coef: the BatchNorm's [4, 128]
+    coefficient block a | b | mean | rstd (bn_eval_coefs); the kernel reads a | b.  float32 CUDA tensors; shapes of
+    crfconv_head_supported (128 hidden channels, 16 or 32 input channels, at most 16 classes) -- anything else raises."""
+    tensors = [t for t in (x, W1, coef, W2, b2) if t is not None]
+    require_gpu(*tensors)
+    for t in tensors:
+        if t.dtype != torch.float32:
+            raise _lib.CrfConvError('head_eval: float32 only (got %s): the path computes in the reference\'s arithmetic' % t.dtype)
+    ci = x.shape[-1]
+    if W1.dim() != 2 or W1.shape[1] != ci:
+        raise _lib.CrfConvError('head_eval: W1 %s does not take %d input channels' % (tuple(W1.shape), ci))
+    co = W1.shape[0]
+    if W2.dim() != 2 or W2.shape[1] != co:
+        raise _lib.CrfConvError('head_eval: W2 %s does not take %d hidden channels' % (tuple(W2.shape), co))
+    c2 = W2.shape[0]
+    if coef.shape[-1] != co or coef.numel() < 2 * co:
+        raise _lib.CrfConvError('head_eval: coefficient block %s for %d channels' % (tuple(coef.shape), co))
+    if b2 is not None and b2.numel() != c2:
+        raise _lib.CrfConvError('head_eval: bias of %d elements for %d classes' % (b2.numel(), c2))
+    if not _lib.load().crfconv_head_supported(1, ci, co, c2):
+        raise _lib.CrfConvError('head_eval: classifier head %d -> %d -> %d is outside the kernel\'s range (crfconv_head_supported)'
+                                % (ci, co, c2))
+    lead = x.shape[:-1]
+    with torch.no_grad():
+        x2 = x.detach().reshape(-1, ci).contiguous()
+        m = x2.shape[0]
+        logits = torch.empty((m, c2), dtype=torch.float32, device=x.device)
+        if m == 0:
+            return logits.reshape(lead + (c2,))
+        b = None if b2 is None else b2.detach().contiguous()
+        _lib.call('crfconv_head_forward', ptr(x2), ptr(W1.detach().contiguous()), ptr(coef.detach().contiguous()), float(slope), 0.0, 0,
+                  None, ptr(W2.detach().contiguous()), ptr(b), m, ci, co, c2, ptr(logits), None, None, stream_ptr())
+    return logits.reshape(lead + (c2,))
+
+
 # names of the sibling modules, imported LAST: every use is inside a function body, so import cycles between the families are harmless
 from .defer import _defer_ok, _defer_weight_grad  # noqa: E402

@@ -9,12 +9,15 @@
 The reference does both on the host with sklearn's KDTree and numpy; here the clouds, possibilities and vote tables
 stay in HBM and each call enqueues a handful of kernels of libcrfconv_amd.so (csrc/evaluate.hip).
 """
+import contextlib
+
 import numpy as np
 import torch
 
 from . import _lib
 from .data import Data
 from .graph import ptr, require_gpu, stream_ptr, to_device
+from .train import no_autograph
 
 
 def _ws(nbytes, device):
@@ -591,8 +594,8 @@ class _GraphedCrops:
         self.cg = CollateGraph(first, kernel_size=kernel_size, ratio=ratio, generator=generator)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), torch.no_grad():
-            net(first)                                   # warm-up outside the capture (lazily built tables, allocator)
+        with torch.cuda.stream(side), torch.no_grad(), no_autograph():
+            net(first)                                   # warm-up outside the capture (lazily built tables, allocator): THIS batch, launch by launch
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
@@ -659,7 +662,8 @@ def vote_scene(sampler, net, votes, n_crops, kernel_size=(16, 16, 16, 16, 16), r
             else:
                 data = stage('collate', lambda: multiscale_compute(pos, x=x, point_idx=crop.point_idx.unsqueeze(0), cloud_idx=crop.cloud_idx.reshape(1, 1),
                                                                    kernel_size=kernel_size, ratio=ratio, generator=generator, sort='morton'))
-                with torch.no_grad():
+                # (graphed: this batch becomes the static one of the capture below -- its own tables are built here, not a self-captured copy's)
+                with torch.no_grad(), (no_autograph() if graphed else contextlib.nullcontext()):
                     logits = stage('network', lambda: net(data))
                 # the collate reordered the crop along its Morton curve: point_idx travelled with it (multiscale_compute permutes x, y, point_idx alike)
                 point_idx = data.point_idx
@@ -723,7 +727,7 @@ class SceneVoter:
         crops = self.sampler.get_batch(self.B)
         data = multiscale_compute(crops.pos, x=crops.x, point_idx=crops.point_idx, cloud_idx=crops.cloud_idx, kernel_size=self.kernel_size,
                                   ratio=self.ratio, num_scales=len(self.kernel_size), generator=self.generator, sort='morton')
-        with torch.no_grad():
+        with torch.no_grad(), no_autograph():              # (this batch becomes the static one: the model must not capture a copy of it itself)
             logits = self.net(data)
         # the collate reordered every crop along its Morton curve: point_idx travelled with it
         self.votes.update_batch(data.point_idx, data.cloud_idx, logits=logits, repeated=self.repeated)
@@ -731,7 +735,7 @@ class SceneVoter:
         self.cg = CollateGraph(data, kernel_size=self.kernel_size, ratio=self.ratio, generator=self.generator, sampler=self.sampler)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), torch.no_grad():
+        with torch.cuda.stream(side), torch.no_grad(), no_autograph():
             self.net(data)                                # warm-up outside the capture (the forward only: a vote would count)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()

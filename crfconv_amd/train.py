@@ -13,8 +13,12 @@ would then have to synchronise with that stream.
 
 Round 6: the dense network captures ITSELF (``autograph``).  ``models.PointConvBig`` in training mode hands its forward to a private
 GraphedModel (below) the first time it is called on a device batch, so the reference loop with nothing wrapped -- trainval.py:96-106 as
-written -- runs as two hipGraph replays per step from its second iteration on.  What does not fit runs eagerly, silently and correctly:
-eval mode, ``no_grad``, a batch of other shapes or on another device, a forward whose predecessor has not been through ``backward()`` yet
+written -- runs as two hipGraph replays per step from its second iteration on.  The other half of that loop -- val_one_epoch and the
+test loops, trainval.py:110-124, :170-178, :236-244: ``model.eval()``, then ``model(data)`` under ``no_grad`` -- captures itself too: a private
+GraphedInference (at the end of this module) replays the fused eval forward (InferenceNet's launches: logits bit-identical to the
+launch-by-launch call) for one batch signature.  What does not fit runs eagerly, silently and correctly -- ``stats(model)`` counts it by reason:
+``no_grad`` in training mode (BatchNorm statistics advance there), eval mode with grad enabled (the caller gets a differentiable output),
+a batch of other shapes or on another device, a forward whose predecessor has not been through ``backward()`` yet
 while anything still reaches that pass's autograd node (a loss is enough -- ``crit(net(b1), y1) + crit(net(b2), y2)``: the replay would
 overwrite the activations its backward needs; a pass whose loss was dropped unused no longer counts), module forward / backward hooks on
 the model or any submodule and torch's global module hooks (checked at every call, also those registered after the capture), parameters
@@ -29,6 +33,8 @@ not keep a replayed pass) -- the model's autograph-off twin gives the eager grad
 if still held (accumulation over several backward passes works; a reference kept to an old ``.grad`` object across a zero_grad() and
 the next step sees the later values).  ``set_autograph(False)`` / ``CRFCONV_AUTOGRAPH=0`` / ``with no_autograph():`` switch it off (every
 launch issued by the host: 2-3 x the step time); ``DistributedDataParallel`` around the model is untested -- switch it off there."""
+import collections
+import gc
 import operator
 import os
 import weakref
@@ -39,7 +45,7 @@ _AUTO = {'on': os.environ.get('CRFCONV_AUTOGRAPH', '1').strip().lower() not in (
 
 
 def set_autograph(on):
-    """Process-wide switch of the self-capturing training forward (default on; CRFCONV_AUTOGRAPH=0 starts with it off)."""
+    """Process-wide switch of the self-capturing training and eval forwards (default on; CRFCONV_AUTOGRAPH=0 starts with it off)."""
     _AUTO['on'] = bool(on)
 
 
@@ -58,10 +64,85 @@ class no_autograph:
 def autograph_wanted(batch):
     if not _AUTO['on'] or _AUTO['bypass'] or not torch.is_grad_enabled():
         return False
+    return _device_batch(batch) and not torch.cuda.is_current_stream_capturing()
+
+
+def _device_batch(batch):
     x = getattr(batch, 'x', None)
-    if not (torch.is_tensor(x) and x.is_cuda and hasattr(batch, 'load_') and hasattr(batch, '_apply')):
-        return False
-    return not torch.cuda.is_current_stream_capturing()
+    return torch.is_tensor(x) and x.is_cuda and hasattr(batch, 'load_') and hasattr(batch, '_apply')
+
+
+def _eval_refusal(batch):
+    """Why an eval-mode call cannot be a replay whatever the runner holds -- one word, or None: grad enabled (the caller gets a
+    differentiable output), no device MultiScaleData, a call during another stream capture (issued inline there)."""
+    if torch.is_grad_enabled():
+        return 'grad'
+    if not _device_batch(batch):
+        return 'batch'
+    if torch.cuda.is_current_stream_capturing():
+        return 'capturing'
+    return None
+
+
+def autograph_eval_wanted(batch):
+    """The eval-mode twin of autograph_wanted: autograph on and not bypassed, grad DISABLED, a device batch, no capture under way."""
+    return bool(_AUTO['on']) and not _AUTO['bypass'] and _eval_refusal(batch) is None
+
+
+def _stock_network(model):
+    """The private eval runner replays InferenceNet's restatement of PointConvResNet._forward: only for a model whose own _forward is
+    that one (a subclass that overrides it computes something else) and that InferenceNet takes (decoders all CRF or all Upsampling)."""
+    from .infer import why_not
+    from .models.point_conv_big import PointConvResNet
+    return type(model)._forward is PointConvResNet._forward and why_not(model) is None
+
+
+def autograph_eval_forward(model, batch):
+    """The eval-mode forward of a self-capturing model: the logits of a replay of its private GraphedInference, or None -- the
+    model's own forward goes on launch by launch (never a nested ``model(batch)``: the model's hooks fire once).  The runner is
+    created by the first call that qualifies; once it exists, calls that do not qualify are counted on it (stats)."""
+    if _AUTO['bypass']:
+        return None
+    runner = model.__dict__.get('_autograph_eval')
+    why = 'off' if not _AUTO['on'] else _eval_refusal(batch)
+    if why is None and runner is None:
+        if _has_hooks(model) or not _stock_network(model):
+            return None
+        runner = GraphedInference(model)
+        object.__setattr__(model, '_autograph_eval', runner)  # (not a submodule of the model: the model is the runner's)
+    if why is None:
+        why = runner.refusal(batch)
+    if why is not None:
+        if runner is not None:
+            runner.eager[why] += 1
+        return None
+    return runner.replay(batch)
+
+
+def count_eager(model, which, why):
+    """One more eager call of `model` for the reason `why` on its 'train' / 'eval' runner, if it has one and autograph is on and not
+    bypassed (stats: calls inside no_autograph() are not counted; a switched-off call in training mode has no eval reason)."""
+    runner = model.__dict__.get('_autograph' if which == 'train' else '_autograph_eval')
+    if runner is not None and _AUTO['on'] and not _AUTO['bypass']:
+        runner.eager[why] += 1
+
+
+def stats(model):
+    """{'train': {...}, 'eval': {...}} of a self-capturing model (or of a GraphedModel / GraphedInference, under its own key): each
+    with `captures`, `replays` and `eager`, a collections.Counter of the calls that ran launch by launch, keyed by a one-word
+    reason.  Training runner: 'mode' (eval or no_grad call handed to it), 'hooks', 'pending' (the previous pass still awaits its
+    backward), 'passes' (re-homed parameters while an earlier pass's autograd graph lives), 'shape', 'frozen'.  Eval runner: 'off'
+    (set_autograph(False)), 'grad', 'training', 'batch', 'dtype', 'capturing', 'hooks', 'phase' (a phase_hook is set: a replay would not
+    call it), 'model' (decoders swapped for a mix InferenceNet does not take), 'shape'.  Calls inside ``no_autograph()``
+    are not counted.  All zeros for a model that never captured.  Nothing is logged or printed: a loop that degrades from replay
+    to launch-by-launch shows here, when asked."""
+    runners = {'train': model.__dict__.get('_autograph'), 'eval': model.__dict__.get('_autograph_eval')}
+    if isinstance(model, GraphedModel):
+        runners['train'] = model
+    elif isinstance(model, GraphedInference):
+        runners['eval'] = model
+    return {k: {'captures': 0 if r is None else r.captures, 'replays': 0 if r is None else r.replays,
+                'eager': collections.Counter() if r is None else collections.Counter(r.eager)} for k, r in runners.items()}
 
 
 def _hook_dicts(modules):
@@ -255,7 +336,7 @@ class GraphedModel(torch.nn.Module):
         self.warmup, self.defer_weight_grads = int(warmup), bool(defer_weight_grads)
         self.guard_pending, self._pending, self._gen = bool(guard_pending), None, 0
         self._passes = weakref.WeakSet()                         # autograd nodes of this runner's passes that are still alive
-        self.captures = 0
+        self.captures, self.replays, self.eager = 0, 0, collections.Counter()      # what train.stats reports
         self.fwd_graph = self.bwd_graph = None
         self.static = self.static_out = self.static_gout = None
         self.params, self.static_grads, self._sig = [], [], None
@@ -305,7 +386,6 @@ class GraphedModel(torch.nn.Module):
         self.captures += 1
         # no garbage collection inside the capture: a dead runner of another model (model <-> runner is a reference cycle) owns graphs,
         # and destroying a graph in the middle of another capture aborts the process -- the dead ones go here, before it
-        import gc
         gc.collect()
         was = gc.isenabled()
         gc.disable()
@@ -397,21 +477,22 @@ class GraphedModel(torch.nn.Module):
             if sg is not None and p.grad is not None and p.grad.data_ptr() == sg.data_ptr():
                 p.grad = p.grad.clone()
 
-    def _eager(self, batch):
+    def _eager(self, batch, why):
+        self.eager[why] += 1
         with no_autograph():
             out = self.model(batch)
         return _EagerPass.apply(self, out) if torch.is_tensor(out) and out.requires_grad else out
 
     def forward(self, batch):
         if not (self.training and torch.is_grad_enabled()):
-            return self._eager(batch)
+            return self._eager(batch, 'mode')
         if not self.guard_pending and self.hooked():            # (autograph_forward has checked: the model's own forward runs them)
-            return self._eager(batch)
+            return self._eager(batch, 'hooks')
         if self.guard_pending and self._pending is not None:
             if self._pending() is None:
                 self._pending = None                            # ... unless its autograd node is gone (a step that skipped its backward)
             else:
-                return self._eager(batch)                       # the previous pass still awaits its backward: nothing may replay over it
+                return self._eager(batch, 'pending')            # the previous pass still awaits its backward: nothing may replay over it
         if self.fwd_graph is not None and self._moved():
             self._drop_graphs()                                 # a pending pass of the old graphs raises at its backward (_GraphedPass)
         if self.fwd_graph is None:
@@ -419,13 +500,132 @@ class GraphedModel(torch.nn.Module):
                 # a live autograd graph of an earlier pass holds the parameters' gradient accumulators, bound to the stream they were
                 # created on: the captured backward would have to join that stream (the capture fails, or worse) -- eagerly until
                 # every earlier pass has been dropped (the next call of a loop that releases its loss before it)
-                return self._eager(batch)
+                return self._eager(batch, 'passes')
             self._capture(batch)
         elif batch is not self.static and self._signature(batch) != self._sig:
-            return self._eager(batch)
+            return self._eager(batch, 'shape')
         elif [p.requires_grad for p in self._all_params] != self._grad_flags:
-            return self._eager(batch)                           # parameters frozen / thawed since the capture
+            return self._eager(batch, 'frozen')                 # parameters frozen / thawed since the capture
         self._keep_accumulated_grads()
         if batch is not self.static:
             self.static.load_(batch, defer_check=True)          # (no host synchronisation: a bad table raises at the next call)
+        self.replays += 1
         return _GraphedPass.apply(self, *self.params)
+
+
+class GraphedInference:
+    """The eval twin of GraphedModel: ``with torch.no_grad(): runner(batch)`` on an eval-mode network as ONE hipGraph replay --
+    what val_one_epoch and the test loops of the reference call (trainval.py:110-124, :170-178, :236-244).
+
+        runner = GraphedInference(net)          # net: a PointConvBig (wrapped in a default InferenceNet) or an InferenceNet,
+        logits = runner(batch)                  # e.g. InferenceNet(model, fused_head=True); logits [B N, C], the caller's own
+
+    ``models.PointConvBig`` keeps one of its own for its eval-mode calls under ``no_grad`` (autograph_eval_forward), so the
+    reference's validation lines need no edit.  The first qualifying call captures (after `warmup` >= 2 eager passes on a side
+    stream: a table's first mean-field forward takes another form than its later ones, ops/crf.py), into a memory pool of its own;
+    later batches of the SAME shapes are copied into the captured batch's buffers and replayed on the caller's current stream.  ONE
+    signature is held.  What runs the network eagerly instead, counted by reason (stats): grad enabled ('grad': the caller gets a
+    differentiable output), training mode ('training': BatchNorm statistics advance there), no device MultiScaleData ('batch'),
+    features that are not float32 ('dtype'), a call during another stream capture ('capturing': issued inline, as SceneVoter needs
+    it), module or global hooks ('hooks'), a set ``phase_hook`` ('phase': the forward calls it, a replay would not), decoders swapped for
+    a mix InferenceNet does not take ('model'), other shapes ('shape').  The model's own runner never calls the model again: it
+    hands such a call back to the model's forward, so hooks on the model fire once.  Weights and running statistics are read where they live at
+    every replay: in-place updates (an optimizer step, load_state_dict) need nothing; parameters or buffers that are other objects
+    or sit at other addresses than at the capture drop the graph, and the next call captures again -- at once: there is no
+    autograd graph to wait for.  Eval mode mutates no buffer, so the warm-up has nothing to undo."""
+
+    def __init__(self, net, warmup=2):
+        from .infer import InferenceNet
+        self.target = net                                       # what an eager call runs: the caller's own object
+        self.own = not isinstance(net, InferenceNet)            # (our wrapper is outside the model's tree: eval() does not reach it)
+        self.net = InferenceNet(net) if self.own else net
+        self.model = self.net.model
+        self.warmup = max(int(warmup), 2)
+        self.captures, self.replays, self.eager = 0, 0, collections.Counter()
+        self.graph = self.static = self.static_out = self._sig = None
+
+    _signature = staticmethod(GraphedModel._signature)
+    _snapshot = GraphedModel._snapshot                          # slots, addresses and hook dictionaries of self.model
+    _moved = GraphedModel._moved
+
+    def hooked(self):
+        if self.graph is None:
+            return _has_hooks(self.model)
+        return _global_hooks() or any(self._hooks)
+
+    def _drop_graph(self):
+        self.graph = self.static = self.static_out = self._sig = None
+
+    def _eager(self, batch, why):
+        self.eager[why] += 1
+        with no_autograph():
+            return self.target(batch)
+
+    def _capture(self, batch):
+        self.captures += 1
+        gc.collect()                                            # (as GraphedModel._capture: no graph may be destroyed inside a capture)
+        was = gc.isenabled()
+        gc.disable()
+        try:
+            with no_autograph(), torch.no_grad():
+                self.static = batch._apply(torch.clone)
+                self._sig = self._signature(batch)
+                side = torch.cuda.Stream()
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):
+                    for _ in range(self.warmup):                # lazily built tables, the coefficient buffer, the mean field's settled form
+                        self.net(self.static)
+                torch.cuda.current_stream().wait_stream(side)
+                torch.cuda.synchronize()
+                self.graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.graph, pool=torch.cuda.graph_pool_handle(), capture_error_mode='thread_local'):
+                    self.static_out = self.net(self.static)
+                self._snapshot()
+        except BaseException:
+            self._drop_graph()
+            raise
+        finally:
+            if was:
+                gc.enable()
+
+    def refusal(self, batch):
+        """Why this call cannot be a replay -- one word (the keys of stats()['eval']['eager']) -- or None."""
+        if torch.is_grad_enabled():
+            return 'grad'
+        if self.own:
+            self.net.training = self.model.training
+        if self.model.training or self.net.training:
+            return 'training'
+        if not _device_batch(batch):
+            return 'batch'
+        if batch.x.dtype != torch.float32:
+            return 'dtype'
+        if torch.cuda.is_current_stream_capturing():
+            return 'capturing'
+        if self.hooked():
+            return 'hooks'
+        if self.model.phase_hook is not None:
+            return 'phase'                                      # (the forward calls it where a phase begins: a replay would not)
+        if self.graph is not None and self._moved():
+            self._drop_graph()
+        if self.graph is None:
+            from .infer import why_not
+            if why_not(self.model) is not None:
+                return 'model'                                  # decoders swapped since the wrapper was built
+        elif batch is not self.static and self._signature(batch) != self._sig:
+            return 'shape'
+        return None
+
+    def __call__(self, batch):
+        why = self.refusal(batch)
+        return self.replay(batch) if why is None else self._eager(batch, why)
+
+    def replay(self, batch):
+        """The logits of `batch` from one replay (the first one captures); the caller has asked refusal(batch)."""
+        if self.graph is None:
+            self._capture(batch)
+        if batch is not self.static:
+            self.static.load_(batch, defer_check=True)          # (no host synchronisation: a bad table raises at the next call)
+        self.graph.replay()
+        self.replays += 1
+        return self.static_out.clone()                          # the caller owns its logits: the next replay overwrites static_out

@@ -784,6 +784,10 @@ int crfconv_linear_forward_dropout(const float* X, const float* W, int64_t M, in
  *             crfconv_bn_apply_dropout (same seed / counter / element numbering e = row * Co + channel: identical logits);
  *             mask_bits [crfconv_head_mask_words(M)] uint32 receives the mask (one bit per element) for the backward;
  *             counter_used as in crfconv_bn_apply_dropout.
+ *             mask_bits == NULL selects the EVAL form, logits = lrelu(a (X W1^T) + b, slope) W2^T + b2: no counter is read, no
+ *             mask is formed or written, nothing is scaled.  It requires p == 0 (CRF_ERR_ARG otherwise); counter and counter_used
+ *             may be NULL and seed is ignored.  Its logits are bit-identical to a call with p = 0 and a mask buffer (which keeps
+ *             every element and scales by 1.f: the same float32 operations in the same order).
  *   backward: g [M, C2] = d loss / d logits  ->  dX [M, Ci] (may be NULL), dW1 [Co, Ci], dgamma / dbeta [Co], dW2 [C2, Co],
  *             db2 [C2] (may be NULL); workspace of crfconv_head_backward_workspace bytes.  Four launches: partial pass, float64
  *             totals, dX, parameters. */
