@@ -1,5 +1,5 @@
 // Sums of per-workgroup partial slabs, float64 results: out[slot] = sum_b partial[b][slot] -- one wavefront per (job, slot).  Shared by
-// pointconv.hip (crfconv_reduce_jobs_f64) and wgrad.hip (crfconv_reduce_jobs_both: these sums and the float weight-gradient sums of a
+// pointconv_fold.hip (crfconv_reduce_jobs_f64) and wgrad.hip (crfconv_reduce_jobs_both: these sums and the float weight-gradient sums of a
 // backward pass in ONE launch).
 #pragma once
 #include "common.hpp"

@@ -224,7 +224,7 @@ extern "C" int crfconv_reduce_jobs(const crf_reduce_job* jobs, int njobs, crf_st
     return CRF_OK;
 }
 
-// crfconv_reduce_jobs_f64 lives in pointconv.hip; the header declares it.
+// crfconv_reduce_jobs_f64 lives in pointconv_fold.hip; the header declares it.
 // Both kinds of sums of a backward pass in ONE launch when each fits one table (96 float jobs, 32 float64 jobs): same results as the
 // two calls.  Larger batches: the two calls.
 extern "C" int crfconv_reduce_jobs_both(const crf_reduce_job* jobs, int njobs, const crf_reduce64_job* jobs64, int njobs64,

@@ -272,13 +272,9 @@ int crfconv_similarity_bwd_scatter(const float* w, const float* y, const float* 
  * layer 1 (0.1 in point_conv_big.py:21, nn.LeakyReLU's default 0.01 in the sparse twin point_conv.py:24).
  * Table entries < 0 mean "no neighbour" (padded variable-degree tables): they contribute nothing. */
 
-/* First and second moments of rel over all edges: out9 = {sum x,y,z, sum xx,xy,xz,yy,yz,zz}
- * as float64 (BatchNorm-1 batch statistics are analytic in these). */
 size_t crfconv_pointconv_workspace(int64_t m_tgt, int K, int d);
-int crfconv_pointconv_moments(const float* pos_src, const float* pos_tgt, const int32_t* idx32,
-                              int K, int64_t m_tgt, double* out9, void* workspace,
-                              size_t workspace_bytes, crf_stream_t stream);
-/* The same sums finished on the device: mean [3] and covariance [3, 3] of rel over the n_edges edges, packed = {mean, cov} [12]
+/* First and second moments of rel over all edges ({sum x,y,z, sum xx,xy,xz,yy,yz,zz}: BatchNorm-1 batch statistics are analytic in
+ * these), finished on the device: mean [3] and covariance [3, 3] of rel over the n_edges edges, packed = {mean, cov} [12]
  * (the `mom` argument of fold1 / fold1_bwd) in float64 and the mean in float32, written into the CALLER's tensors -- a refresh
  * of a static batch recomputes them in place (two launches instead of ~17 and four copies). */
 int crfconv_pointconv_moments_packed(const float* pos_src, const float* pos_tgt, const int32_t* idx32, int K, int64_t m_tgt,
@@ -291,20 +287,15 @@ typedef struct { const float* pos_src; const float* pos_tgt; const int32_t* idx3
 size_t crfconv_pointconv_moments_batched_workspace(const crf_moments_job* jobs, int njobs);
 int crfconv_pointconv_moments_batched(const crf_moments_job* jobs, int njobs, void* workspace, size_t workspace_bytes,
                                       crf_stream_t stream);
-/* Batch statistics of h2 over all edges: stats [2, d] float64 = {sum(h2 - shift), sum (h2 - shift)^2},
- * shift [d] float32 out (= h2 at the mean rel; variance is shift-invariant). */
-int crfconv_pointconv_stats(const float* pos_src, const float* pos_tgt, const int32_t* idx32, int K,
-                            int64_t m_tgt, int d, const float* A1, const float* b1,
-                            const float* W2, float slope, const float* mean_rel3, float* shift, double* stats,
-                            void* workspace, size_t workspace_bytes, crf_stream_t stream);
 /* Training forward in ONE edge pass.  BatchNorm-2 is affine per channel, so
  *   out_i = a2 * U_i + (a2 * shift + b2) * V_i,   U_i = sum_k (h2_k - shift) * x_j,   V_i = sum_k x_j
- * (U, V [m_tgt, d] float32 out) and the batch statistics of h2 (stats, shift: as crfconv_pointconv_stats) come
- * out of the same pass; crfconv_pointconv_combine folds BatchNorm-2 (as crfconv_pointconv_fold2 in training mode:
+ * (U, V [m_tgt, d] float32 out) and the batch statistics of h2 over all edges come out of the same pass: stats [2, d] float64 =
+ * {sum(h2 - shift), sum (h2 - shift)^2}, shift [d] float32 out (= h2 at the mean rel, mean_rel3; variance is shift-invariant).
+ * crfconv_pointconv_combine folds BatchNorm-2 (as crfconv_pointconv_fold2 in training mode:
  * a2, b2, aux2 out, running statistics advanced) and finishes the convolution in one elementwise launch.
  * The backward reductions of BatchNorm-2 need no edge pass either:
  *   {sum_e g_w, sum_e g_w (h2 - shift)} = {sum_i gout_i * V_i, sum_i gout_i * U_i};
- * crfconv_pointconv_bwd_reduce_uv forms them and applies crfconv_pointconv_fold2_bwd (ca, cb, cc, dgamma2, dbeta2). */
+ * crfconv_pointconv_bwd_input_reduce forms them and applies crfconv_pointconv_fold2_bwd's arithmetic (ca, cb, cc, dgamma2, dbeta2). */
 int crfconv_pointconv_forward_uv(const float* x, const float* pos_src, const float* pos_tgt,
                                  const int32_t* idx32, int K, int64_t m_tgt, int d, const float* A1,
                                  const float* b1, const float* W2, float slope, const float* mean_rel3,
@@ -333,10 +324,6 @@ typedef struct {
     double n_edges; float* run_mean; float* run_var; float momentum; float eps;
     float* a2; float* b2; double* aux2; float* out;
 } crf_uv_fold;
-int crfconv_pointconv_bwd_reduce_uv(const float* gout, const float* U, const float* V, int64_t m_tgt, int d,
-                                    const float* shift, const double* aux2, const float* gamma2, double n_edges,
-                                    int use_batch, float* ca, float* cb, float* cc, float* dgamma2, float* dbeta2,
-                                    void* workspace, size_t workspace_bytes, unsigned* ticket, crf_stream_t stream);
 int crfconv_pointconv_forward(const float* x, const float* pos_src, const float* pos_tgt,
                               const int32_t* idx32, int K, int64_t m_tgt, int d, const float* A1,
                               const float* b1, const float* W2, float slope, const float* a2, const float* b2,
@@ -386,7 +373,7 @@ int crfconv_pointconv_bwd_dump_jobs(const crf_pc_dump_job* jobs, int njobs, crf_
  * target point, the three d x d products per edge (h2 = W2 h1, W2^T gh2, dW2 += gh2 (x) h1) on v_mfma_f32_16x16x4_f32.  Per
  * workgroup b < crfconv_pointconv_wide_params_nblk(m_tgt, d): dw2_partial[b] [d, d] float (row = output channel of W2) and
  * a1_partial[b] [d, 4] float64 ({dA1[c][0..2], db1[c]}); the caller sums the slabs (crfconv_reduce_jobs / crfconv_reduce_jobs_f64).
- * ca, cb, cc: the per-channel coefficients of crfconv_pointconv_bwd_reduce_uv (as crf_pc_dump_job).  One launch per width. */
+ * ca, cb, cc: the per-channel coefficients of crfconv_pointconv_bwd_input_reduce (as crf_pc_dump_job).  One launch per width. */
 typedef struct { const float* x; const float* gout; const float* pos_src; const float* pos_tgt; const int32_t* idx32; int K; int64_t m_tgt;
                  int d; const float* A1; const float* b1; const float* W2; float slope; const float* ca; const float* cb; const float* cc;
                  float* dw2_partial; double* a1_partial; } crf_pc_wide_job;
@@ -410,8 +397,10 @@ int crfconv_pointconv_bwd_input(const float* gout, const float* pos_src, const f
                                 int64_t m_src, int d, const float* A1, const float* b1,
                                 const float* W2, float slope, const float* a2, const float* b2, float* dx,
                                 crf_stream_t stream);
-/* crfconv_pointconv_bwd_input and the ticketed crfconv_pointconv_bwd_reduce_uv of one layer in ONE launch (round 5): the input gradient
- * needs the forward coefficients only and nothing reads the reduction's outputs before the next launch.  Same results as the two calls. */
+/* crfconv_pointconv_bwd_input and the layer's BatchNorm-2 backward reduction in ONE launch (round 5): extra workgroups form
+ * {sum_i gout_i * V_i, sum_i gout_i * U_i} over the m_tgt rows of U, V (block partials in `workspace`, float [<= 512][2 d]) and the last
+ * of them to finish (ticket, required) derives ca, cb, cc, dgamma2, dbeta2 as crfconv_pointconv_fold2_bwd does.  The input gradient
+ * needs the forward coefficients only and nothing reads the reduction's outputs before the next launch. */
 int crfconv_pointconv_bwd_input_reduce(const float* gout, const float* pos_src, const float* pos_tgt, const int32_t* rev_ptr,
                                        const int32_t* rev_eid, int K, int64_t m_src, int64_t m_tgt, int d, const float* A1, const float* b1,
                                        const float* W2, float slope, const float* a2, const float* b2, float* dx, const float* U,
@@ -425,7 +414,7 @@ int crfconv_pointconv_bwd_input_reduce(const float* gout, const float* pos_src, 
  *             statistics updated in place when use_batch != 0 and non-NULL; aux1 [3,d] float64 saved for backward.
  *  fold1_bwd  dA1b1 [d,4] float64 -> dW1 [d,3], dgamma1, dbeta1 (through the analytic statistics); when dW2_f64 [d,d] (the
  *             float64 accumulator of crfconv_pointconv_bwd_params) is given, also dW2_f32 = (float) dW2_f64 (both or neither NULL).
- *  fold2      stats [2,d] + shift (crfconv_pointconv_stats) -> a2, b2; aux2 [2,d] = {mean2, rstd2}.
+ *  fold2      stats [2,d] + shift (crfconv_pointconv_forward_uv) -> a2, b2; aux2 [2,d] = {mean2, rstd2}.
  *  fold2_bwd  red [2,d] (crfconv_pointconv_bwd_reduce) -> ca, cb, cc for pass 2, dgamma2, dbeta2. */
 int crfconv_pointconv_fold1(const float* W1, const float* gamma1, const float* beta1, const double* mom,
                             double n_edges, float* run_mean, float* run_var, float momentum, float eps,
@@ -524,7 +513,7 @@ int crfconv_mlp_small_forward_join_uv(const crf_uv_fold* f, const float* W, int6
  * and writes dX = gY W (skipped when dX is NULL).  gA, Y [M, Co]; X [M, Ci]; W [Co, Ci]; coef = the [4, Co] block of
  * crfconv_bn_forward / crfconv_bn_coef_from_records for Y.  Same results as crfconv_bn_backward ->
  * crfconv_linear_forward(transpose) + crfconv_linear_wgrad up to summation order.
- * ticket (crfconv_mlp_backward / _add / _cat, crfconv_pointconv_forward_uv / _bwd_reduce_uv): crfconv_ticket_bytes() ZERO device
+ * ticket (crfconv_mlp_backward / _add / _cat, crfconv_pointconv_forward_uv / _bwd_input_reduce): crfconv_ticket_bytes() ZERO device
  * bytes owned by the stream (the kernels leave them zero; large launches draw their tickets in two levels, one 128-byte line per
  * group), or NULL.  With it the LAST workgroup of the first pass to finish adds the partial rows and
  * does the finalize's channel part itself (write-through stores, one atomic ticket per workgroup, fixed summation order): one

@@ -38,7 +38,7 @@ if '--pointconv-json' in sys.argv:
         d = blocks[k]
         return (2 * d['FETCH_SIZE'][0] + d['WRITE_SIZE'][0]) * 1024
     fwd = hbm('crf::uvstats_kernel<8>') + sum(hbm(k) for k in blocks if k.startswith('crf::uv_combine_kernel') or k.startswith('crf::reduce_partials_kernel')) * 0  # see note
-    srcs = ['crfconv_amd/csrc/pointconv.hip']
+    srcs = ['crfconv_amd/csrc/pointconv.hip', 'crfconv_amd/csrc/pointconv_common.hpp']
     h = hashlib.sha1()
     for s_ in srcs:
         h.update(open(os.path.join(ROOT, s_), 'rb').read())

@@ -378,12 +378,19 @@ def test_pointconv_module_golden(golden, form, mode):
                 assert_close(sd[k], v, 1e-5, k)
 
 
-@pytest.mark.parametrize('d,deferred', [(4, False), (16, False), (32, False), (64, False), (128, False), (16, True), (32, True),
-                                        (64, True), (128, True)])
-def test_pointconv_widths_vs_oracle(d, deferred):
+# (the training cases keep the ids they had before there was a mode)
+@pytest.mark.parametrize('d,deferred,mode',
+                         [pytest.param(d, df, 'train', id='%d-%s' % (d, df))
+                          for d, df in [(4, False), (8, False), (16, False), (32, False), (64, False), (128, False), (8, True), (16, True),
+                                        (32, True), (64, True), (128, True)]]
+                         + [pytest.param(d, False, 'eval', id='%d-eval' % d) for d in (4, 8, 16, 32, 64, 128)])
+def test_pointconv_widths_vs_oracle(d, deferred, mode):
     """PointConv forward, input gradient and every parameter gradient against the float32 oracle anchored on float64, all widths.
     deferred: the backward under ops.deferred_weight_grads -- the wide layers' parameter pass then runs at the end of the pass, at
-    d = 32 / 64 as ONE matrix-pipe launch without per-edge tensors (csrc/pointconv_wide.hip), at d = 128 as dump + GEMM passes."""
+    d = 32 / 64 as ONE matrix-pipe launch without per-edge tensors (csrc/pointconv_wide.hip), at d = 128 as dump + GEMM passes.
+    mode 'eval': running statistics instead of batch statistics -- the entries a training step never takes (forward_kernel,
+    bwd_reduce_kernel, the input gradient without its riding reduction, fold2 / fold2_bwd), at every width."""
+    training = mode == 'train'
     from crfconv_amd import ops
     from crfconv_amd.models import PointConv
     B, N, K = 2, 200, 16
@@ -397,12 +404,12 @@ def test_pointconv_widths_vs_oracle(d, deferred):
         prm = {k: (v.to(dtype) if v.is_floating_point() else v).clone().requires_grad_(
             v.is_floating_point() and 'running' not in k) for k, v in sd.items()}
         xr = torch.from_numpy(x).to(dtype).requires_grad_(True)
-        ref = O.point_conv(prm, '', xr, torch.from_numpy(pos).to(dtype), torch.from_numpy(nbr), True)
+        ref = O.point_conv(prm, '', xr, torch.from_numpy(pos).to(dtype), torch.from_numpy(nbr), training)
         (ref * torch.from_numpy(gout).to(dtype)).sum().backward()
         return prm, xr, ref
     prm, xr, ref = oracle(torch.float32)
     prm64, xr64, ref64 = oracle(torch.float64)
-    m = m.to(DEV).train()
+    m = m.to(DEV).train(training)
     xd = t(x).requires_grad_(True)
     out = m(xd, t(pos), t(nbr))
     with ops.deferred_weight_grads(enabled=deferred):
@@ -415,7 +422,9 @@ def test_pointconv_widths_vs_oracle(d, deferred):
     P64 = torch.from_numpy(pos).double()
     rel = (P64.unsqueeze(2) - O._rows(P64, torch.from_numpy(nbr))).reshape(-1, 3)
     h = rel @ sd['weight_nn.0.lin.weight'].double().t()
-    pre = (h - h.mean(0)) / torch.sqrt(h.var(0, unbiased=False) + 1e-5) * sd['weight_nn.0.bn.batch_norm.weight'].double() \
+    mean, var = (h.mean(0), h.var(0, unbiased=False)) if training else \
+        (sd['weight_nn.0.bn.batch_norm.running_mean'].double(), sd['weight_nn.0.bn.batch_norm.running_var'].double())
+    pre = (h - mean) / torch.sqrt(var + 1e-5) * sd['weight_nn.0.bn.batch_norm.weight'].double() \
         + sd['weight_nn.0.bn.batch_norm.bias'].double()
     ok = (pre.abs().min(0).values > 1e-5).to(DEV)
     for k, v in grads(m).items():
