@@ -1,4 +1,4 @@
-// BatchNorm from the per-workgroup statistic records that the Linear kernels leave in their epilogue (linear_fwd.hpp, gemm.hip)
+// BatchNorm from the per-workgroup statistic records that the Linear kernels leave in their epilogue (linear_fwd.hpp, gemm_stats.hip)
 // instead of a statistics pass over y: the coefficients alone (bn_finalize_records_kernel), or coefficients and apply
 // (+ the ResNet join) in one launch, for one layer or up to four independent ones.
 #include "common.hpp"

@@ -2,7 +2,7 @@
 //   out = a2 U + (a2 shift + b2) V
 // of the training forward (pointconv.hip: uvstats_body leaves U, V, stats and shift).  ONE arithmetic for every kernel that forms
 // `out`: uv_combine_kernel (the elementwise pass), and the Linear kernels that form it while they load their operand -- lin_out of the
-// ResNet block is the only forward reader of `out`, so the pass of its own disappears (linear_fwd.hpp, gemm.hip, mlp_small.hip).  Every consumer
+// ResNet block is the only forward reader of `out`, so the pass of its own disappears (linear_fwd.hpp, gemm_stats.hip, mlp_small.hip).  Every consumer
 // derives bit-identical a2, b2, mean, rstd and the same `out`.
 #pragma once
 

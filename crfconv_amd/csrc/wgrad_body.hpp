@@ -1,6 +1,5 @@
 // The weight-gradient partial pass  partial[slice][co][ci] = sum_{rows of the slice} G[r][co] X[r][ci]  as a device routine with its job
-// table, shared by the translation units that run it: wgrad.hip (the pass's own launches) and gemm.hip (round 5: the pending
-// passes of a backward ride as SIDE jobs on the coarse-level launches of the chain, whose own workgroups cover a fraction of the chip).
+// table: wgrad.hip runs it (one pass, or the pending passes of a backward as jobs of one launch); mlp_bwd.hip shares its block constants.
 #pragma once
 #include "common.hpp"
 

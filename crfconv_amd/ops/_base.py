@@ -182,11 +182,11 @@ class _State:
     # set by check_gridsync after a barrier failure (CRFCONV_NO_ONE_LAUNCH_MLP: from the start): launch-separated forward from then on
     small_mlp_disabled = __import__('os').environ.get('CRFCONV_NO_ONE_LAUNCH_MLP') is not None
     # the two launches of a coarse-level MLP backward (tile sums, dX product) as one whose product workgroups wait for the sums inside
-    # the launch (csrc/gemm.hip mlp_small_bwd_jobs_kernel); CRFCONV_SMALL_BWD_TWO_LAUNCHES=1: A/B runs of bench.py
+    # the launch (csrc/mlp_small_bwd.hip mlp_small_bwd_jobs_kernel); CRFCONV_SMALL_BWD_TWO_LAUNCHES=1: A/B runs of bench.py
     small_bwd_one_launch = __import__('os').environ.get('CRFCONV_SMALL_BWD_TWO_LAUNCHES') is None
     # the backward of the CRF layers' matrices as riders of the MLP blocks' end-of-pass weight-gradient launch (defer._flush_mlp_dw)
     dw_hosts_mats = __import__('os').environ.get('CRFCONV_NO_TAIL_RIDERS') is None
-    # below this many rows the tiled product (gemm.hip) and the small-MLP nodes; swept on the step: 4096 -> 4.733 ms, 12288 (the
+    # below this many rows the tiled product (gemm.hip, gemm_stats.hip) and the small-MLP nodes; swept on the step: 4096 -> 4.733 ms, 12288 (the
     # 10 240-row level joins the small forms) -> 4.694 ms, 65536 -> 4.736 ms
     mfma_min_rows = 12288
     # the mean-field forward as one launch with block-resident rows (csrc/crf_block.hip; ops.crf._block_rows): 'auto' | 'on' | 'off'

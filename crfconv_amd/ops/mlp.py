@@ -444,7 +444,7 @@ def _small_bwd_jobs(jobs, n, dev, st):
 
 def _mlp_bwd_jobs(blocks):
     """The crf_mlp_bwd_job array of coarse-level blocks, each (gA, y, coef, W, add, slope, gY, dX, dgamma, dbeta, ws, mask); mask:
-    None or (ref [M, Ci], slope) -- without a reference the kernels do not read the mask slope (csrc/gemm.hip)."""
+    None or (ref [M, Ci], slope) -- without a reference the kernels do not read the mask slope (csrc/mlp_small_bwd.hip)."""
     jobs = (_lib.MlpBwdJob * len(blocks))()
     for i, (gA, y, coef, W, add, slope, gY, dX, dgamma, dbeta, ws, mask) in enumerate(blocks):
         m, co = y.shape

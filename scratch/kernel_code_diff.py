@@ -7,7 +7,8 @@ A side is a set of source files, compiled here with the library's flags (csrc/Ma
 whose *.o have their gfx950 code object unbundled.  Per kernel symbol of either side: only-left, only-right, identical or DIFFERS, with
 the number of instruction encoding words up to the kernel's last s_endpgm, and the resource block of the code object's metadata (SGPRs,
 VGPRs, AGPRs, scratch, LDS, spills; from source also the occupancy of the compiler's resource-usage remarks).  The two sides are only
-compared with each other.  Exit status 1 when a kernel that both sides have differs."""
+compared with each other.  Exit status 1 when a kernel that both sides have differs.  --rename REGEX REPL matches the kernels by their
+demangled names after that substitution: a kernel whose parameter list changed (profiles/r15_gemm_split.md)."""
 import argparse
 import glob
 import os
@@ -87,6 +88,8 @@ def main():
     ap.add_argument('--left', nargs='+', required=True)
     ap.add_argument('--right', nargs='+', required=True)
     ap.add_argument('-q', '--quiet', action='store_true', help='list only the kernels that are not identical')
+    ap.add_argument('--rename', nargs=2, metavar=('REGEX', 'REPL'),
+                    help='re.sub on the demangled names of both sides before matching (a kernel whose parameter list changed)')
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         left, right = side(a.left, tmp), side(a.right, tmp)
@@ -95,6 +98,11 @@ def main():
     base = [k.split(' @')[0] for k in names]
     plain = subprocess.check_output([filt] + base, text=True).splitlines() if filt and names else base
     pretty = {k: p + k[len(b):] for k, b, p in zip(names, base, plain)}
+    if a.rename:                                             # kernels are matched by their demangled, rewritten names
+        pretty = {k: re.sub(a.rename[0], a.rename[1], p) for k, p in pretty.items()}
+        left, right = ({pretty[k]: v for k, v in s.items()} for s in (left, right))
+        names = sorted(set(left) | set(right))
+        pretty = {k: k for k in names}
     count = {'only-left': 0, 'only-right': 0, 'identical': 0, 'DIFFERS': 0}
     words = 0
     for k in names:

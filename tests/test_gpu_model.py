@@ -1831,7 +1831,7 @@ def test_linear_forward_mfma_and_fused_stats(M, Ci, Co, bias):
 def test_gemm_kernel_vs_float64(M, N, K, nk):
     """crfconv_gemm (csrc/gemm.hip: the coarse-level Linear forward and every dX / g_h1 product that used to be a vendor
     GEMM) against float64 torch, with and without the bias / addend epilogue, ragged tile edges included; bitwise
-    reproducible; every tile shape (CRFCONV_GEMM_TILE is read once, so the shapes are forced through the row count)."""
+    reproducible.  Every size here takes the 32 x 32 tile; test_gemm_every_tile_shape runs the larger ones."""
     from crfconv_amd import _lib
     from crfconv_amd.ops import ptr, stream_ptr, _gemm
     g = torch.Generator().manual_seed(M + N + K)
@@ -1851,6 +1851,59 @@ def test_gemm_kernel_vs_float64(M, N, K, nk):
     _lib.call('crfconv_gemm', ptr(A), ptr(B), None, ptr(acc), M, N, K, nk, ptr(acc), stream_ptr())
     torch.cuda.synchronize()
     assert float((acc.double() - (ref + add.double())).abs().max()) <= 2e-6 * (scale + 8.0)
+
+
+@pytest.mark.parametrize('nk', [0, 1])
+@pytest.mark.parametrize('M,N', [(65473, 256), (65473, 254), (32737, 256), (32737, 254), (262081, 32), (262081, 30)])
+def test_gemm_every_tile_shape(M, N, nk):
+    """The three larger tile shapes of crfconv_gemm / crfconv_gemm_bn_act, at the smallest sizes that select them (the launcher takes
+    the largest shape that still gives 4096 workgroups), each with a ragged last row tile:
+      64 x 64:  65 473 rows x 256 | 254 columns = 1024 x 4 tiles of 64 x 64;
+      32 x 64:  32 737 rows x 256 | 254 = 512 x 4 = 2048 tiles of 64 x 64, 1024 x 4 = 4096 of 32 x 64;
+      64 x 32: 262 081 rows x 32 | 30 = 4096 x 1 tiles of 64 x 32.
+    The entry points are called directly, so no row-count switch of ops redirects a size.  K = 8 with the aligned N is the 16-byte form
+    (one chunk, zero-filled past K), K = 6 with the odd N the element-wise form.  crfconv_gemm with bias and addend against the float64
+    product, twice with equal bits; for N % 4 == 0, at K = 8 and K = 6, crfconv_gemm_bn_act bit-equal to crfconv_gemm ->
+    crfconv_bn_apply (-> crfconv_add_lrelu with a skip): the identity the C header states for that entry."""
+    from crfconv_amd import _lib
+    from crfconv_amd.ops import ptr, stream_ptr
+    g = torch.Generator().manual_seed(M + 3 * N + nk)
+    bias, add = torch.randn(N, generator=g).to(DEV), torch.randn(M, N, generator=g).to(DEV)
+
+    def operands(K):
+        A = torch.randn(M, K, generator=g).to(DEV)
+        return A, (torch.randn(N, K, generator=g) if nk else torch.randn(K, N, generator=g)).to(DEV)
+
+    def gemm(A, B, bias, add):
+        C = torch.full((M, N), float('nan'), device=DEV)
+        _lib.call('crfconv_gemm', ptr(A), ptr(B), ptr(bias), ptr(add), M, N, A.shape[1], nk, ptr(C), stream_ptr())
+        return C
+
+    K = 8 if N % 4 == 0 else 6
+    A, B = operands(K)
+    ref = A.double() @ (B.double().t() if nk else B.double())
+    scale = float(ref.abs().max())
+    C = gemm(A, B, bias, add)
+    err = float((C.double() - (ref + bias.double() + add.double())).abs().max())
+    print('gemm %d x %d x %d nk=%d: max error %.3e, bound %.3e' % (M, N, K, nk, err, 2e-6 * (scale + 8.0)))
+    assert err <= 2e-6 * (scale + 8.0)
+    assert torch.equal(C, gemm(A, B, bias, add))
+    if N % 4:
+        return
+    coef = torch.cat([1.0 + 0.25 * torch.randn(1, N, generator=g), torch.randn(1, N, generator=g)]).to(DEV)
+    for K in (8, 6):
+        if K != A.shape[1]:
+            A, B = operands(K)
+        for skip, slope in ((add, 0.1), (None, 1.0)):
+            y = gemm(A, B, bias, None)
+            want = torch.full_like(y, float('nan'))
+            _lib.call('crfconv_bn_apply', ptr(y), M, N, ptr(coef), 1.0 if skip is not None else slope, ptr(want), stream_ptr())
+            if skip is not None:
+                normed, want = want, torch.full_like(y, float('nan'))
+                _lib.call('crfconv_add_lrelu', ptr(normed), ptr(skip), want.numel(), slope, ptr(want), stream_ptr())
+            got = torch.full_like(y, float('nan'))
+            _lib.call('crfconv_gemm_bn_act', ptr(A), ptr(B), ptr(bias), ptr(coef), ptr(skip), slope, M, N, K, nk, ptr(got), stream_ptr())
+            assert torch.equal(got, want), 'gemm_bn_act K=%d skip=%s: %d elements differ' % (K, skip is not None, int((got != want).sum()))
 
 
 @pytest.mark.parametrize('M,N,K,nk', [(10, 6, 8, 0), (10, 8, 6, 0), (2000, 13, 128, 1), (2000, 128, 13, 0), (333, 7, 5, 1), (65, 1, 1, 0),
