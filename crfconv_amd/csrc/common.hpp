@@ -57,6 +57,23 @@ inline hipStream_t as_stream(crf_stream_t s) { return reinterpret_cast<hipStream
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// The one place where a run-time width picks a template instantiation: f(std::integral_constant<int, D>{}) for the D of the list
+// that equals d.  Returns whether there was one -- a width outside the list is the caller's CRF_ERR_UNSUPPORTED.
+template <int... Ds>
+struct Widths {};
+
+template <int... Ds, class F>
+inline bool dispatch_width(Widths<Ds...>, int d, F&& f) {
+    return ((d == Ds && (f(std::integral_constant<int, Ds>{}), true)) || ...);
+}
+
+// The same for a run-time flag that is a bool template argument: f(std::true_type{}) or f(std::false_type{}).
+template <class F>
+inline void dispatch_flag(bool on, F&& f) {
+    if (on) f(std::true_type{});
+    else f(std::false_type{});
+}
+
 // ----------------------------------------------------------------------------- device helpers
 // XCD-aware block order.  MI355X deals workgroups round-robin over its 8 XCDs (block b -> XCD b % 8),
 // each with a private 4 MiB L2.  Kernels here walk spatially sorted points and gather neighbour rows,

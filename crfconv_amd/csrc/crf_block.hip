@@ -492,8 +492,10 @@ int device_cus() {
 template <int H, int K, int NW, int HP>
 int launch_block(const float* z, const float* y, const int32_t* idx32, const uint16_t* idx16, int n_tgt, int n_src, int64_t m,
                  const float* Q, const float* P, int T, float* s, float* xs, unsigned* ws, int nblk, hipStream_t st) {
-    if (idx16) hipLaunchKernelGGL((mf_block_kernel<H, K, NW, HP, true>), dim3((unsigned)nblk), dim3(NW * WAVE), 0, st, y, z, idx32, idx16, n_tgt, n_src, Q, P, s, xs, m, T, ws, (unsigned long long*)nullptr);
-    else hipLaunchKernelGGL((mf_block_kernel<H, K, NW, HP, false>), dim3((unsigned)nblk), dim3(NW * WAVE), 0, st, y, z, idx32, idx16, n_tgt, n_src, Q, P, s, xs, m, T, ws, (unsigned long long*)nullptr);
+    dispatch_flag(idx16 != nullptr, [&](auto U16) {
+        hipLaunchKernelGGL((mf_block_kernel<H, K, NW, HP, decltype(U16)::value>), dim3((unsigned)nblk), dim3(NW * WAVE), 0, st, y, z, idx32,
+                           idx16, n_tgt, n_src, Q, P, s, xs, m, T, ws, (unsigned long long*)nullptr);
+    });
     CRF_LAUNCH_CHECK();
     return CRF_OK;
 }
@@ -518,8 +520,7 @@ extern "C" int crfconv_meanfield_forward_block(const float* z, const float* y, c
     if (int rc = check_common(m, H, K, k0)) return rc;
     CRF_REQUIRE(z && y && idx32 && Q && P && xs && ws, CRF_ERR_ARG, "null pointer");
     CRF_REQUIRE(s || T == 1, CRF_ERR_ARG, "s == NULL needs T == 1");
-    CRF_REQUIRE(idx16 == nullptr || (n_tgt > 0 && n_src > 0 && n_src <= 65536 && m % n_tgt == 0), CRF_ERR_ARG,
-                "u16 table needs n_src <= 65536 and m a multiple of n_tgt (n_tgt=%d n_src=%d)", n_tgt, n_src);
+    if (int rc = check_u16(idx16, n_tgt, n_src, m)) return rc;
     CRF_REQUIRE(crfconv_meanfield_forward_block_rows(m, H, K, k0, T) > 0, CRF_ERR_UNSUPPORTED,
                 "block-resident mean field: shape m=%lld H=%d K=%d k0=%d T=%d is not covered", (long long)m, H, K, k0, T);
     const BlkPlan pl = plan_for<8>(m, device_cus());

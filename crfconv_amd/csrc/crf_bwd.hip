@@ -622,19 +622,18 @@ __global__ __launch_bounds__(BLOCK, (H <= 16 && K == 16) ? EDGE_LB : 1) void bwd
 
 using namespace crf;
 
-extern "C" int crfconv_meanfield_backward_supported(int H, int K, int k0) {
-    return (k0 == 1 && (K == 16 || K == 32) && (H == 4 || H == 8 || H == 16 || H == 32 || H == 64)) ? 1 : 0;
-}
+extern "C" int crfconv_meanfield_backward_supported(int H, int K, int k0) { return (fast_shape(K, k0) && crf_width(H)) ? 1 : 0; }
 
 // 1 when dP and dQ come out of the backward launches themselves (H in {8, 16}); 0 when the caller finishes them from
 // mts / Gs / sumG with crfconv_linear_wgrad
 extern "C" int crfconv_meanfield_backward_param_grads_inside(int H) { return (H == 8 || H == 16) ? 1 : 0; }
 
+// bytes of the workspace and where its parts begin; 0 for an H that is no mean-field width
 static size_t bwd_ws_layout(int64_t m, int H, int K, size_t* off_dp, size_t* off_dq, size_t* off_scratch) {
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     size_t o = up((size_t)m * K * sizeof(RevEdge));
     size_t nb_edge = 0;
-    DISPATCH_H(H, { nb_edge = (size_t)cdiv(m, Geo<HH>::PPB); });
+    if (!dispatch_width(CRF_WIDTHS, H, [&](auto HC) { nb_edge = (size_t)cdiv(m, Geo<decltype(HC)::value>::PPB); })) return 0;
     *off_dp = o; o = up(o + nb_edge * H * H * 4);
     *off_dq = o; o = up(o + nb_edge * H * H * 4);
     *off_scratch = o; o = up(o + 2 * RS_CHUNKS * (size_t)H * H * 4);
@@ -654,20 +653,12 @@ static void launch_rev(const RevArgs& ra, int64_t m, hipStream_t st) {
     constexpr int TR = MODE == REV_FINAL ? (HH <= 8 ? REV_TR_FINAL : 1) : (HH <= 8 ? REV_TR_CHAIN : (HH == 16 ? 2 : 8));
     const unsigned nb = (unsigned)cdiv(m, Rev<HH, EPV>::RPB) + (MODE == REV_FINAL ? (unsigned)ra.n_reduce : 0u);
     const bool oob = REV_PAD_OOB && CRF_GATHER_SRD && m * ra.K * 8 < (int64_t)0xFFFFFFF0u;      // the record table as one buffer resource
-    if (ra.K == 16) {
-        if (oob) hipLaunchKernelGGL((bwd_rev_kernel<HH, EPV, TR, MODE, FIRST, 4, true>), dim3(nb), dim3(Rev<HH, EPV>::NW * WAVE), 0, st, ra);
-        else hipLaunchKernelGGL((bwd_rev_kernel<HH, EPV, TR, MODE, FIRST, 4, false>), dim3(nb), dim3(Rev<HH, EPV>::NW * WAVE), 0, st, ra);
-    } else {
-        if (oob) hipLaunchKernelGGL((bwd_rev_kernel<HH, EPV, TR, MODE, FIRST, 5, true>), dim3(nb), dim3(Rev<HH, EPV>::NW * WAVE), 0, st, ra);
-        else hipLaunchKernelGGL((bwd_rev_kernel<HH, EPV, TR, MODE, FIRST, 5, false>), dim3(nb), dim3(Rev<HH, EPV>::NW * WAVE), 0, st, ra);
-    }
-}
-
-template <int HH, int KK, typename... A>
-static void launch_edge_all(dim3 grid, hipStream_t st, const float* gout, const float* Gs, const float* xs, const float* z,
-                            const float* y, const float* s, const int32_t* idx32, const uint16_t* idx16, A... rest) {
-    if (idx16) hipLaunchKernelGGL((bwd_edge_all_kernel<HH, KK, true>), grid, dim3(BLOCK), 0, st, gout, Gs, xs, z, y, s, idx32, idx16, rest...);
-    else hipLaunchKernelGGL((bwd_edge_all_kernel<HH, KK, false>), grid, dim3(BLOCK), 0, st, gout, Gs, xs, z, y, s, idx32, idx16, rest...);
+    dispatch_flag(ra.K == 16, [&](auto K16) {           // KSH = log2 K: 4 or 5
+        dispatch_flag(oob, [&](auto OOB) {
+            hipLaunchKernelGGL((bwd_rev_kernel<HH, EPV, TR, MODE, FIRST, decltype(K16)::value ? 4 : 5, decltype(OOB)::value>), dim3(nb),
+                               dim3(Rev<HH, EPV>::NW * WAVE), 0, st, ra);
+        });
+    });
 }
 
 extern "C" int crfconv_meanfield_backward(const float* gout, const float* z, const float* y, const float* s,
@@ -691,9 +682,7 @@ extern "C" int crfconv_meanfield_backward(const float* gout, const float* z, con
     const size_t need = bwd_ws_layout(m, H, K, &off_dp, &off_dq, &off_scratch);
     CRF_REQUIRE(ws_bytes >= need && (reinterpret_cast<uintptr_t>(ws) & 15) == 0, CRF_ERR_ARG,
                 "workspace of %zu bytes (16-byte aligned), need %zu", ws_bytes, need);
-    CRF_REQUIRE(idx16 == nullptr || (n_tgt > 0 && n_src > 0 && n_src <= 65536 && m % n_tgt == 0), CRF_ERR_ARG,
-                "u16 table needs n_src <= 65536 and m a multiple of n_tgt (n_tgt=%d n_src=%d)", n_tgt, n_src);
-    CRF_REQUIRE(m * H * 4 < ((int64_t)1 << 31), CRF_ERR_ARG, "m H = %lld rows x channels exceed 32-bit byte offsets", (long long)(m * H));
+    if (int rc = check_u16(idx16, n_tgt, n_src, m)) return rc;
     hipStream_t st = as_stream(stream);
     char* wsb = static_cast<char*>(ws);
     RevEdge* rec = reinterpret_cast<RevEdge*>(wsb);
@@ -701,7 +690,8 @@ extern "C" int crfconv_meanfield_backward(const float* gout, const float* z, con
     float* dq_partial = reinterpret_cast<float*>(wsb + off_dq);
     float* scratch = reinterpret_cast<float*>(wsb + off_scratch);
     const int64_t step = m * H;
-    DISPATCH_H(H, {
+    auto launches = [&](auto HC) -> int {
+        constexpr int HH = decltype(HC)::value;
         const dim3 grid((unsigned)cdiv(m, Geo<HH>::PPB));
         RevArgs ra{};
         ra.rev_ptr = rev_ptr; ra.rev_eid = rev_eid; ra.s = s; ra.P = P; ra.K = K; ra.m = m;
@@ -716,8 +706,12 @@ extern "C" int crfconv_meanfield_backward(const float* gout, const float* z, con
             CRF_LAUNCH_CHECK();
         }
         float* gcopy = mts != nullptr ? Gs : nullptr;
-        if (K == 16) launch_edge_all<HH, 16>(grid, st, gout, Gs, xs, z, y, s, idx32, idx16, n_tgt, n_src, P, Q, T, mts, gcopy, sumG, dzq, dp_partial, dq_partial, w, dy_self, m);
-        else launch_edge_all<HH, 32>(grid, st, gout, Gs, xs, z, y, s, idx32, idx16, n_tgt, n_src, P, Q, T, mts, gcopy, sumG, dzq, dp_partial, dq_partial, w, dy_self, m);
+        dispatch_width(Widths<16, 32>{}, K, [&](auto KC) {
+            dispatch_flag(idx16 != nullptr, [&](auto U16) {
+                hipLaunchKernelGGL((bwd_edge_all_kernel<HH, decltype(KC)::value, decltype(U16)::value>), grid, dim3(BLOCK), 0, st, gout, Gs, xs,
+                                   z, y, s, idx32, idx16, n_tgt, n_src, P, Q, T, mts, gcopy, sumG, dzq, dp_partial, dq_partial, w, dy_self, m);
+            });
+        });
         CRF_LAUNCH_CHECK();
         ra.Gin = T == 1 ? gout : Gs + (int64_t)(T - 1) * step;
         ra.Gprev = nullptr; ra.rec_out = nullptr;
@@ -731,6 +725,9 @@ extern "C" int crfconv_meanfield_backward(const float* gout, const float* z, con
         if (T == 1) launch_rev<HH, REV_FINAL, true>(ra, m, st);
         else launch_rev<HH, REV_FINAL, false>(ra, m, st);
         CRF_LAUNCH_CHECK();
-    });
-    return CRF_OK;
+        return CRF_OK;
+    };
+    int rc = CRF_OK;
+    dispatch_width(CRF_WIDTHS, H, [&](auto HC) { rc = launches(HC); });
+    return rc;
 }

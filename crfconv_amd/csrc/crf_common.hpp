@@ -1,5 +1,6 @@
-// Helpers shared by the mean-field translation units (crf.hip: forward + generic backward; crf_bwd.hip: the
-// restructured backward for K in {16, 32}, k0 = 1).  Thread mapping and layout: see the header of crf.hip.
+// Helpers shared by the mean-field translation units (crf.hip: the per-step forward; crf_step_bwd.hip: the per-step backward of
+// the generic path; crf_bwd.hip: the restructured backward for K in {16, 32}, k0 = 1; crf_block.hip: the one-launch forward;
+// crf_wide.hip: H = 128 / 256).  Thread mapping and layout: see the header of crf.hip.
 #pragma once
 #include "common.hpp"
 #include "gridsync.hpp"
@@ -121,13 +122,6 @@ __device__ __forceinline__ void load_index_offsets_t(const int32_t* __restrict__
 #pragma unroll
         for (int k = 0; k < K; ++k) off[k] = j[k] * RB + 16 * q;
     }
-}
-
-template <int K>
-__device__ __forceinline__ void load_index_row(const int32_t* __restrict__ idx32, const uint16_t* __restrict__ idx16,
-                                               int64_t r, int n_tgt, int n_src, int (&j)[K]) {
-    if (idx16 != nullptr) load_index_row_t<K, true>(idx32, idx16, r, n_tgt, n_src, j);
-    else load_index_row_t<K, false>(idx32, idx16, r, n_tgt, n_src, j);
 }
 
 // An H x H matrix on its way into LDS in two halves: fetch() issues the global loads into registers (branch-free, no
@@ -274,12 +268,26 @@ __device__ __forceinline__ void reduce_small_body(SmallJob j0, SmallJob j1, int 
     }
 }
 
+// The hidden widths every mean-field kernel below H = 128 is compiled for: dispatch_width(CRF_WIDTHS, H, ...) picks the instantiation.
+constexpr Widths<4, 8, 16, 32, 64> CRF_WIDTHS{};
+inline bool crf_width(int H) { return dispatch_width(CRF_WIDTHS, H, [](auto) {}); }
+
 inline int check_common(int64_t m, int H, int K, int k0) {
     CRF_REQUIRE(m > 0 && m < (int64_t)1 << 31, CRF_ERR_ARG, "rows m=%lld out of range", (long long)m);
-    CRF_REQUIRE(H == 4 || H == 8 || H == 16 || H == 32 || H == 64, CRF_ERR_UNSUPPORTED,
-                "hidden channels H=%d not in {4,8,16,32,64}", H);
+    CRF_REQUIRE(crf_width(H), CRF_ERR_UNSUPPORTED, "hidden channels H=%d not in {4,8,16,32,64}", H);
     CRF_REQUIRE(K >= 1 && K <= 64 && k0 >= 0 && k0 < K, CRF_ERR_ARG, "K=%d k0=%d invalid", K, k0);
     CRF_REQUIRE(m * K < (int64_t)1 << 31, CRF_ERR_ARG, "edge ids exceed int32 (m=%lld K=%d)", (long long)m, K);
+    return CRF_OK;
+}
+
+// The shapes of the fast kernels (index and weight rows as aligned dwordx4 loads held in registers, no self column).  The per-step
+// forward asks for row tables below 2 GiB on top of it (32-bit byte offsets); the restructured backward refuses larger ones.
+inline bool fast_shape(int K, int k0) { return k0 == 1 && (K == 16 || K == 32); }
+
+// uint16 per-cloud tables (load_index_row_t): what the decode  cloud * n_src + id, cloud = row / n_tgt  needs
+inline int check_u16(const uint16_t* idx16, int n_tgt, int n_src, int64_t m) {
+    CRF_REQUIRE(idx16 == nullptr || (n_tgt > 0 && n_src > 0 && n_src <= 65536 && m % n_tgt == 0), CRF_ERR_ARG,
+                "u16 table needs n_src <= 65536 and m a multiple of n_tgt (n_tgt=%d n_src=%d)", n_tgt, n_src);
     return CRF_OK;
 }
 
@@ -288,14 +296,5 @@ inline int kshift_of(int K) {
         if ((1 << sft) == K) return sft;
     return -1;
 }
-
-#define DISPATCH_H(H, ...)                                      \
-    switch (H) {                                                \
-        case 4: { constexpr int HH = 4; __VA_ARGS__; break; }   \
-        case 8: { constexpr int HH = 8; __VA_ARGS__; break; }   \
-        case 16: { constexpr int HH = 16; __VA_ARGS__; break; } \
-        case 32: { constexpr int HH = 32; __VA_ARGS__; break; } \
-        default: { constexpr int HH = 64; __VA_ARGS__; break; } \
-    }
 
 }  // namespace crf

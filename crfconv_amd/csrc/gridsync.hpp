@@ -1,6 +1,6 @@
 // Grid-wide arrival barrier for kernels whose workgroups are ALL resident at once (the host checks the grid against the
 // occupancy query), plus the write-through / L1-bypassing buffer accesses that carry data between workgroups inside one
-// launch.  Used by the one-launch mean-field forward (crf.hip) and the small-level Linear + BatchNorm kernels
+// launch.  Used by the one-launch mean-field forward (crf_block.hip) and the small-level Linear + BatchNorm kernels
 // (mlp_small.hip).
 //
 // Protocol (MI355X_MICROARCH.md, inter-workgroup visibility): a producer stores write-through (`sc1`), drains its stores

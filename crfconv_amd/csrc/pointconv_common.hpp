@@ -312,16 +312,8 @@ static int check_pc(int64_t m, int K, int d) {
     return CRF_OK;
 }
 
-// The one place where a run-time width picks a template instantiation: f(std::integral_constant<int, D>{}) for the D of the list
-// that equals d.  Returns whether there was one -- a width outside the list is the caller's CRF_ERR_UNSUPPORTED.
-template <int... Ds>
-struct Widths {};
+// the PointConv widths (dispatch_width: common.hpp)
 constexpr Widths<4, 8, 16, 32, 64, 128> ALL_WIDTHS{};
-
-template <int... Ds, class F>
-inline bool dispatch_width(Widths<Ds...>, int d, F&& f) {
-    return ((d == Ds && (f(std::integral_constant<int, Ds>{}), true)) || ...);
-}
 
 // workgroups of an edge kernel over m points (0: d is no PointConv width)
 template <int D>

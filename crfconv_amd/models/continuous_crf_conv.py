@@ -3,7 +3,7 @@
 Drop-ins for models/continuous_crf_conv.py:9-69 (`GuideGaussianCRFConv`) and :72-133
 (`ContinuousGaussianCRFConv`): constructor arguments, forward signatures and parameter names are the
 reference's.  The variable-degree graph is packed into a padded neighbour table
-(graph.table_from_edges) and runs through the same kernels as the dense layer (csrc/crf.hip, generic path
+(graph.table_from_edges) and runs through the same kernels as the dense layer (csrc/crf.hip and crf_step_bwd.hip, generic path
 with "no neighbour" entries)."""
 import torch
 import torch.nn as nn

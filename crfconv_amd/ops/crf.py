@@ -151,6 +151,7 @@ class _MeanField(torch.autograd.Function):
             return dz, dy, dQ, dP, None, None, None, None
 
         # generic shapes (any K <= 64 / k0, padded variable-degree tables): one edge + one scatter launch per step
+        # (csrc/crf_step_bwd.hip; the edge kernel is in csrc/crf.hip)
         gm = torch.empty_like(z)
         ds = torch.empty_like(s)
         # G_t (gradient entering step t) and m_t for t = T..1 stacked row-wise: dP = sum_t m_t^T G_t and
@@ -382,7 +383,7 @@ class _MeanFieldWide(torch.autograd.Function):
     """The mean-field loop for H in {128, 256} (the 256- / 128-channel GCRFConv stages of the sparse networks,
     models/point_conv.py:318-339, on the coarsest point sets): the H x H tiles of csrc/crf.hip's kernels no longer fit
     LDS, so the graph work -- similarity soft-max, neighbour aggregation, the reverse-CSR scatters and the soft-max
-    backward -- runs on the one-point-per-wavefront kernels (crfconv_wide_*), and the genuinely dense [m, H] x [H, H]
+    backward -- runs on the one-point-per-wavefront kernels (crfconv_wide_*, csrc/crf_wide.hip), and the genuinely dense [m, H] x [H, H]
     products of each step run on this library's tiled MFMA product (csrc/gemm.hip) and row-reduction kernel (dP, dQ).  Same
     recurrence and gradients as _MeanField."""
 

@@ -220,7 +220,7 @@ int crfconv_meanfield_bwd_scatter(const float* gm, const float* s, const int32_t
  * word that is ZERO on entry (left zero).  Otherwise mts [T, m, H] and sumG [m, H] are written -- and Gs[0] = G_T = gout,
  * so that Gs is the whole stacked [T, m, H] operand -- and the caller finishes dP = sum_i mts[i]^T Gs[i], dQ = z^T sumG
  * (crfconv_linear_wgrad); dP, dQ, ticket may be NULL.  ws: crfconv_meanfield_backward_workspace(m, H, K) bytes, 16-byte
- * aligned.  m H 4 < 2^31. */
+ * aligned (the query returns 0 for an H outside {4, 8, 16, 32, 64}).  m H 4 < 2^31. */
 int crfconv_meanfield_backward_supported(int H, int K, int k0);
 int crfconv_meanfield_backward_param_grads_inside(int H);
 size_t crfconv_meanfield_backward_workspace(int64_t m, int H, int K);

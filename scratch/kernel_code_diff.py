@@ -1,4 +1,4 @@
-"""Per-kernel comparison of the gfx950 device code of two trees (no GPU needed); profiles/r14_pointconv_split.md quotes it.
+"""Per-kernel comparison of the gfx950 device code of two trees (no GPU needed); profiles/r14_pointconv_split.md and r16_crf_split.md quote it.
 
     python scratch/kernel_code_diff.py --left A.hip [B.hip ...] --right C.hip [D.hip ...]
     python scratch/kernel_code_diff.py --left OLD/csrc/build --right crfconv_amd/csrc/build

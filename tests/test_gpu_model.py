@@ -180,6 +180,50 @@ def test_meanfield_vs_oracle(H, K, steps, B):
     assert_close(zero(cd.grad, cd), zero(cr.grad, cr), GRAD_TOL, 'dc')
 
 
+@pytest.mark.parametrize('table', ['K9_k0_1', 'K16_k0_0', 'ragged'])
+@pytest.mark.parametrize('H', [4, 8, 16, 32, 64])
+def test_meanfield_generic_path_every_width(H, table):
+    """The generic per-step path at every compiled width: sim_kernel / step_kernel forward, then bwd_edge / bwd_scatter per step and
+    similarity_bwd / similarity_bwd_scatter (csrc/crf.hip, csrc/crf_step_bwd.hip), on tables for which
+    crfconv_meanfield_backward_supported is 0 -- dense K = 9 with the self column skipped, dense K = 16 with EVERY column a neighbour
+    (k0 = 0: the shape the fast row forms would take with k0 = 1), and a padded variable-degree table (entries < 0; degrees 0..12, isolated
+    nodes, one self loop).  301 points per cloud: the last wavefront and the last workgroup are partly filled at every H.  Forward and
+    every gradient against the float32 oracles."""
+    from crfconv_amd import _lib, ops
+    from crfconv_amd.graph import NeighborTable, table_from_edges
+    B, N, steps = 2, 301, 2
+    c = (np.eye(H) + 0.1 * S.uniform(H, 'c', (H, H))).astype(np.float32)
+    if table == 'ragged':
+        shape, k0 = (N, H), 0
+        pairs = np.unique(np.stack([S.integers(H, 'tg', (2400,), 0, N - 20), S.integers(H, 'sr', (2400,), 0, N)], 1), axis=0)
+        pairs = pairs[pairs[:, 0] != pairs[:, 1]]
+        rank = np.arange(len(pairs)) - np.searchsorted(pairs[:, 0], pairs[:, 0])      # position of an edge among its target's (sorted)
+        pairs = np.concatenate([pairs[rank < 11], [[7, 7]]])                           # degrees 0..11, + one self loop: 0..12
+        tgt, src = (torch.from_numpy(pairs[:, i].astype(np.int64)) for i in (0, 1))
+        deg = np.bincount(pairs[:, 0], minlength=N)
+        assert deg.min() == 0 and deg.max() <= 12 and (deg[N - 20:] == 0).all()
+        tab = table_from_edges(tgt.to(DEV), src.to(DEV), N, N)
+        oracle = lambda zr, yr, cr: O.sparse_crf_meanfield(zr, yr, tgt, src, cr, steps)
+    else:
+        K, k0 = (9, 1) if table == 'K9_k0_1' else (16, 0)
+        shape = (B, N, H)
+        _, nbr = knn_tables(B, N, K, 60 + H)
+        tab = NeighborTable(t(nbr), N)
+        oracle = lambda zr, yr, cr: O.crf_meanfield(zr, yr, torch.from_numpy(nbr)[:, :, k0:], cr, steps)   # k0 = 0: all columns
+    assert _lib.load().crfconv_meanfield_backward_supported(H, tab.K, k0) == 0
+    z, y, g = (S.uniform(H, n, shape) for n in 'zyg')
+    zr, yr, cr = (torch.from_numpy(a).requires_grad_(True) for a in (z, y, c))
+    ref = oracle(zr, yr, cr)
+    (ref * torch.from_numpy(g)).sum().backward()
+    zd, yd, cd = (t(a).requires_grad_(True) for a in (z, y, c))
+    out = ops.crf_meanfield(zd.reshape(-1, H), yd.reshape(-1, H), cd, tab, steps, k0=k0)
+    (out.reshape(shape) * t(g)).sum().backward()
+    assert_close(out.reshape(shape), ref, OUT_TOL, 'x_T')
+    assert_close(zd.grad, zr.grad, GRAD_TOL, 'dz')
+    assert_close(yd.grad, yr.grad, GRAD_TOL, 'dy')
+    assert_close(cd.grad, cr.grad, GRAD_TOL, 'dc')
+
+
 @pytest.mark.parametrize('H,K,steps', [(8, 16, 3), (16, 16, 3), (32, 16, 2), (64, 16, 2), (8, 32, 2), (8, 16, 1)])
 def test_meanfield_backward_hub_rows_and_rows_without_in_edges(H, K, steps):
     """Reverse walks over very uneven in-degrees: three columns of every row point at rows 5, 6 and N - 1 of its cloud (in-degrees of

@@ -33,6 +33,26 @@ def test_library_exports_every_declared_symbol():
     assert rc == -1
 
 
+def test_meanfield_width_list_has_no_default_case():
+    """One list of hidden widths behind the mean-field entries (csrc/crf_common.hpp CRF_WIDTHS): a width outside it is refused or
+    answered with 0, never treated as 64."""
+    from crfconv_amd import _lib
+    lib = _lib.load()
+    for H in (4, 8, 16, 32, 64):
+        assert lib.crfconv_meanfield_backward_supported(H, 16, 1) == 1 and lib.crfconv_meanfield_backward_supported(H, 32, 1) == 1
+        assert lib.crfconv_meanfield_backward_supported(H, 16, 0) == 0 and lib.crfconv_meanfield_backward_supported(H, 9, 1) == 0
+        assert lib.crfconv_meanfield_backward_workspace(1000, H, 16) > 0
+    for H in (0, 7, 12, 65, 128):
+        assert lib.crfconv_meanfield_backward_supported(H, 16, 1) == 0
+        assert lib.crfconv_meanfield_backward_workspace(1000, H, 16) == 0
+        assert lib.crfconv_meanfield_step(None, None, None, None, 16, 1, 10, H, None, None, None, None) == -3
+        assert lib.crfconv_meanfield_bwd_edge(None, None, None, None, 16, 1, 10, H, None, None, None, None, 0, None) == -3
+        assert lib.crfconv_similarity_bwd(None, None, None, None, 16, 1, 10, H, None, None, None) == -3
+        assert (b'H=%d' % H) in lib.crfconv_last_error()
+    assert lib.crfconv_wide_similarity(None, None, 16, 0, 10, 64, None, None) == -3
+    assert lib.crfconv_wide_similarity(None, None, 16, 0, 10, 128, None, None) == -1      # a wide width: on to the null-pointer check
+
+
 def test_state_dict_layout_matches_reference(golden):
     from crfconv_amd import models
     g = golden('g5_pointconvbig.npz')
