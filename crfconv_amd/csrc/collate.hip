@@ -6,6 +6,8 @@
 //                            the s smallest keys are selected by a radix select and a block-wide scan writes their indices
 //                            in ascending order.  One workgroup per level, all levels in one launch.  The DRAWS differ from
 //                            torch.randperm's (any uniform subset is the reference's semantics); reproducible from the seed.
+//   crfconv_fps              the other way to pick a level's sub-cloud: farthest point sampling, one workgroup per cloud.
+//   crfconv_morton_codes     30-bit Z-order codes of every cloud's points, two launches.
 //   crfconv_argsort_codes    stable argsort of the 30-bit Morton codes per cloud (torch.argsort(stable=True) needs a private
 //                            segment: not replayable from a captured graph on ROCm 7.2): bucket by the top 16 bits
 //                            (histogram -> exclusive scan -> fill), then every element ranks itself inside its bucket by
@@ -139,6 +141,60 @@ __global__ __launch_bounds__(SUB_NT) void random_subsets_kernel(const SubsetJobs
     else random_subset_level<false>(n, s, jobs.out[level], jobs.rank[level], seed, ctr, level, s_hist, s_sel, s_cnt);
 }
 
+// ------------------------------------------------------------------ farthest point sampling
+// torch_cluster.fps as used by the reference's sparse graph builder (models/point_conv.py:381).  Inherently
+// sequential in the number of samples; one 1024-thread workgroup per cloud keeps the running min-distance
+// array in global memory (L2-resident) and does min-update + argmax (ties -> lower index) per iteration.
+__global__ __launch_bounds__(1024) void fps_kernel(const float* __restrict__ pos, const int64_t* __restrict__ seg_start,
+                                                   const int64_t* __restrict__ seg_count,
+                                                   const int64_t* __restrict__ out_start,
+                                                   const int64_t* __restrict__ n_sample,
+                                                   const int64_t* __restrict__ first, float* __restrict__ dist,
+                                                   int64_t* __restrict__ out) {
+    const int c = blockIdx.x;
+    const int64_t s0 = seg_start[c], n = seg_count[c], m = n_sample[c];
+    const float* p = pos + 3 * s0;
+    float* d = dist + s0;
+    int64_t* o = out + out_start[c];
+    __shared__ float sval[16];
+    __shared__ int sidx[16];
+    __shared__ int scur;
+    for (int64_t i = threadIdx.x; i < n; i += 1024) d[i] = 3.4e38f;
+    if (threadIdx.x == 0) scur = (int)first[c];
+    __syncthreads();
+    for (int64_t t = 0; t < m; ++t) {
+        const int cur = scur;
+        if (threadIdx.x == 0) o[t] = s0 + cur;
+        const float cx = p[3 * cur], cy = p[3 * cur + 1], cz = p[3 * cur + 2];
+        float best = -1.f;
+        int bi = 0x7fffffff;
+        for (int64_t i = threadIdx.x; i < n; i += 1024) {
+            const float dx = p[3 * i] - cx, dy = p[3 * i + 1] - cy, dz = p[3 * i + 2] - cz;
+            const float dd = fminf(d[i], dx * dx + dy * dy + dz * dz);
+            d[i] = dd;
+            if (dd > best) { best = dd; bi = (int)i; }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const float ov = __shfl_xor(best, off, WAVE);
+            const int oi = __shfl_xor(bi, off, WAVE);
+            if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+        }
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        __syncthreads();                                   // scur consumed by everyone
+        if (lane == 0) { sval[wave] = best; sidx[wave] = bi; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            float bv = sval[0];
+            int bj = sidx[0];
+            for (int w = 1; w < 16; ++w)
+                if (sval[w] > bv || (sval[w] == bv && sidx[w] < bj)) { bv = sval[w]; bj = sidx[w]; }
+            scur = bj;
+        }
+        __syncthreads();
+    }
+}
+
 // ------------------------------------------------------------------ up-index from the fine level's own neighbour table
 // up_idx[b][i] = the subset member nearest to point i (datasets/semantic3d_dataset.py:524: knn_batch(sub_pos, pos, 1), the order
 // (distance, subset position) of utils/nearest_neighbors).  The level's K-nearest table (distance order, the point itself first) already
@@ -245,6 +301,72 @@ __global__ __launch_bounds__(256) void upindex_scan_kernel(const float* __restri
         const int done = atomicAdd(state + 1, 1);
         if (done + 1 == (int)gridDim.x) { state[0] = 0; state[1] = 0; }
     }
+}
+
+// ------------------------------------------------------------------ Morton (Z-order) codes of a batch of clouds
+// code = 30 bits, ten per axis, of q = clamp((p - lo) / ext * 1023, 0, 1023) with lo = the cloud's per-axis minimum and ext =
+// its largest extent (>= 1e-20): what data.morton_order computed with ~45 framework launches (min / max reductions, the bit
+// spreading one elementwise op at a time), in two.  Every float operation is rounded on its own, as the framework's were.
+__global__ __launch_bounds__(1024) void morton_bbox_kernel(const float* __restrict__ pts, int64_t npts, float* __restrict__ box) {
+    const float* p = pts + (int64_t)blockIdx.x * npts * 3;
+    float mn[3] = {3.4e38f, 3.4e38f, 3.4e38f}, mx[3] = {-3.4e38f, -3.4e38f, -3.4e38f};
+    for (int64_t i = threadIdx.x; i < npts; i += 1024) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float v = p[3 * i + a];
+            mn[a] = fminf(mn[a], v);
+            mx[a] = fmaxf(mx[a], v);
+        }
+    }
+    __shared__ float smn[16][3], smx[16][3];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        float lo = mn[a], hi = mx[a];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            lo = fminf(lo, __shfl_xor(lo, o, WAVE));
+            hi = fmaxf(hi, __shfl_xor(hi, o, WAVE));
+        }
+        if (lane == 0) { smn[wave][a] = lo; smx[wave][a] = hi; }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float ext = 0.f;
+        for (int a = 0; a < 3; ++a) {
+            float lo = smn[0][a], hi = smx[0][a];
+            for (int w = 1; w < 16; ++w) { lo = fminf(lo, smn[w][a]); hi = fmaxf(hi, smx[w][a]); }
+            box[4 * blockIdx.x + a] = lo;
+            ext = fmaxf(ext, sub_rn(hi, lo));
+        }
+        box[4 * blockIdx.x + 3] = fmaxf(ext, 1e-20f);
+    }
+}
+
+__device__ __forceinline__ long long morton_spread3(long long v) {
+    v &= 0x3FF;
+    v = (v | (v << 16)) & 0x030000FF;
+    v = (v | (v << 8)) & 0x0300F00F;
+    v = (v | (v << 4)) & 0x030C30C3;
+    v = (v | (v << 2)) & 0x09249249;
+    return v;
+}
+
+__global__ __launch_bounds__(256) void morton_code_kernel(const float* __restrict__ pts, int64_t npts,
+                                                          const float* __restrict__ box, long long* __restrict__ code) {
+    const int b = blockIdx.y;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= npts) return;
+    const float* p = pts + ((int64_t)b * npts + i) * 3;
+    const float ext = box[4 * b + 3];
+    long long q[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        float t = mul_rn(sub_rn(p[a], box[4 * b + a]) / ext, 1023.0f);
+        t = fminf(fmaxf(t, 0.f), 1023.f);
+        q[a] = (long long)t;                               // truncation, as Tensor.to(int64)
+    }
+    code[(int64_t)b * npts + i] = morton_spread3(q[0]) | (morton_spread3(q[1]) << 1) | (morton_spread3(q[2]) << 2);
 }
 
 // ------------------------------------------------------------------ stable argsort of 30-bit codes, per cloud
@@ -396,6 +518,29 @@ extern "C" int crfconv_random_subsets(const int* n, const int* s, int64_t* const
     }
     hipLaunchKernelGGL(random_subsets_kernel, dim3((unsigned)nlevels), dim3(SUB_NT), 0, as_stream(stream), jobs,
                        (unsigned long long)seed, reinterpret_cast<const long long*>(counter));
+    CRF_LAUNCH_CHECK();
+    return CRF_OK;
+}
+
+extern "C" int crfconv_fps(const float* pos, int n_clouds, const int64_t* seg_start, const int64_t* seg_count,
+                           const int64_t* out_start, const int64_t* n_sample, const int64_t* first, float* dist_ws,
+                           int64_t* out, crf_stream_t stream) {
+    CRF_REQUIRE(pos && seg_start && seg_count && out_start && n_sample && first && dist_ws && out, CRF_ERR_ARG, "null pointer");
+    CRF_REQUIRE(n_clouds >= 1 && n_clouds <= 65535, CRF_ERR_ARG, "n_clouds=%d out of range", n_clouds);
+    hipLaunchKernelGGL(crf::fps_kernel, dim3(n_clouds), dim3(1024), 0, crf::as_stream(stream), pos, seg_start, seg_count,
+                       out_start, n_sample, first, dist_ws, out);
+    CRF_LAUNCH_CHECK();
+    return CRF_OK;
+}
+
+extern "C" int crfconv_morton_codes(const float* pts, int64_t B, int64_t npts, float* box_ws, int64_t* codes,
+                                    crf_stream_t stream) {
+    CRF_REQUIRE(pts && box_ws && codes, CRF_ERR_ARG, "null pointer");
+    CRF_REQUIRE(B > 0 && npts > 0 && B < 65536, CRF_ERR_ARG, "bad shape B=%lld npts=%lld", (long long)B, (long long)npts);
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(morton_bbox_kernel, dim3((unsigned)B), dim3(1024), 0, st, pts, npts, box_ws);
+    hipLaunchKernelGGL(morton_code_kernel, dim3((unsigned)cdiv(npts, 256), (unsigned)B), dim3(256), 0, st, pts, npts, box_ws,
+                       reinterpret_cast<long long*>(codes));
     CRF_LAUNCH_CHECK();
     return CRF_OK;
 }

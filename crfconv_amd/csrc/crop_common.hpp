@@ -1,6 +1,6 @@
-// What the crop paths share -- the single-crop entry with its full sort (evaluate.hip) and the batch forms with their select
-// (sampler.hip): every piece of arithmetic the bit-for-bit guarantees rest on (batch = loop of single crops = the reference's fixtures)
-// is written here once.  Workgroups of CROP_NT = 256 threads throughout.
+// What the crop paths of sampler.hip share -- the single-crop entry with its full sort and the batch forms with their select: every
+// piece of arithmetic the bit-for-bit guarantees rest on (batch = loop of single crops = the reference's fixtures) is written here
+// once.  Workgroups of CROP_NT = 256 threads throughout.
 #pragma once
 #include "common.hpp"
 

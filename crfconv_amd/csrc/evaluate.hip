@@ -1,14 +1,11 @@
-// The callers either side of the network, on the device so that a training / voting loop
+// What consumes the network's output, on the device so that a training / voting loop
 // never leaves it:
 //   * confusion matrix of utils/metrics.py:13-27 (runningScore._fast_hist / update), optionally with the arg-max of
 //     the logits fused in (trainval.py:108: y_pred.max(dim=1)[1]);
 //   * vote accumulator of trainval.py:170-190 (running mean of soft-max probabilities per cloud point) and the
-//     re-projection arg-max of trainval.py:198-203;
-//   * possibility sampler of datasets/semantic3d_dataset.py:423-460 (_get_random): seed = arg-min possibility,
-//     crop = the num_points nearest points of the (jittered) seed, possibility += (1 - d / d_max)^2 * weight.
+//     re-projection arg-max of trainval.py:198-203.
 // Integer / byte work and streaming reductions: HBM-bound, no LDS tiling beyond block-local histograms.
-#include "crop_common.hpp"
-#include "radix_sort.hpp"
+#include "common.hpp"
 
 namespace crf {
 
@@ -233,101 +230,6 @@ __global__ __launch_bounds__(EV_BLOCK) void vote_confusion_kernel(const float* _
     }
 }
 
-// ------------------------------------------------------------------------------------------ possibility sampler
-// arg-min with the first index on ties (np.argmin; crop_common.hpp), two passes: per-block candidates, then one block.
-__global__ __launch_bounds__(EV_BLOCK) void argmin_partial_kernel(const double* __restrict__ v, int64_t n,
-                                                                  double* __restrict__ pv, int64_t* __restrict__ pi) {
-    MinIdx m = min_none();
-    for (int64_t i = (int64_t)blockIdx.x * EV_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * EV_BLOCK)
-        m = min_first(m, MinIdx{v[i], i});
-    m = block_min_first(m);
-    if (threadIdx.x == 0) { pv[blockIdx.x] = m.v; pi[blockIdx.x] = m.i; }
-}
-
-__global__ __launch_bounds__(EV_BLOCK) void argmin_final_kernel(const double* __restrict__ pv,
-                                                                const int64_t* __restrict__ pi, int nblk,
-                                                                double* __restrict__ out_v, int64_t* __restrict__ out_i) {
-    MinIdx m = min_none();
-    for (int b = threadIdx.x; b < nblk; b += EV_BLOCK) m = min_first(m, MinIdx{pv[b], pi[b]});
-    m = block_min_first(m);
-    if (threadIdx.x == 0) { *out_v = m.v; *out_i = m.i; }
-}
-
-// pick point = float64(points[pick]) + noise (semantic3d_dataset.py:426-430)
-__global__ void pick_point_kernel(const float* __restrict__ points, const int64_t* __restrict__ pick,
-                                  const double* __restrict__ noise, double* __restrict__ center) {
-    if (threadIdx.x < 3) center[threadIdx.x] = (double)points[*pick * 3 + threadIdx.x] + (noise ? noise[threadIdx.x] : 0.0);
-}
-
-// The single-crop entry: the key of EVERY point for a full stable sort of the cloud -- the independent twin of sampler.hip's select --
-// then the distances, the update and the row write of crop_common.hpp in the Semantic3D form.
-__global__ __launch_bounds__(EV_BLOCK) void crop_keys_kernel(const float* __restrict__ points, int64_t n,
-                                                             const double* __restrict__ center,
-                                                             unsigned long long* __restrict__ keys,
-                                                             unsigned int* __restrict__ ids) {
-    const int64_t i = (int64_t)blockIdx.x * EV_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    keys[i] = crop_key(points, i, center[0], center[1], center[2]);
-    ids[i] = (unsigned int)i;
-}
-
-__global__ __launch_bounds__(EV_BLOCK) void crop_dist_kernel(const float* __restrict__ points,
-                                                             const unsigned int* __restrict__ sel, int64_t k,
-                                                             const double* __restrict__ center,
-                                                             float* __restrict__ dist, float* __restrict__ pmax) {
-    const int64_t t = (int64_t)blockIdx.x * EV_BLOCK + threadIdx.x;
-    float d = 0.f;
-    if (t < k) dist[t] = d = crop_row_dist<false>(points, sel[t], center);
-    block_max_to(d, pmax);
-}
-
-// possibility[q] += (1 - d / d_max)^2 * weight[label_to_idx(labels[q])]     (:449-450), and the crop's outputs
-__global__ __launch_bounds__(EV_BLOCK) void crop_update_kernel(const float* __restrict__ points,
-                                                               const unsigned int* __restrict__ sel,
-                                                               const int64_t* __restrict__ perm, int64_t k,
-                                                               const double* __restrict__ center,
-                                                               const float* __restrict__ dist,
-                                                               const float* __restrict__ pmax, int nblk,
-                                                               const double* __restrict__ point_weight,
-                                                               double* __restrict__ possibility,
-                                                               int64_t* __restrict__ out_idx,
-                                                               float* __restrict__ out_xyz) {
-    const int64_t t = (int64_t)blockIdx.x * EV_BLOCK + threadIdx.x;
-    if (t >= k) return;
-    const int64_t src = perm ? perm[t] : t;            // output row t shows selected element perm[t] (the shuffle)
-    const int64_t i = sel[src];
-    const float sq = crop_gain(dist[src], crop_dmax(pmax, nblk));
-    // the weights are float64 for train / val (class_weight array) and the python int 1 for test (float32 result)
-    possibility[i] += point_weight ? dmul_rn((double)sq, point_weight[i]) : (double)sq;      // rows of a crop are distinct points
-    crop_write_row<false>(points, nullptr, nullptr, i, center, t, out_xyz, nullptr, 0, nullptr, out_idx);
-}
-
-static_assert(EV_BLOCK == CROP_NT, "the crop helpers reduce over 256 threads");
-constexpr int ARGMIN_BLOCKS = 1024;
-
-struct CropWs {                   // workspace of the single-crop entry
-    unsigned long long *keys_in, *keys_out;
-    unsigned int *ids_in, *ids_out;
-    float *dist, *pmax;
-    double* center;
-    char* sort;
-    size_t bytes;
-};
-static CropWs crop_carve(void* workspace, int64_t n, int64_t k) {
-    Carve c(workspace);
-    CropWs w;
-    w.keys_in = c.take<unsigned long long>((size_t)n);
-    w.keys_out = c.take<unsigned long long>((size_t)n);
-    w.ids_in = c.take<unsigned int>((size_t)n);
-    w.ids_out = c.take<unsigned int>((size_t)n);
-    w.dist = c.take<float>((size_t)k);
-    w.pmax = c.take<float>((size_t)cdiv(k, EV_BLOCK));
-    w.center = c.take<double>(3);
-    w.sort = c.take<char>(rsort_workspace(n));      // this library's radix sort (radix_sort.hpp)
-    w.bytes = c.bytes();
-    return w;
-}
-
 }  // namespace crf
 
 using namespace crf;
@@ -492,59 +394,5 @@ extern "C" int crfconv_vote_confusion(const float* test_probs, int64_t n_cloud, 
         hipLaunchKernelGGL(vote_confusion_kernel<false>, dim3((unsigned)blocks), dim3(EV_BLOCK), 0, as_stream(stream), test_probs, n_cloud, C,
                            proj_idx, labels, n_rows, label_shift, h, bad_count);
     CRF_LAUNCH_CHECK();
-    return CRF_OK;
-}
-
-extern "C" size_t crfconv_argmin_workspace(void) { return ARGMIN_BLOCKS * (sizeof(double) + sizeof(int64_t)); }
-
-extern "C" int crfconv_argmin_f64(const double* values, int64_t n, double* out_value, int64_t* out_index,
-                                  void* workspace, size_t workspace_bytes, crf_stream_t stream) {
-    CRF_REQUIRE(values && out_value && out_index && workspace, CRF_ERR_ARG, "null pointer");
-    CRF_REQUIRE(n > 0, CRF_ERR_ARG, "empty array");
-    CRF_REQUIRE(workspace_bytes >= crfconv_argmin_workspace(), CRF_ERR_WORKSPACE, "argmin workspace too small");
-    double* pv = reinterpret_cast<double*>(workspace);
-    int64_t* pi = reinterpret_cast<int64_t*>(pv + ARGMIN_BLOCKS);
-    int64_t blocks = cdiv(n, EV_BLOCK);
-    if (blocks > ARGMIN_BLOCKS) blocks = ARGMIN_BLOCKS;
-    hipLaunchKernelGGL(argmin_partial_kernel, dim3((unsigned)blocks), dim3(EV_BLOCK), 0, as_stream(stream), values, n, pv, pi);
-    CRF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(argmin_final_kernel, dim3(1), dim3(EV_BLOCK), 0, as_stream(stream), pv, pi, (int)blocks, out_value,
-                       out_index);
-    CRF_LAUNCH_CHECK();
-    return CRF_OK;
-}
-
-extern "C" size_t crfconv_possibility_crop_workspace(int64_t n, int64_t k) {
-    if (n <= 0 || k <= 0) return 0;
-    return crop_carve(nullptr, n, k).bytes;
-}
-
-extern "C" int crfconv_possibility_crop(const float* points, int64_t n, int64_t k, const int64_t* pick_index,
-                                        const double* noise, const int64_t* perm, const double* point_weight,
-                                        double* possibility, int64_t* out_idx, float* out_xyz, double* out_center,
-                                        void* workspace, size_t workspace_bytes, crf_stream_t stream) {
-    CRF_REQUIRE(points && pick_index && possibility && out_idx && out_xyz && workspace, CRF_ERR_ARG, "null pointer");
-    CRF_REQUIRE(n > 0 && k > 0 && k <= n && n < ((int64_t)1 << 32), CRF_ERR_ARG, "n=%lld k=%lld invalid", (long long)n,
-                (long long)k);
-    const CropWs w = crop_carve(workspace, n, k);
-    CRF_REQUIRE(workspace_bytes >= w.bytes, CRF_ERR_WORKSPACE, "possibility_crop workspace %zu < %zu", workspace_bytes, w.bytes);
-    hipStream_t st = as_stream(stream);
-    const int nblk = (int)cdiv(k, EV_BLOCK);
-    hipLaunchKernelGGL(pick_point_kernel, dim3(1), dim3(64), 0, st, points, pick_index, noise, w.center);
-    CRF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(crop_keys_kernel, dim3((unsigned)cdiv(n, EV_BLOCK)), dim3(EV_BLOCK), 0, st, points, n, (const double*)w.center,
-                       w.keys_in, w.ids_in);
-    CRF_LAUNCH_CHECK();
-    // stable LSD radix sort over all eight digits of the float64 keys: equal distances keep ascending point order (the KD-tree's order
-    // on ties is unspecified)
-    const unsigned int* sel = rsort_pairs_u64(w.keys_in, w.ids_in, w.keys_out, w.ids_out, n, 0, 64, w.sort, st) ? w.ids_out : w.ids_in;
-    CRF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(crop_dist_kernel, dim3((unsigned)nblk), dim3(EV_BLOCK), 0, st, points, sel, k, (const double*)w.center, w.dist,
-                       w.pmax);
-    CRF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(crop_update_kernel, dim3((unsigned)nblk), dim3(EV_BLOCK), 0, st, points, sel, perm, k, (const double*)w.center,
-                       (const float*)w.dist, (const float*)w.pmax, nblk, point_weight, possibility, out_idx, out_xyz);
-    CRF_LAUNCH_CHECK();
-    if (out_center) CRF_HIP(hipMemcpyAsync(out_center, w.center, 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
     return CRF_OK;
 }

@@ -1,11 +1,15 @@
 // Exact batched kNN on gfx950 -- replaces the reference's nanoflann KD-tree extension
-// (utils/nearest_neighbors/knn_.cxx:22-135, knn_.h:2-19) with a uniform-grid search:
-//   1. per-cloud bounding box            (one block per cloud)
-//   2. cell id + histogram               (flat, int atomics)
-//   3. exclusive scan of cell counts     (scan.hpp: this library's own scratch-free scan)
-//   4. counting-sort scatter             (points packed as float4 {x, y, z, id})
-//   5. one thread per query: expanding Chebyshev rings of cells, register-resident top-K,
-//      stops when the K-th distance is strictly inside the searched cube.
+// (utils/nearest_neighbors/knn_.cxx:22-135, knn_.h:2-19) with three searches that rank the same keys (crfconv_knn_batch_dev says
+// which serves which (npts, K)):
+//   whole cloud   knn_brute_kernel: small clouds, no grid; sixteen lanes per query look at every point of the cloud.
+//   uniform grid, built by
+//     1. per-cloud bounding box            (one block per cloud)
+//     2. cell id + histogram               (flat, int atomics)
+//     3. exclusive scan of cell counts     (scan.hpp: this library's own scratch-free scan)
+//     4. counting-sort scatter             (points packed as float4 {x, y, z, id})
+//   and searched over expanding Chebyshev rings of cells until the K-th distance is strictly inside the searched cube, by
+//     5.  knn_query_kernel: one lane per query, register-resident top-K, or
+//     5b. knn_coop_kernel: sixteen lanes per query, the ring's row segments dealt over them, top-K in an LDS pool.
 // Result contract (bit-exact against the oracle / the reference on tie-free input):
 //   distance = fl(fl(fl(dx*dx) + fl(dy*dy)) + fl(dz*dz)) in float32, no FMA contraction
 //   (nanoflann.hpp:342-347); neighbours ascending by (distance, point id).
@@ -78,72 +82,6 @@ __global__ __launch_bounds__(1024) void bbox_kernel(const float* __restrict__ pt
         g.margin = 1e-5f * (amax + emax) + 1e-30f;
         info[blockIdx.x] = g;
     }
-}
-
-// ------------------------------------------------------------------ Morton (Z-order) codes of a batch of clouds
-// code = 30 bits, ten per axis, of q = clamp((p - lo) / ext * 1023, 0, 1023) with lo = the cloud's per-axis minimum and ext =
-// its largest extent (>= 1e-20): what data.morton_order computed with ~45 framework launches (min / max reductions, the bit
-// spreading one elementwise op at a time), in two.  Every float operation is rounded on its own, as the framework's were.
-__global__ __launch_bounds__(1024) void morton_bbox_kernel(const float* __restrict__ pts, int64_t npts, float* __restrict__ box) {
-    const float* p = pts + (int64_t)blockIdx.x * npts * 3;
-    float mn[3] = {3.4e38f, 3.4e38f, 3.4e38f}, mx[3] = {-3.4e38f, -3.4e38f, -3.4e38f};
-    for (int64_t i = threadIdx.x; i < npts; i += 1024) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float v = p[3 * i + a];
-            mn[a] = fminf(mn[a], v);
-            mx[a] = fmaxf(mx[a], v);
-        }
-    }
-    __shared__ float smn[16][3], smx[16][3];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        float lo = mn[a], hi = mx[a];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            lo = fminf(lo, __shfl_xor(lo, o, WAVE));
-            hi = fmaxf(hi, __shfl_xor(hi, o, WAVE));
-        }
-        if (lane == 0) { smn[wave][a] = lo; smx[wave][a] = hi; }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float ext = 0.f;
-        for (int a = 0; a < 3; ++a) {
-            float lo = smn[0][a], hi = smx[0][a];
-            for (int w = 1; w < 16; ++w) { lo = fminf(lo, smn[w][a]); hi = fmaxf(hi, smx[w][a]); }
-            box[4 * blockIdx.x + a] = lo;
-            ext = fmaxf(ext, sub_rn(hi, lo));
-        }
-        box[4 * blockIdx.x + 3] = fmaxf(ext, 1e-20f);
-    }
-}
-
-__device__ __forceinline__ long long morton_spread3(long long v) {
-    v &= 0x3FF;
-    v = (v | (v << 16)) & 0x030000FF;
-    v = (v | (v << 8)) & 0x0300F00F;
-    v = (v | (v << 4)) & 0x030C30C3;
-    v = (v | (v << 2)) & 0x09249249;
-    return v;
-}
-
-__global__ __launch_bounds__(256) void morton_code_kernel(const float* __restrict__ pts, int64_t npts,
-                                                          const float* __restrict__ box, long long* __restrict__ code) {
-    const int b = blockIdx.y;
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= npts) return;
-    const float* p = pts + ((int64_t)b * npts + i) * 3;
-    const float ext = box[4 * b + 3];
-    long long q[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        float t = mul_rn(sub_rn(p[a], box[4 * b + a]) / ext, 1023.0f);
-        t = fminf(fmaxf(t, 0.f), 1023.f);
-        q[a] = (long long)t;                               // truncation, as Tensor.to(int64)
-    }
-    code[(int64_t)b * npts + i] = morton_spread3(q[0]) | (morton_spread3(q[1]) << 1) | (morton_spread3(q[2]) << 2);
 }
 
 __device__ __forceinline__ int3 cell_of(const GridInfo& g, float x, float y, float z) {
@@ -225,6 +163,7 @@ struct TopK {
 };
 
 constexpr int QCAP = 8;     // accepted candidates a lane may hold before the wavefront inserts them
+constexpr Widths<1, 32, 64> KNN_QUERY_CAPS{};       // top-K capacities KM the one-lane search is compiled for (K <= KM)
 
 template <int KM>
 __global__ __launch_bounds__(QBLOCK) void knn_query_kernel(const float* __restrict__ queries, int64_t nq,
@@ -520,6 +459,7 @@ __global__ __launch_bounds__(CO_BLOCK) void knn_coop_kernel(const float* __restr
 // K rounds of group-wide minimum.  No grid construction (seven launches less per call), results identical: the K smallest
 // keys of a set do not depend on the order they are offered in.
 constexpr int BRUTE_MAX = 4096, BRUTE_LPQ = 16, BRUTE_BLOCK = 256, BRUTE_QPB = BRUTE_BLOCK / BRUTE_LPQ;
+constexpr Widths<1, 8, 16, 32> KNN_BRUTE_KS{};      // the K the whole-cloud search is compiled for (K == KM exactly)
 
 __device__ __forceinline__ unsigned long long group16_min(unsigned long long v) {
 #pragma unroll
@@ -662,18 +602,6 @@ static KnnLayout knn_layout(size_t B, size_t npts) {
 
 using namespace crf;
 
-extern "C" int crfconv_morton_codes(const float* pts, int64_t B, int64_t npts, float* box_ws, int64_t* codes,
-                                    crf_stream_t stream) {
-    CRF_REQUIRE(pts && box_ws && codes, CRF_ERR_ARG, "null pointer");
-    CRF_REQUIRE(B > 0 && npts > 0 && B < 65536, CRF_ERR_ARG, "bad shape B=%lld npts=%lld", (long long)B, (long long)npts);
-    hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(morton_bbox_kernel, dim3((unsigned)B), dim3(1024), 0, st, pts, npts, box_ws);
-    hipLaunchKernelGGL(morton_code_kernel, dim3((unsigned)cdiv(npts, 256), (unsigned)B), dim3(256), 0, st, pts, npts, box_ws,
-                       reinterpret_cast<long long*>(codes));
-    CRF_LAUNCH_CHECK();
-    return CRF_OK;
-}
-
 extern "C" size_t crfconv_knn_batch_dev_workspace(size_t batch_size, size_t npts, size_t nqueries, size_t K) {
     (void)nqueries; (void)K;
     if (batch_size == 0 || npts == 0) return 0;
@@ -692,18 +620,20 @@ extern "C" int crfconv_knn_batch_dev(const float* pts, size_t batch_size, size_t
     const KnnLayout L = knn_layout(batch_size, npts);
     CRF_REQUIRE(workspace_bytes >= L.total, CRF_ERR_WORKSPACE, "knn workspace %zu < %zu", workspace_bytes, L.total);
     hipStream_t st = as_stream(stream);
-    if (npts <= (size_t)BRUTE_MAX && (K == 1 || K == 8 || K == 16 || K == 32)) {
+    // Which search serves which (npts, K):
+    //   npts <= BRUTE_MAX and K in KNN_BRUTE_KS   the whole-cloud search, no grid;
+    //   otherwise the grid, searched by           1 < K <= 16: sixteen lanes per query;
+    //                                             K == 1, K > 16: one lane per query, capacity 1, 32 or 64.
+    if (npts <= (size_t)BRUTE_MAX) {
         const dim3 bgrid((unsigned)cdiv((int64_t)nqueries, BRUTE_QPB), (unsigned)batch_size);
-#define KNN_BRUTE(KM)                                                                                       \
-    hipLaunchKernelGGL(knn_brute_kernel<KM>, bgrid, dim3(BRUTE_BLOCK), 0, st, pts, (int64_t)npts, queries, \
-                       (int64_t)nqueries, out_i64, out_i32)
-        if (K == 1) KNN_BRUTE(1);
-        else if (K == 8) KNN_BRUTE(8);
-        else if (K == 16) KNN_BRUTE(16);
-        else KNN_BRUTE(32);
-#undef KNN_BRUTE
-        CRF_LAUNCH_CHECK();
-        return CRF_OK;
+        const bool whole = dispatch_width(KNN_BRUTE_KS, (int)K, [&](auto KM) {
+            hipLaunchKernelGGL(knn_brute_kernel<decltype(KM)::value>, bgrid, dim3(BRUTE_BLOCK), 0, st, pts, (int64_t)npts, queries,
+                               (int64_t)nqueries, out_i64, out_i32);
+        });
+        if (whole) {
+            CRF_LAUNCH_CHECK();
+            return CRF_OK;
+        }
     }
     char* ws = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
     GridInfo* info = reinterpret_cast<GridInfo*>(ws + L.off_info);
@@ -734,10 +664,6 @@ extern "C" int crfconv_knn_batch_dev(const float* pts, size_t batch_size, size_t
     hipLaunchKernelGGL(cell_scatter_kernel, pgrid, dim3(256), 0, st, pts, (int64_t)npts, L.ncell_alloc, cell_id,
                        starts, fill, sorted);
     CRF_LAUNCH_CHECK();
-    const dim3 qgrid((unsigned)cdiv((int64_t)nqueries, QBLOCK), (unsigned)batch_size);
-#define KNN_LAUNCH(KM)                                                                                     \
-    hipLaunchKernelGGL(knn_query_kernel<KM>, qgrid, dim3(QBLOCK), 0, st, queries, (int64_t)nqueries,       \
-                       (int64_t)npts, (int)K, info, L.ncell_alloc, starts, sorted, out_i64, out_i32)
     if (K > 1 && K <= 16) {
         const dim3 cgrid((unsigned)cdiv((int64_t)nqueries, CO_QPB), (unsigned)batch_size);
         hipLaunchKernelGGL(knn_coop_kernel<16>, cgrid, dim3(CO_BLOCK), 0, st, queries, (int64_t)nqueries, (int)K, info,
@@ -745,12 +671,11 @@ extern "C" int crfconv_knn_batch_dev(const float* pts, size_t batch_size, size_t
         CRF_LAUNCH_CHECK();
         return CRF_OK;
     }
-    if (K == 1) KNN_LAUNCH(1);
-    else if (K <= 8) KNN_LAUNCH(8);
-    else if (K <= 16) KNN_LAUNCH(16);
-    else if (K <= 32) KNN_LAUNCH(32);
-    else KNN_LAUNCH(64);
-#undef KNN_LAUNCH
+    const dim3 qgrid((unsigned)cdiv((int64_t)nqueries, QBLOCK), (unsigned)batch_size);
+    dispatch_width(KNN_QUERY_CAPS, K == 1 ? 1 : K <= 32 ? 32 : 64, [&](auto KM) {
+        hipLaunchKernelGGL(knn_query_kernel<decltype(KM)::value>, qgrid, dim3(QBLOCK), 0, st, queries, (int64_t)nqueries,
+                           (int64_t)npts, (int)K, info, L.ncell_alloc, starts, sorted, out_i64, out_i32);
+    });
     CRF_LAUNCH_CHECK();
     return CRF_OK;
 }
@@ -802,71 +727,4 @@ extern "C" int crfconv_knn_batch(const float* batch_data, size_t batch_size, siz
 extern "C" int crfconv_knn_batch_omp(const float* batch_data, size_t batch_size, size_t npts, size_t dim,
                                      const float* queries, size_t nqueries, size_t K, long* batch_indices) {
     return knn_host(batch_data, batch_size, npts, dim, queries, nqueries, K, batch_indices);
-}
-
-// ------------------------------------------------------------------ farthest point sampling
-// torch_cluster.fps as used by the reference's sparse graph builder (models/point_conv.py:381).  Inherently
-// sequential in the number of samples; one 1024-thread workgroup per cloud keeps the running min-distance
-// array in global memory (L2-resident) and does min-update + argmax (ties -> lower index) per iteration.
-namespace crf {
-__global__ __launch_bounds__(1024) void fps_kernel(const float* __restrict__ pos, const int64_t* __restrict__ seg_start,
-                                                   const int64_t* __restrict__ seg_count,
-                                                   const int64_t* __restrict__ out_start,
-                                                   const int64_t* __restrict__ n_sample,
-                                                   const int64_t* __restrict__ first, float* __restrict__ dist,
-                                                   int64_t* __restrict__ out) {
-    const int c = blockIdx.x;
-    const int64_t s0 = seg_start[c], n = seg_count[c], m = n_sample[c];
-    const float* p = pos + 3 * s0;
-    float* d = dist + s0;
-    int64_t* o = out + out_start[c];
-    __shared__ float sval[16];
-    __shared__ int sidx[16];
-    __shared__ int scur;
-    for (int64_t i = threadIdx.x; i < n; i += 1024) d[i] = 3.4e38f;
-    if (threadIdx.x == 0) scur = (int)first[c];
-    __syncthreads();
-    for (int64_t t = 0; t < m; ++t) {
-        const int cur = scur;
-        if (threadIdx.x == 0) o[t] = s0 + cur;
-        const float cx = p[3 * cur], cy = p[3 * cur + 1], cz = p[3 * cur + 2];
-        float best = -1.f;
-        int bi = 0x7fffffff;
-        for (int64_t i = threadIdx.x; i < n; i += 1024) {
-            const float dx = p[3 * i] - cx, dy = p[3 * i + 1] - cy, dz = p[3 * i + 2] - cz;
-            const float dd = fminf(d[i], dx * dx + dy * dy + dz * dz);
-            d[i] = dd;
-            if (dd > best) { best = dd; bi = (int)i; }
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const float ov = __shfl_xor(best, off, WAVE);
-            const int oi = __shfl_xor(bi, off, WAVE);
-            if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-        }
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        __syncthreads();                                   // scur consumed by everyone
-        if (lane == 0) { sval[wave] = best; sidx[wave] = bi; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            float bv = sval[0];
-            int bj = sidx[0];
-            for (int w = 1; w < 16; ++w)
-                if (sval[w] > bv || (sval[w] == bv && sidx[w] < bj)) { bv = sval[w]; bj = sidx[w]; }
-            scur = bj;
-        }
-        __syncthreads();
-    }
-}
-}  // namespace crf
-
-extern "C" int crfconv_fps(const float* pos, int n_clouds, const int64_t* seg_start, const int64_t* seg_count,
-                           const int64_t* out_start, const int64_t* n_sample, const int64_t* first, float* dist_ws,
-                           int64_t* out, crf_stream_t stream) {
-    CRF_REQUIRE(pos && seg_start && seg_count && out_start && n_sample && first && dist_ws && out, CRF_ERR_ARG, "null pointer");
-    CRF_REQUIRE(n_clouds >= 1 && n_clouds <= 65535, CRF_ERR_ARG, "n_clouds=%d out of range", n_clouds);
-    hipLaunchKernelGGL(crf::fps_kernel, dim3(n_clouds), dim3(1024), 0, crf::as_stream(stream), pos, seg_start, seg_count,
-                       out_start, n_sample, first, dist_ws, out);
-    CRF_LAUNCH_CHECK();
-    return CRF_OK;
 }

@@ -1,6 +1,6 @@
 // Device-wide STABLE radix sort of (uint64 key, uint32 value) pairs -- this library's own, for the two places that sorted
 // through rocPRIM until round 3: the voxel-key sort of the grid subsampling (grid_subsample.hip, utils/cpp_wrappers:
-// grid_subsampling.cpp:53-56 keys) and the distance sort of the possibility crop (evaluate.hip,
+// grid_subsampling.cpp:53-56 keys) and the distance sort of the possibility crop (sampler.hip,
 // datasets/semantic3d_dataset.py:433 KDTree.query order).  No scratch (private-segment) memory, so -- unlike rocPRIM's
 // onesweep kernel on ROCm 7.2 -- its launches can sit in a captured hipGraph.
 //

@@ -1,10 +1,15 @@
-// B possibility crops per call, decided and written on the device (datasets/semantic3d_dataset.py:423-460, `_get_random`, as B
-// consecutive __getitem__ calls; crfconv_amd.sampling.PossibilitySampler.get_batch).  No host read anywhere, no scratch memory:
-// the whole call can sit in a captured hipGraph (data.CollateGraph(sampler=)).  Bit for bit what B calls of
-// crfconv_possibility_crop (evaluate.hip) give for the same jitter and shuffle, without sorting the cloud.  The key, the distances,
-// the gain, the row write and the arg-min are those of crop_common.hpp, which that entry uses too.
+// The possibility sampler of datasets/semantic3d_dataset.py:423-460 (`_get_random`): seed = arg-min possibility, crop = the
+// num_points nearest points of the (jittered) seed, possibility += (1 - d / d_max)^2 * weight.  Three forms, one arithmetic
+// (crop_common.hpp: the key, the distances, the gain, the row write, the arg-min):
+//   single cloud   crfconv_argmin_f64 + crfconv_possibility_crop: the caller picks the seed, the entry sorts the keys of EVERY point
+//                  (a full stable radix sort) and takes the first k.  The independent twin the batch forms are tested against.
+//   batch          crfconv_possibility_crop_batch: B crops per call, decided and written on the device (B consecutive __getitem__
+//                  calls; crfconv_amd.sampling.PossibilitySampler.get_batch).  No host read anywhere, no scratch memory: the whole
+//                  call can sit in a captured hipGraph (data.CollateGraph(sampler=)).  Bit for bit what B calls of the single form
+//                  give for the same jitter and shuffle, without sorting the cloud.
+//   S3DIS batch    crfconv_possibility_crop_batch_s3dis: the same for rooms that may be smaller than a crop (below).
 //
-//   ONE sequence per crop b for both forms (sb_run), in stream order (crop b + 1 sees the possibilities crop b left):
+//   ONE sequence per crop b for both batch forms (sb_run), in stream order (crop b + 1 sees the possibilities crop b left):
 //     sb_choose_kernel   1 workgroup: cloud = arg-min of the per-cloud minima (first index on ties), seed point = that cloud's
 //                        arg-min, jitter (Box-Muller in float64 on 53-bit uniforms of smp_hash, or noise_in), centre; clears the
 //                        select's histograms.  The cloud is read through a DEVICE table of descriptors (crf_cloud_desc), the grids
@@ -20,7 +25,7 @@
 //     sb_scatter_kernel  ORDER-PRESERVING compaction (ballot ranks inside a wavefront, tile bases summed from the counts): keys
 //                        below the k-th in point order into [0, L), then the first k - L points with the k-th key in point order.
 //     rsort_pairs_u64    the library's stable radix sort over those k pairs only: (key, point id) order, i.e. what the full stable
-//                        sort of evaluate.hip yields; ties at the ball's boundary go to the lower point id.
+//                        sort of the single form yields; ties at the ball's boundary go to the lower point id.
 //     (S3DIS form only)  the padding of a short crop, see below: sb_perm_compact_kernel, sb_choice_keys_kernel + its sort,
 //                        sb_choice_final_kernel -- each enqueued only when the table or the caller's outputs can need it.
 //     sb_dist_kernel / sb_update_kernel   float32 distances, d_max, possibility += (1 - d / d_max)^2 weight, and row b of the batch:
@@ -45,7 +50,7 @@
 namespace crf {
 
 constexpr int SB_NT = CROP_NT, SB_IPT = 16, SB_TILE = SB_NT * SB_IPT;  // threads per workgroup; points per thread / per tile
-constexpr int SB_ARGMIN_BLOCKS = 1024;
+constexpr int SB_ARGMIN_BLOCKS = 1024;                                // workgroups of an arg-min's first pass, every form
 constexpr unsigned long long SMP_DOMAIN = 0x8CB92BA72F3D8DD7ull;       // separates these draws from the subsets' / dropout's / augmentation's
 constexpr int SMP_PERM_SLOT = 8;                                       // slots 0 .. 5: the jitter's uniforms; 8 + t: shuffle key of row t
 
@@ -429,6 +434,99 @@ __global__ __launch_bounds__(SB_NT) void sb_choice_final_kernel(const SbCrop* __
     if (choice_out != nullptr) choice_out[t] = v;
 }
 
+// ------------------------------------------------------------------------------------------ the single-cloud form
+// arg-min with the first index on ties (np.argmin; crop_common.hpp), two passes: per-block candidates, then one block.
+__global__ __launch_bounds__(SB_NT) void argmin_partial_kernel(const double* __restrict__ v, int64_t n,
+                                                               double* __restrict__ pv, int64_t* __restrict__ pi) {
+    MinIdx m = min_none();
+    for (int64_t i = (int64_t)blockIdx.x * SB_NT + threadIdx.x; i < n; i += (int64_t)gridDim.x * SB_NT)
+        m = min_first(m, MinIdx{v[i], i});
+    m = block_min_first(m);
+    if (threadIdx.x == 0) { pv[blockIdx.x] = m.v; pi[blockIdx.x] = m.i; }
+}
+
+__global__ __launch_bounds__(SB_NT) void argmin_final_kernel(const double* __restrict__ pv,
+                                                             const int64_t* __restrict__ pi, int nblk,
+                                                             double* __restrict__ out_v, int64_t* __restrict__ out_i) {
+    MinIdx m = min_none();
+    for (int b = threadIdx.x; b < nblk; b += SB_NT) m = min_first(m, MinIdx{pv[b], pi[b]});
+    m = block_min_first(m);
+    if (threadIdx.x == 0) { *out_v = m.v; *out_i = m.i; }
+}
+
+// pick point = float64(points[pick]) + noise (semantic3d_dataset.py:426-430)
+__global__ void pick_point_kernel(const float* __restrict__ points, const int64_t* __restrict__ pick,
+                                  const double* __restrict__ noise, double* __restrict__ center) {
+    if (threadIdx.x < 3) center[threadIdx.x] = (double)points[*pick * 3 + threadIdx.x] + (noise ? noise[threadIdx.x] : 0.0);
+}
+
+// The key of EVERY point for a full stable sort of the cloud -- the independent twin of the batch forms' select -- then the
+// distances, the update and the row write of crop_common.hpp in the Semantic3D form.
+__global__ __launch_bounds__(SB_NT) void crop_keys_kernel(const float* __restrict__ points, int64_t n,
+                                                          const double* __restrict__ center,
+                                                          unsigned long long* __restrict__ keys,
+                                                          unsigned int* __restrict__ ids) {
+    const int64_t i = (int64_t)blockIdx.x * SB_NT + threadIdx.x;
+    if (i >= n) return;
+    keys[i] = crop_key(points, i, center[0], center[1], center[2]);
+    ids[i] = (unsigned int)i;
+}
+
+__global__ __launch_bounds__(SB_NT) void crop_dist_kernel(const float* __restrict__ points,
+                                                          const unsigned int* __restrict__ sel, int64_t k,
+                                                          const double* __restrict__ center,
+                                                          float* __restrict__ dist, float* __restrict__ pmax) {
+    const int64_t t = (int64_t)blockIdx.x * SB_NT + threadIdx.x;
+    float d = 0.f;
+    if (t < k) dist[t] = d = crop_row_dist<false>(points, sel[t], center);
+    block_max_to(d, pmax);
+}
+
+// possibility[q] += (1 - d / d_max)^2 * weight[label_to_idx(labels[q])]     (:449-450), and the crop's outputs
+__global__ __launch_bounds__(SB_NT) void crop_update_kernel(const float* __restrict__ points,
+                                                            const unsigned int* __restrict__ sel,
+                                                            const int64_t* __restrict__ perm, int64_t k,
+                                                            const double* __restrict__ center,
+                                                            const float* __restrict__ dist,
+                                                            const float* __restrict__ pmax, int nblk,
+                                                            const double* __restrict__ point_weight,
+                                                            double* __restrict__ possibility,
+                                                            int64_t* __restrict__ out_idx,
+                                                            float* __restrict__ out_xyz) {
+    const int64_t t = (int64_t)blockIdx.x * SB_NT + threadIdx.x;
+    if (t >= k) return;
+    const int64_t src = perm ? perm[t] : t;            // output row t shows selected element perm[t] (the shuffle)
+    const int64_t i = sel[src];
+    const float sq = crop_gain(dist[src], crop_dmax(pmax, nblk));
+    // the weights are float64 for train / val (class_weight array) and the python int 1 for test (float32 result)
+    possibility[i] += point_weight ? dmul_rn((double)sq, point_weight[i]) : (double)sq;      // rows of a crop are distinct points
+    crop_write_row<false>(points, nullptr, nullptr, i, center, t, out_xyz, nullptr, 0, nullptr, out_idx);
+}
+
+struct CropWs {                   // workspace of the single-crop entry
+    unsigned long long *keys_in, *keys_out;
+    unsigned int *ids_in, *ids_out;
+    float *dist, *pmax;
+    double* center;
+    char* sort;
+    size_t bytes;
+};
+static CropWs crop_carve(void* workspace, int64_t n, int64_t k) {
+    Carve c(workspace);
+    CropWs w;
+    w.keys_in = c.take<unsigned long long>((size_t)n);
+    w.keys_out = c.take<unsigned long long>((size_t)n);
+    w.ids_in = c.take<unsigned int>((size_t)n);
+    w.ids_out = c.take<unsigned int>((size_t)n);
+    w.dist = c.take<float>((size_t)k);
+    w.pmax = c.take<float>((size_t)cdiv(k, SB_NT));
+    w.center = c.take<double>(3);
+    w.sort = c.take<char>(rsort_workspace(n));      // this library's radix sort (radix_sort.hpp)
+    w.bytes = c.bytes();
+    return w;
+}
+
+// ------------------------------------------------------------------------------------------ the batch forms' workspace and sequence
 struct SbWs {                     // the workspace of one call; the last seven pieces exist in the S3DIS form only
     SbCrop* crop;
     int32_t *hist, *cnt;
@@ -593,6 +691,60 @@ static int sb_run(bool s3dis, const crf_cloud_desc* clouds, int n_clouds, int64_
     return CRF_OK;
 }
 #undef SB_LAUNCH
+
+extern "C" size_t crfconv_argmin_workspace(void) { return SB_ARGMIN_BLOCKS * (sizeof(double) + sizeof(int64_t)); }
+
+extern "C" int crfconv_argmin_f64(const double* values, int64_t n, double* out_value, int64_t* out_index,
+                                  void* workspace, size_t workspace_bytes, crf_stream_t stream) {
+    CRF_REQUIRE(values && out_value && out_index && workspace, CRF_ERR_ARG, "null pointer");
+    CRF_REQUIRE(n > 0, CRF_ERR_ARG, "empty array");
+    CRF_REQUIRE(workspace_bytes >= crfconv_argmin_workspace(), CRF_ERR_WORKSPACE, "argmin workspace too small");
+    double* pv = reinterpret_cast<double*>(workspace);
+    int64_t* pi = reinterpret_cast<int64_t*>(pv + SB_ARGMIN_BLOCKS);
+    int64_t blocks = cdiv(n, SB_NT);
+    if (blocks > SB_ARGMIN_BLOCKS) blocks = SB_ARGMIN_BLOCKS;
+    hipLaunchKernelGGL(argmin_partial_kernel, dim3((unsigned)blocks), dim3(SB_NT), 0, as_stream(stream), values, n, pv, pi);
+    CRF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(argmin_final_kernel, dim3(1), dim3(SB_NT), 0, as_stream(stream), pv, pi, (int)blocks, out_value,
+                       out_index);
+    CRF_LAUNCH_CHECK();
+    return CRF_OK;
+}
+
+extern "C" size_t crfconv_possibility_crop_workspace(int64_t n, int64_t k) {
+    if (n <= 0 || k <= 0) return 0;
+    return crop_carve(nullptr, n, k).bytes;
+}
+
+extern "C" int crfconv_possibility_crop(const float* points, int64_t n, int64_t k, const int64_t* pick_index,
+                                        const double* noise, const int64_t* perm, const double* point_weight,
+                                        double* possibility, int64_t* out_idx, float* out_xyz, double* out_center,
+                                        void* workspace, size_t workspace_bytes, crf_stream_t stream) {
+    CRF_REQUIRE(points && pick_index && possibility && out_idx && out_xyz && workspace, CRF_ERR_ARG, "null pointer");
+    CRF_REQUIRE(n > 0 && k > 0 && k <= n && n < ((int64_t)1 << 32), CRF_ERR_ARG, "n=%lld k=%lld invalid", (long long)n,
+                (long long)k);
+    const CropWs w = crop_carve(workspace, n, k);
+    CRF_REQUIRE(workspace_bytes >= w.bytes, CRF_ERR_WORKSPACE, "possibility_crop workspace %zu < %zu", workspace_bytes, w.bytes);
+    hipStream_t st = as_stream(stream);
+    const int nblk = (int)cdiv(k, SB_NT);
+    hipLaunchKernelGGL(pick_point_kernel, dim3(1), dim3(64), 0, st, points, pick_index, noise, w.center);
+    CRF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(crop_keys_kernel, dim3((unsigned)cdiv(n, SB_NT)), dim3(SB_NT), 0, st, points, n, (const double*)w.center,
+                       w.keys_in, w.ids_in);
+    CRF_LAUNCH_CHECK();
+    // stable LSD radix sort over all eight digits of the float64 keys: equal distances keep ascending point order (the KD-tree's order
+    // on ties is unspecified)
+    const unsigned int* sel = rsort_pairs_u64(w.keys_in, w.ids_in, w.keys_out, w.ids_out, n, 0, 64, w.sort, st) ? w.ids_out : w.ids_in;
+    CRF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(crop_dist_kernel, dim3((unsigned)nblk), dim3(SB_NT), 0, st, points, sel, k, (const double*)w.center, w.dist,
+                       w.pmax);
+    CRF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(crop_update_kernel, dim3((unsigned)nblk), dim3(SB_NT), 0, st, points, sel, perm, k, (const double*)w.center,
+                       (const float*)w.dist, (const float*)w.pmax, nblk, point_weight, possibility, out_idx, out_xyz);
+    CRF_LAUNCH_CHECK();
+    if (out_center) CRF_HIP(hipMemcpyAsync(out_center, w.center, 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
+    return CRF_OK;
+}
 
 extern "C" size_t crfconv_possibility_crop_batch_workspace(int64_t n_max, int64_t k, int64_t B) {
     if (n_max <= 0 || k <= 0 || B <= 0 || k > n_max) return 0;

@@ -1,5 +1,6 @@
 // Exclusive scan of int32 in three small launches (local scan + block totals | scan of the totals by ONE block | add),
-// shared by the reverse-CSR builder (graph.hip) and the kNN grid build (knn.hip).  No scratch memory, no library call:
+// shared by the reverse-CSR builder (graph.hip), the kNN grid build (knn.hip) and the argsort of the Morton codes
+// (collate.hip).  No scratch memory, no library call:
 // the rocPRIM scans / sorts these replaced are not safe to replay from a captured hipGraph on ROCm 7.2 (graph.hip).
 #pragma once
 #include "common.hpp"

@@ -122,7 +122,7 @@ def _spread3(v):
 
 def morton_codes(pos):
     """30-bit Morton (Z-order) codes [B, N] int64 of pos [B, N, 3]: ten bits per axis of the position inside the cloud's
-    bounding cube.  On the device: two launches (csrc/knn.hip: crfconv_morton_codes)."""
+    bounding cube.  On the device: two launches (csrc/collate.hip: crfconv_morton_codes)."""
     if pos.is_cuda and pos.dtype == torch.float32 and pos.dim() == 3 and pos.shape[-1] == 3 and pos.shape[1] > 0:
         from . import _lib
         from .graph import ptr, stream_ptr
@@ -217,7 +217,7 @@ def up_index_from_table(pos, neighbor_idx, choice, rank=None, sub_pos=None):
 
 def _fps_choice(pos, n_sample):
     """[B, n_sample] per-cloud farthest-point picks in pick order, first pick = point 0 -- what the reference's
-    ``tpcuda.furthest_point_sampling(pos, n)`` returns (datasets/semantic3d_dataset.py:520) -- on csrc/knn.hip: fps_kernel
+    ``tpcuda.furthest_point_sampling(pos, n)`` returns (datasets/semantic3d_dataset.py:520) -- on csrc/collate.hip: fps_kernel
     (one workgroup per cloud; ties -> lower index)."""
     from . import _lib
     from .graph import ptr, stream_ptr

@@ -81,7 +81,7 @@ def radius_graph(pos, r, batch=None, loop=False, max_num_neighbors=32):
 
 def fps(pos, batch=None, ratio=0.5, random_start=False):
     """Farthest point sampling per cloud -> sorted global indices (torch_cluster.fps).  One HIP workgroup per cloud
-    (csrc/knn.hip: fps_kernel); the number of picks is ceil(ratio * n) per cloud."""
+    (csrc/collate.hip: fps_kernel); the number of picks is ceil(ratio * n) per cloud."""
     import math
 
     from .. import _lib

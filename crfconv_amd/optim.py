@@ -2,7 +2,7 @@
 wrapped by ExponentialLR).
 
 All parameters of the model become views of ONE contiguous float32 vector, their gradients views of the
-``FlatGradAllReduce`` bucket, and the update is a single kernel launch (csrc/loss.hip: sgd_hyper_kernel) instead of the
+``FlatGradAllReduce`` bucket, and the update is a single kernel launch (csrc/optim.hip: sgd_hyper_kernel) instead of the
 ~15 multi-tensor launches of the framework optimizer.  Same arithmetic, same state (one momentum buffer).
 
 It IS a ``torch.optim.Optimizer``: ``param_groups[0]['lr']`` is the learning rate, so
@@ -152,7 +152,7 @@ class FlatAdam(torch.optim.Optimizer):
     """torch.optim.Adam / AdamW (single-tensor arithmetic, operation for operation) over the flat parameter vector, FlatSGD's sibling:
     it reads the flat gradient bucket, takes the mean inside the update (`grad_scale`), honours the sticky grid-barrier failure words
     and the rank-reduced guard slot, follows an LR scheduler inside a captured graph (``push_hyper()``) and issues no framework kernel:
-    two library launches per step (csrc/loss.hip: adam_prologue_kernel, adam_update_kernel), three with `max_grad_norm`.
+    two library launches per step (csrc/optim.hip: adam_prologue_kernel, adam_update_kernel), three with `max_grad_norm`.
 
     The step count ``t`` is a DEVICE word (``opt.t``, int64): the host does not run while a captured step is replayed, so a launch
     scalar would freeze the bias corrections at capture time.  The one-thread prologue launch reads the guard, advances ``t`` -- not

@@ -7,7 +7,7 @@
   trainval.py:170-214.
 
 The reference does both on the host with sklearn's KDTree and numpy; here the clouds, possibilities and vote tables
-stay in HBM and each call enqueues a handful of kernels of libcrfconv_amd.so (csrc/evaluate.hip).
+stay in HBM and each call enqueues a handful of kernels of libcrfconv_amd.so (csrc/sampler.hip, csrc/evaluate.hip).
 """
 import contextlib
 

@@ -822,24 +822,17 @@ int crfconv_softmax_ce_backward(const float* logits, const int64_t* target, cons
                                 const double* sums, const float* grad_loss, int64_t m, int C, int64_t ignore_index,
                                 int64_t label_shift, float* dlogits, crf_stream_t stream);
 
-/* torch.optim.SGD step (trainval.py:69-72, 105) over one flat float32 parameter vector of n elements:
- *   g = grad + weight_decay * p;  buf = first_step ? g : momentum * buf + (1 - dampening) * g;
- *   g = nesterov ? g + momentum * buf : buf;  p -= lr * g          (momentum == 0: buf unused, may be NULL). */
-int crfconv_sgd_step(float* param, const float* grad, float* momentum_buf, int64_t n, float lr, float momentum,
-                     float dampening, float weight_decay, int nesterov, int first_step, crf_stream_t stream);
-/* The same with hyper = {lr, momentum, dampening, weight_decay, grad_scale} (5 floats) in DEVICE memory, so that a
- * captured graph of the step honours a learning-rate scheduler; grad is multiplied by grad_scale first (1 / world size
- * when the bucket holds the all-reduce SUM; 1 otherwise); momentum_buf is required (zero-filled when momentum is 0). */
-int crfconv_sgd_step_hyper(float* param, const float* grad, float* momentum_buf, int64_t n, const float* hyper,
-                           int nesterov, int first_step, crf_stream_t stream);
-/* The same, guarded by the grid-barrier failure word (crfconv_gridsync_fail_word() of the caller's barrier workspace, device
- * memory; NULL = unguarded): while *fail_word != 0 the launch changes NOTHING -- a one-launch kernel whose barrier timed out has
+/* torch.optim.SGD step (trainval.py:69-72, 105) over one flat float32 parameter vector of n elements (csrc/optim.hip):
+ *   g = grad * grad_scale + weight_decay * p;  buf = first_step ? g : momentum * buf + (1 - dampening) * g;
+ *   g = nesterov ? g + momentum * buf : buf;  p -= lr * g          (momentum == 0: buf is not touched, but required).
+ * hyper: 5 floats in DEVICE memory, so that a captured graph of the step honours a learning-rate scheduler:
+ *   [0] lr  [1] momentum  [2] dampening  [3] weight_decay  [4] grad_scale (1 / world size when the bucket holds the all-reduce SUM
+ *   of the ranks' gradients; 1 otherwise).
+ * Guard: while any guarded word is set the launch changes NOTHING -- a one-launch kernel whose grid barrier timed out has
  * NaN-poisoned its outputs and therefore this step's gradient, and parameters / momentum must survive until the host reads the
- * word (it is sticky; captured replays are protected too). */
-int crfconv_sgd_step_guarded(float* param, const float* grad, float* momentum_buf, int64_t n, const float* hyper,
-                             int nesterov, int first_step, const unsigned* fail_word, crf_stream_t stream);
-/* The guard over SEVERAL sticky words (fail_words: HOST array of n_fail_words <= 8 device pointers -- every barrier workspace of
- * the device: eager streams and the captured-graph buffer each have their own) and over reduced_flag (device float, may be NULL):
+ * word (it is sticky; captured replays are protected too).  fail_words: HOST array of n_fail_words <= 8 device pointers
+ * (crfconv_gridsync_fail_word() of every barrier workspace of the device: eager streams and the captured-graph buffer each have
+ * their own; n_fail_words == 0: none).  reduced_flag (device float, may be NULL):
  * the slot behind the flat gradient bucket that every rank fills with crfconv_sgd_guard_publish BEFORE the gradient all-reduce and
  * that the all-reduce sums with the bucket -- non-zero on every rank when any rank's step failed, so all replicas skip together
  * (the failed rank's NaN gradient is in everybody's bucket by then). */

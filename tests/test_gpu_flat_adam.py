@@ -1,4 +1,4 @@
-"""-m gpu: optim.FlatAdam / FlatAdamW (csrc/loss.hip: adam_sqnorm_kernel, adam_prologue_kernel, adam_update_kernel) against
+"""-m gpu: optim.FlatAdam / FlatAdamW (csrc/optim.hip: adam_sqnorm_kernel, adam_prologue_kernel, adam_update_kernel) against
 torch.optim.Adam / AdamW, and through train.CapturedStep and the self-capturing forward.
 
 Bound of every comparison against torch: ``assert_close_anchored(got, ref32, ref64, 1e-6)`` -- `got` the device result, `ref64` / `ref32`

@@ -74,13 +74,23 @@ def test_knn_duplicates_and_errors(nn_mod):
 
 
 @pytest.mark.parametrize('Np,K', [(6000, 16), (6000, 8), (6000, 2), (6000, 24), (6000, 1), (3000, 16), (3000, 8), (3000, 32),
-                                  (3000, 1), (4096, 16), (4097, 16), (40, 16)])
+                                  (3000, 1), (4096, 16), (4097, 16), (40, 16),
+                                  (4096, 17), (4097, 17), (4097, 32), (4097, 64)])
 def test_knn_clustered_duplicates_every_search_path(nn_mod, Np, K):
     """The three searches of csrc/knn.hip on hostile input -- blobs of very different density, a planar sheet, 10 % exact
     duplicates (ties -> lower id), queries far outside the support -- against the oracle, bit for bit: sixteen lanes per
     query over the whole cloud (<= 4096 points, K in {1, 8, 16, 32}), sixteen lanes per query on the grid with the LDS
     rank selection (larger clouds, 1 < K <= 16; the dense blob overflows the candidate pool and forces mid-ring
-    compactions), one lane per query (everything else)."""
+    compactions), one lane per query (everything else).
+
+    Which search each (Np, K) reaches:
+      whole cloud                   (3000, 1), (3000, 8), (3000, 16), (3000, 32), (4096, 16), (40, 16)
+      grid, sixteen lanes           (6000, 2), (6000, 8), (6000, 16), (4097, 16)
+      grid, one lane, capacity 1    (6000, 1)
+      grid, one lane, capacity 32   (6000, 24); (4097, 17): the first K above the sixteen-lane search; (4097, 32): the capacity
+                                    full; (4096, 17): a cloud small enough for the whole-cloud search with a K that search is not
+                                    compiled for, which must fall through to the grid
+      grid, one lane, capacity 64   (4097, 64): the largest K"""
     rng = np.random.default_rng(Np * 131 + K)
     parts = [rng.normal(0, 0.01, (Np // 4, 3)), rng.normal(2, 0.5, (Np // 4, 3)),
              np.concatenate([rng.uniform(-3, 3, (Np // 4, 2)), np.full((Np // 4, 1), 0.25)], 1)]
