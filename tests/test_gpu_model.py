@@ -10,7 +10,8 @@ import torch.nn as nn
 
 import _seeded as S
 from conftest import sub
-from gpu_util import DEV, assert_close, assert_close_anchored, grads, load_sd, relerr, t
+from gpu_util import (DEV, assert_close, assert_close_anchored, assert_grads_check_can_fail, assert_grads_close, grad_errors, grad_summary, grads,
+                      load_sd, oracle_grads, relerr, t)
 from oracle import crf_oracle as O
 from oracle import native as onative
 
@@ -610,6 +611,17 @@ def test_pointconvbig_golden(golden, use_crf):
         assert float((proj - want).abs().max()) <= 2e-3 * scale * np.sqrt(got.numel()), k
     for k, v in sub(g, tagc + '_train/grad').items():
         assert_close(gr[k], v, 2e-4, 'grad ' + k)            # measured worst: 1.6e-5 (conv1_2.lin_in.lin.weight); was 2e-3
+    # every parameter gradient (not only the stored ones) on its own scale, against the float64 run of the oracle: no entry of the
+    # fixture's gradients reaches 0.1, so the 2e-4 above, relative to max(1, |ref|), is absolute
+    sd = S.fill_state_dict(shapes, 17)
+    ms = [{k: getattr(l, k).cpu() for k in ('pos', 'neighbor_idx', 'sub_idx', 'up_idx')} for l in data.multiscale]
+    torch.set_num_threads(16)
+    g32, g64 = [oracle_grads(sd, g['feats'], ms, g['labels'], int(g['steps']), double, dropout_mask=torch.from_numpy(mask).float(),
+                             class_weights=g['class_weights'], use_crf=use_crf)[2] for double in (False, True)]
+    what = 'g5 %s parameter gradients' % tagc
+    print('[grad scale] %s: %s' % (what, grad_summary(grad_errors(gr, g32, g64), 2e-4)), flush=True)
+    assert_grads_close(gr, g32, g64, 2e-4, what)
+    assert_grads_check_can_fail(gr, g32, g64, 2e-4, what)      # a zeroed / mis-scaled small tensor is rejected
 
 
 def test_b1_is_supported():
@@ -1222,7 +1234,8 @@ def test_benchmarked_training_step_replayed_graph_matches_oracle(cfg, B, N, ncls
     assert_close_anchored(logits, t32, t64, OUT_TOL, 'replayed train logits')       # the stated 1e-4 (measured: 2e-6 normalised, 7e-5 absolute)
     assert_close_anchored(loss, l32, l64, 1e-5, 'replayed loss')
     assert flat.numel() == g64.numel()
-    # per parameter tensor, relative to that tensor's largest gradient entry
+    # per parameter tensor, relative to max(1, that tensor's largest gradient entry): no entry reaches 1, so this bound is an absolute one
+    # (on the tensors' own scale: profiles/r18_gradient_scale.md)
     o, worst = 0, (0.0, '')
     for k in names:
         n = dict(net.named_parameters())[k].numel()
@@ -1349,6 +1362,41 @@ def test_mlp_block_fused_backward(M, Ci, Co, slope, need_dx, min_rows, monkeypat
     assert_close(bn.running_mean, ref.running_mean, 1e-6, 'running_mean')
     assert_close(bn.running_var, ref.running_var, 1e-5, 'running_var')
     assert int(bn.num_batches_tracked) == 1
+
+
+@pytest.mark.parametrize('M,Ci,Co,slope', [(300, 32, 128, 0.1), (333, 64, 16, 1.0), (16400, 32, 128, 0.1)])
+def test_mlp_block_backward_at_the_gradient_scale_of_a_mean_loss(M, Ci, Co, slope):
+    """ops.mlp_block's backward with the upstream gradient a whole network hands it under a mean cross entropy -- entries of 1e-5 with
+    a mean near zero, so that dbeta and dgamma are sums that cancel -- on each result's own scale (assert_grads_close) against float64
+    torch: the one-launch kernel of the coarse levels at a few hundred rows, the row-streaming form above the switch-over.  The
+    LeakyReLU branch is the kernel's own (an element within rounding of the kink is a different FUNCTION, not an error: what the
+    whole-network comparisons cannot separate).  The backward is linear in the upstream gradient, so the bound is the 2e-5 that
+    test_mlp_block_fused_backward holds the same results to at order one, where max(1, |ref|) is |ref|."""
+    from crfconv_amd import ops
+    g = torch.Generator().manual_seed(M + Ci + Co)
+    x = (torch.randn(M, Ci, generator=g) + 0.5).to(DEV).requires_grad_(True)
+    W = (torch.randn(Co, Ci, generator=g) / np.sqrt(Ci)).to(DEV).requires_grad_(True)
+    go = (1e-5 * torch.randn(M, Co, generator=g)).to(DEV)                      # column means of 1e-5 / sqrt(M)
+    bn = torch.nn.BatchNorm1d(Co)
+    with torch.no_grad():
+        bn.weight.copy_(torch.rand(Co, generator=g) + 0.5); bn.bias.copy_(torch.rand(Co, generator=g) * 0.6 - 0.3)
+    bn = bn.to(DEV).train()
+    assert ops.mlp_block_ok(x, W, None, bn, True) and ops._mlp_small_ok(M, Ci, Co) == (M < 4096)
+    out = ops.mlp_block(x, W, bn, slope)
+    out.backward(go)
+    got = {'dx': x.grad, 'dW': W.grad, 'dgamma': bn.weight.grad, 'dbeta': bn.bias.grad}
+    branch = torch.where(out.detach() > 0, 1.0, slope).cpu()
+    refs = []
+    for dt in (torch.float32, torch.float64):
+        xr, Wr, gam, bet = (v.detach().cpu().to(dt).requires_grad_(True) for v in (x, W, bn.weight, bn.bias))
+        y = xr @ Wr.t()
+        pre = (y - y.mean(0)) / torch.sqrt(y.var(0, unbiased=False) + bn.eps) * gam + bet
+        pre.backward((go.cpu() * branch).to(dt))
+        refs.append({'dx': xr.grad, 'dW': Wr.grad, 'dgamma': gam.grad, 'dbeta': bet.grad})
+    assert max(float(v.abs().max()) for v in refs[1].values()) < 1e-2         # relerr's floor of 1 would hide all four
+    rows = grad_errors(got, refs[0], refs[1])
+    print('[grad scale] mlp_block %d x %d -> %d: %s' % (M, Ci, Co, grad_summary(rows, 2e-5)), flush=True)
+    assert_grads_close(got, refs[0], refs[1], 2e-5, 'mlp_block backward, upstream gradient 1e-5', max_under_floor=0)
 
 
 def test_mlp_block_dropout_fused_mask_is_consistent():
