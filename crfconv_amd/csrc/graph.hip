@@ -499,9 +499,9 @@ extern "C" int crfconv_copy_jobs(const crf_copy_job* jobs, int njobs, crf_stream
     return CRF_OK;
 }
 
-extern "C" int crfconv_index_narrow(const int64_t* idx64, int64_t B, int64_t n_tgt, int K,
-                                    int64_t n_src, int32_t* idx32, uint16_t* idx16, int32_t* bad_count,
-                                    crf_stream_t stream) {
+// The table narrowed with its columns left in place: what crfconv_index_narrow_sorted does when nothing is to be re-ordered.
+static int index_narrow(const int64_t* idx64, int64_t B, int64_t n_tgt, int K, int64_t n_src, int32_t* idx32, uint16_t* idx16,
+                        int32_t* bad_count, crf_stream_t stream) {
     CRF_REQUIRE(idx64 && idx32 && bad_count, CRF_ERR_ARG, "null pointer");
     CRF_REQUIRE(idx16 == nullptr || n_src <= 65536, CRF_ERR_ARG, "uint16 table needs n_src <= 65536");
     CRF_REQUIRE(B > 0 && n_tgt > 0 && K > 0 && n_src > 0, CRF_ERR_ARG, "empty table");
@@ -520,7 +520,7 @@ extern "C" int crfconv_index_narrow_sorted(const int64_t* idx64, int64_t B, int6
                                            int32_t* bad_count, crf_stream_t stream) {
     CRF_REQUIRE(sort_from >= 0, CRF_ERR_ARG, "sort_from=%d < 0", sort_from);
     if (sort_from >= K - 1 || K > 64)       // nothing to re-order (or wider than the register network)
-        return crfconv_index_narrow(idx64, B, n_tgt, K, n_src, idx32, idx16, bad_count, stream);
+        return index_narrow(idx64, B, n_tgt, K, n_src, idx32, idx16, bad_count, stream);
     CRF_REQUIRE(idx64 && idx32 && bad_count, CRF_ERR_ARG, "null pointer");
     CRF_REQUIRE(idx16 == nullptr || n_src <= 65536, CRF_ERR_ARG, "uint16 table needs n_src <= 65536");
     CRF_REQUIRE(B > 0 && n_tgt > 0 && K > 0 && n_src > 0, CRF_ERR_ARG, "empty table");

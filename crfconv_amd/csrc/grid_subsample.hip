@@ -192,13 +192,13 @@ static GsLayout gs_layout(int64_t N) {
 
 using namespace crf;
 
-extern "C" size_t crfconv_grid_subsample_dev_workspace(int64_t N, int fdim, int ldim) {
+static size_t grid_subsample_dev_workspace(int64_t N, int fdim, int ldim) {
     (void)fdim; (void)ldim;
     if (N <= 0) return 0;
     return gs_layout(N).total;
 }
 
-extern "C" int64_t crfconv_grid_subsample_dev(const float* points, int64_t N, const float* feats, int fdim,
+static int64_t grid_subsample_dev(const float* points, int64_t N, const float* feats, int fdim,
                                               const int32_t* classes, int ldim, float sampleDl,
                                               float* out_points, float* out_feats, int32_t* out_classes,
                                               int64_t cap, void* workspace, size_t workspace_bytes,
@@ -273,7 +273,7 @@ extern "C" int64_t crfconv_grid_subsample(const float* points, int64_t N, const 
     CRF_REQUIRE(points && out_points, CRF_ERR_ARG, "null pointer");
     CRF_REQUIRE(N > 0, CRF_ERR_ARG, "empty cloud");
     if (cap > N) cap = N;
-    const size_t wsb = crfconv_grid_subsample_dev_workspace(N, fdim, ldim);
+    const size_t wsb = grid_subsample_dev_workspace(N, fdim, ldim);
     float *dp = nullptr, *df = nullptr, *dop = nullptr, *dof = nullptr;
     int32_t *dc = nullptr, *doc = nullptr;
     void* ws = nullptr;
@@ -294,7 +294,7 @@ extern "C" int64_t crfconv_grid_subsample(const float* points, int64_t N, const 
         TRY(hipMemcpy(dc, classes, sizeof(int32_t) * ldim * N, hipMemcpyHostToDevice));
     }
     TRY(hipMalloc(&ws, wsb));
-    rc = crfconv_grid_subsample_dev(dp, N, df, fdim, dc, ldim, sampleDl, dop, dof, doc, cap, ws, wsb, nullptr);
+    rc = grid_subsample_dev(dp, N, df, fdim, dc, ldim, sampleDl, dop, dof, doc, cap, ws, wsb, nullptr);
     if (rc < 0) goto done;
     TRY(hipMemcpy(out_points, dop, sizeof(float) * 3 * rc, hipMemcpyDeviceToHost));
     if (feats) TRY(hipMemcpy(out_feats, dof, sizeof(float) * fdim * rc, hipMemcpyDeviceToHost));

@@ -1,6 +1,6 @@
 """Device-side graph builders with the call signatures of the torch_cluster / torch_geometric functions the
 reference's sparse path uses (models/point_conv.py:5, 341-396; models/continuous_crf_conv.py:53):
-knn_graph, knn, radius_graph, fps -- all on top of the exact HIP grid kNN (csrc/knn.hip).
+knn_graph, knn, radius_graph, fps -- all on top of the exact HIP grid kNN (csrc/knn.hip), one segmented search per graph.
 
 Conventions (PyG): an edge_index is [2, E] with row 0 = source j ("col"), row 1 = target i ("row").
 Third-party semantics are unpinned (no version, no tests in the reference): knn_* are exact; radius_graph keeps
@@ -24,43 +24,61 @@ def _segments(batch, n):
     return out
 
 
-def _knn_segments(x, y, k, seg_x, seg_y):
-    """For every y row the k nearest x rows of the same cloud -> (y_index, x_index) global ids, nearest first."""
-    rows, cols = [], []
-    for (xs, xe), (ys, ye) in zip(seg_x, seg_y):
-        kk = min(k, xe - xs)
-        idx = nn_.knn_batch_device(x[xs:xe].unsqueeze(0), y[ys:ye].unsqueeze(0), kk)[0]     # [ny, kk]
-        rows.append((torch.arange(ys, ye, device=x.device).unsqueeze(1).expand(-1, kk)).reshape(-1))
-        cols.append((idx + xs).reshape(-1))
-    return torch.cat(rows), torch.cat(cols)
+def _ptr(batch, n, clouds, device):
+    """int64 [clouds + 1] row boundaries of a sorted `batch` vector over n rows (None -> one cloud), made on the device."""
+    if batch is None:
+        return torch.tensor([0, n], dtype=torch.int64, device=device)
+    out = torch.zeros(clouds + 1, dtype=torch.int64, device=device)
+    out[1:] = torch.cumsum(torch.bincount(batch, minlength=clouds), 0)
+    return out
+
+
+def _knn_table(x, y, k, batch_x, batch_y):
+    """[Ny, k] global x rows: for every y row the k nearest x rows of the same cloud, nearest first, -1 where the cloud has fewer
+    than k -- ONE search for all clouds (csrc/knn.hip: crfconv_knn_segments_dev)."""
+    clouds = 1
+    if batch_x is not None or batch_y is not None:
+        if batch_x is None or batch_y is None:
+            raise ValueError('batch_x and batch_y must be given together')
+        clouds = int(torch.maximum(batch_x.max(), batch_y.max())) + 1 if batch_x.numel() and batch_y.numel() else 1
+    k = min(k, x.shape[0])              # no cloud has more points than that; the columns left out would be -1
+    return nn_.knn_segments_device(x, _ptr(batch_x, x.shape[0], clouds, x.device), y, _ptr(batch_y, y.shape[0], clouds, x.device), k)
+
+
+def _knn_segments(x, y, k, batch_x, batch_y):
+    """For every y row the k nearest x rows of the same cloud -> (y_index, x_index) global ids, nearest first, cloud by cloud;
+    a cloud with fewer than k points gives each of its y rows as many edges as it has points."""
+    idx = _knn_table(x, y, k, batch_x, batch_y)
+    row, slot = (idx >= 0).nonzero(as_tuple=True)           # row-major order
+    return row, idx[row, slot]
 
 
 def knn_dilated(x, y, k, dilation, batch_x=None, batch_y=None, generator=None):
     """The reference's random dilation (models/point_conv.py:357-364, 387-394): search k * dilation neighbours, keep k
-    of them per query, drawn with replacement by torch.randint.  Done per cloud so that a cloud with fewer than
+    of them per query, drawn with replacement by torch.randint.  Drawn per cloud so that a cloud with fewer than
     k * dilation points (the coarse levels of small clouds) draws from the neighbours it has instead of indexing
-    past them.  -> (y_index, x_index)."""
+    past them; the search is one call for all clouds.  -> (y_index, x_index)."""
+    seg_x, seg_y = _segments(batch_x, x.shape[0]), _segments(batch_y, y.shape[0])
+    idx = _knn_table(x, y, min(k * dilation, max(xe - xs for xs, xe in seg_x)), batch_x, batch_y)
     rows, cols = [], []
-    for (xs, xe), (ys, ye) in zip(_segments(batch_x, x.shape[0]), _segments(batch_y, y.shape[0])):
+    for (xs, xe), (ys, ye) in zip(seg_x, seg_y):
         have = min(k * dilation, xe - xs)
-        idx = nn_.knn_batch_device(x[xs:xe].unsqueeze(0), y[ys:ye].unsqueeze(0), have)[0]     # [ny, have]
         keep = min(k, have)
         pick = torch.randint(have, (ye - ys, keep), dtype=torch.long, device=x.device, generator=generator)
         rows.append(torch.arange(ys, ye, device=x.device).unsqueeze(1).expand(-1, keep).reshape(-1))
-        cols.append((idx.gather(1, pick) + xs).reshape(-1))
+        cols.append(idx[ys:ye].gather(1, pick).reshape(-1))
     return torch.cat(rows), torch.cat(cols)
 
 
 def knn(x, y, k, batch_x=None, batch_y=None):
     """torch_cluster.knn: [2, E] = [y index; x index]."""
-    row, col = _knn_segments(x, y, k, _segments(batch_x, x.shape[0]), _segments(batch_y, y.shape[0]))
+    row, col = _knn_segments(x, y, k, batch_x, batch_y)
     return torch.stack([row, col])
 
 
 def knn_graph(pos, k, batch=None, loop=False):
     """torch_cluster.knn_graph (flow source_to_target): [2, E] = [neighbour j; node i]."""
-    seg = _segments(batch, pos.shape[0])
-    row, col = _knn_segments(pos, pos, k if loop else k + 1, seg, seg)
+    row, col = _knn_segments(pos, pos, k if loop else k + 1, batch, batch)
     if not loop:
         keep = row != col
         row, col = row[keep], col[keep]
@@ -69,9 +87,8 @@ def knn_graph(pos, k, batch=None, loop=False):
 
 def radius_graph(pos, r, batch=None, loop=False, max_num_neighbors=32):
     """[2, E] = [neighbour j; node i] for |p_i - p_j| <= r, at most max_num_neighbors per node."""
-    seg = _segments(batch, pos.shape[0])
     k = max_num_neighbors + (0 if loop else 1)
-    row, col = _knn_segments(pos, pos, k, seg, seg)
+    row, col = _knn_segments(pos, pos, k, batch, batch)
     d2 = ((pos[row] - pos[col]) ** 2).sum(1)
     keep = d2 <= r * r
     if not loop:
@@ -101,8 +118,4 @@ def fps(pos, batch=None, ratio=0.5, random_start=False):
     ws = torch.empty(pos.shape[0], dtype=torch.float32, device=dev)
     _lib.call('crfconv_fps', ptr(p), len(segs), ptr(starts), ptr(cnt), ptr(ostart), ptr(npick), ptr(first), ptr(ws),
               ptr(out), stream_ptr())
-    pieces, o = [], 0
-    for k in picks:
-        pieces.append(out[o:o + k].sort().values)
-        o += k
-    return torch.cat(pieces)
+    return out.sort().values            # picks are global rows and clouds are contiguous: one sort orders every cloud's picks

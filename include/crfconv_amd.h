@@ -6,15 +6,15 @@
  *        utils/nearest_neighbors/knn_.h:2-19          (cpp_knn / cpp_knn_omp / cpp_knn_batch / cpp_knn_batch_omp)
  *        utils/cpp_wrappers/cpp_subsampling/grid_subsampling/grid_subsampling.h:84-91 (grid_subsampling)
  *      Host-pointer forms keep the reference signatures (same argument order and meaning,
- *      caller-owned buffers); `_dev` forms take device pointers + a hipStream_t and are what the
- *      Python host (crfconv_amd.utils.nearest_neighbors / cpp_subsampling) drives.
+ *      caller-owned buffers); the kNN's `_dev` forms take device pointers + a hipStream_t and are what
+ *      crfconv_amd.utils.nearest_neighbors drives for tensors on the device.
  *
  *  (B) The fused device kernels behind the nn.Module mirrors (crfconv_amd.models):
  *        CRF mean field   <- models/continuous_crf_conv_big.py:49-54, 63-72 (+ sparse :56-67)
  *        PointConv        <- models/point_conv_big.py:37-58
  *        neighbour max-pool / nearest up-sampling <- models/point_conv_big.py:74-77, 97-101
  *      All tensors are dense row-major fp32; neighbour tables are int32 GLOBAL row ids
- *      (cloud b, local id j  ->  b * n_src + j) produced once per batch by crfconv_index_narrow.
+ *      (cloud b, local id j  ->  b * n_src + j) produced once per batch by crfconv_index_narrow_sorted.
  *
  * Every function returns CRF_OK (0) or a negative error code; crfconv_last_error() gives the
  * message (thread-local).  Device entry points only enqueue work on `stream`; they never
@@ -80,6 +80,29 @@ int crfconv_knn_batch_dev(const float* pts, size_t batch_size, size_t npts, size
                           int32_t* out_i32, void* workspace, size_t workspace_bytes,
                           crf_stream_t stream);
 
+/* The same search over a RAGGED batch in one call (torch_cluster.knn(x, y, k, batch_x, batch_y)): segment s owns rows
+ * pts_ptr[s] .. pts_ptr[s + 1] of pts [total_pts, 3] and rows q_ptr[s] .. q_ptr[s + 1] of queries [total_queries, 3]; pts_ptr / q_ptr are
+ * DEVICE int64 [n_segments + 1].  Row q of the output [total_queries, K] holds the K nearest points of q's own segment as GLOBAL rows of
+ * pts, ascending by the key of crfconv_knn_batch_dev (distance bits, then the id within the cloud): for a segment with >= K points it
+ * is that entry's row for the cloud alone plus pts_ptr[s], bit for bit.  A segment with n_s < K points fills its first n_s columns and
+ * writes -1 into the rest; queries of a segment without points, and rows outside every segment, get -1 rows; a segment without
+ * queries is legal.  1 <= K <= 64, 1 <= n_segments <= 65535, total_pts < 2^31 with 8 n_segments + 4 total_pts < 2^31 - 1,
+ * total_queries < 2^28.
+ * The host passes only the three sizes (tensor shapes): segment sizes, grid resolutions and each segment's place in the cell arrays are
+ * computed on the device, so the call reads nothing back, can be captured into a hipGraph, and a replay follows whatever the pointer
+ * arrays hold then.  They are not validated but clamped: their running maximum inside [0, total] is what the kernels use, so a
+ * non-monotone or too large array gives wrong neighbours for its own segments and addresses nothing outside the buffers.  NaN /
+ * infinite coordinates never extend a search; a NaN distance is never a neighbour.
+ * Workspace: sized from (n_segments, total_pts) alone by a bound over every possible split, 8 n_segments + 4 total_pts grid cells
+ * (csrc/knn.hip: seg_cells_bound, with the proof).  crfconv_knn_segments_need(seg_sizes, n_segments) -- seg_sizes a HOST array -- is
+ * what one given split uses, for checking the bound without a device. */
+size_t crfconv_knn_segments_dev_workspace(size_t n_segments, size_t total_pts, size_t total_queries, size_t K);
+size_t crfconv_knn_segments_need(const int64_t* seg_sizes, size_t n_segments);
+int crfconv_knn_segments_dev(const float* pts, const int64_t* pts_ptr, const float* queries, const int64_t* q_ptr,
+                             size_t n_segments, size_t total_pts, size_t total_queries, size_t dim, size_t K,
+                             int64_t* out_i64, int32_t* out_i32, void* workspace, size_t workspace_bytes,
+                             crf_stream_t stream);
+
 /* Farthest point sampling per cloud (torch_cluster.fps as called at models/point_conv.py:381).  All descriptor arrays
  * are device int64 [n_clouds]: seg_start / seg_count = the cloud's rows in pos [N, 3]; n_sample = picks per cloud
  * (<= seg_count); first = local index of the first pick; out_start = offset of the cloud's picks in out.  Picks are
@@ -97,25 +120,15 @@ int crfconv_fps(const float* pos, int n_clouds, const int64_t* seg_start, const 
 int64_t crfconv_grid_subsample(const float* points, int64_t N, const float* feats, int fdim,
                                const int32_t* classes, int ldim, float sampleDl, float* out_points,
                                float* out_feats, int32_t* out_classes, int64_t cap);
-size_t crfconv_grid_subsample_dev_workspace(int64_t N, int fdim, int ldim);
-/* Device buffers; synchronises `stream` once (the row count comes back to the host). */
-int64_t crfconv_grid_subsample_dev(const float* points, int64_t N, const float* feats, int fdim,
-                                   const int32_t* classes, int ldim, float sampleDl,
-                                   float* out_points, float* out_feats, int32_t* out_classes,
-                                   int64_t cap, void* workspace, size_t workspace_bytes,
-                                   crf_stream_t stream);
 
 /* ===================================================================== (B) neighbour tables
  * idx64 [B, n_tgt, K] per-cloud local ids into n_src points  ->  idx32 [B*n_tgt, K] global rows.
  * Out-of-range entries are clamped and counted into *bad_count (device int32, caller zeroes it);
  * the host must check it before any kernel consumes the table.  idx16 (may be NULL; needs n_src <= 65536)
- * additionally receives the per-cloud LOCAL ids as uint16 -- half the index bytes for the streaming kernels. */
-int crfconv_index_narrow(const int64_t* idx64, int64_t B, int64_t n_tgt, int K, int64_t n_src,
-                         int32_t* idx32, uint16_t* idx16, int32_t* bad_count, crf_stream_t stream);
-
-/* Same, with columns sort_from .. K-1 of every row re-ordered by ascending source id (sort_from = 1 keeps the
- * self column of a self-query kNN table in place).  Consumers reduce over the columns of a row, so the order is
- * free; ascending ids make the k-th gathers of adjacent target rows hit adjacent source rows. */
+ * additionally receives the per-cloud LOCAL ids as uint16 -- half the index bytes for the streaming kernels.
+ * Columns sort_from .. K-1 of every row are re-ordered by ascending source id (sort_from = 1 keeps the
+ * self column of a self-query kNN table in place; sort_from >= K - 1 leaves every column where it is).  Consumers reduce over the
+ * columns of a row, so the order is free; ascending ids make the k-th gathers of adjacent target rows hit adjacent source rows. */
 int crfconv_index_narrow_sorted(const int64_t* idx64, int64_t B, int64_t n_tgt, int K, int64_t n_src,
                                 int sort_from, int32_t* idx32, uint16_t* idx16, int32_t* bad_count,
                                 crf_stream_t stream);
