@@ -103,16 +103,6 @@ __device__ __forceinline__ int group_bcast_i(int v, int base_lane) {
     return __float_as_int(group_bcast<L, HQ>(__int_as_float(v), base_lane));
 }
 
-// STAMP: diagnostic build only (crfconv_meanfield_forward_block_stamps): thread 0 of every workgroup writes 100 MHz s_memrealtime
-// stamps of its phases to dbg[block][..]; no output depends on them.
-#define BLK_STAMP(slot)                                                                           \
-    do {                                                                                          \
-        if constexpr (STAMP) {                                                                    \
-            const unsigned long long t_ = __builtin_amdgcn_s_memrealtime();                       \
-            if (threadIdx.x == 0) dbg[(size_t)blockIdx.x * 64 + (slot)] = t_;                     \
-        }                                                                                         \
-    } while (0)
-
 // The grid barrier of gridsync.hpp (fused_grid_sync: same words, same counting) in two halves, so that work that needs nothing from
 // other workgroups can sit between them.  blk_arrive: call after every wavefront has drained its write-through stores AND the
 // workgroup has synchronised; blk_wait returns false (for the whole workgroup) when the spin gave up.
@@ -148,13 +138,12 @@ __device__ __forceinline__ bool blk_wait(unsigned* ws, unsigned phase, int* s_ok
     return *s_ok != 0;
 }
 
-template <int H, int K, int NW, int HP, bool U16, bool STAMP = false>
+template <int H, int K, int NW, int HP, bool U16>
 __global__ __launch_bounds__(NW * WAVE) void mf_block_kernel(const float* __restrict__ y, const float* __restrict__ z,
                                                              const int32_t* __restrict__ idx, const uint16_t* __restrict__ idx16,
                                                              int n_tgt, int n_src, const float* __restrict__ Q,
                                                              const float* __restrict__ P, float* __restrict__ s, float* xs,
-                                                             int64_t m64, int T, unsigned* ws, unsigned long long* dbg) {
-    BLK_STAMP(0);
+                                                             int64_t m64, int T, unsigned* ws) {
     using G = BlkGeo<H, NW, HP>;
     constexpr int L = G::L, PPW = G::PPW, NT = G::NT, PB = G::PB, RB = G::RB, PPL = G::PPL, CPR = K / 4, NCH = PPW * CPR, KL = K / L;
     constexpr int TAG = (int)0x80000000u;
@@ -212,7 +201,6 @@ __global__ __launch_bounds__(NW * WAVE) void mf_block_kernel(const float* __rest
     mq.park(sQ);
     mp.park(sP);
     __syncthreads();
-    BLK_STAMP(1);
 
     const int step_bytes = m * RB;
     const __amdgpu_buffer_rsrc_t ry = make_rsrc(y, step_bytes), rz = make_rsrc(z, step_bytes);
@@ -301,7 +289,6 @@ __global__ __launch_bounds__(NW * WAVE) void mf_block_kernel(const float* __rest
         }
         __builtin_amdgcn_sched_barrier(0);             // one point's rows at a time: the next pass's gathers are NOT hoisted over this one's arithmetic (registers)
     }
-    BLK_STAMP(2);
     // x_1 first (what the other workgroups wait for), the weight rows behind it: the barrier's drain below leaves them in flight
     if (T > 0) {
 #pragma unroll
@@ -336,7 +323,6 @@ __global__ __launch_bounds__(NW * WAVE) void mf_block_kernel(const float* __rest
     for (int p = 0; p < PPL; ++p)
         if (act(p)) bufA[(rl[p] + 1) * L + q] = o[p];
     __syncthreads();
-    BLK_STAMP(3);
 
     // ---------------------------------------------------------------- steps 2 .. T
     // sum over the columns whose rows are in the block (LDS; the others read the zero row) / outside it (buffer loads; the others
@@ -378,19 +364,15 @@ __global__ __launch_bounds__(NW * WAVE) void mf_block_kernel(const float* __rest
         }
         float4 msgin[PPL];
         msgin[0] = inblock(std::integral_constant<int, 0>{}, q16);
-        BLK_STAMP(8 * t + 0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // the x_t rows have left
         __syncthreads();
-        BLK_STAMP(8 * t + 4);
         blk_arrive(ws, (unsigned)t, n_in_group, n_groups);
         if (t == 1 && s != nullptr) store_weights();
         static_for<PPL - 1>([&](auto PP) {
             constexpr int p1 = decltype(PP)::value + 1;
             if (act(p1)) msgin[p1] = inblock(std::integral_constant<int, p1>{}, q16);
         });
-        BLK_STAMP(8 * t + 5);
         if (!blk_wait(ws, (unsigned)t, &s_ok)) return;
-        BLK_STAMP(8 * t + 1);
         const int sbase = (t - 1) * step_bytes;
 #pragma unroll
         for (int p = 0; p < PPL; ++p) {
@@ -420,17 +402,12 @@ __global__ __launch_bounds__(NW * WAVE) void mf_block_kernel(const float* __rest
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        BLK_STAMP(8 * t + 2);
         if (t + 1 < T) {                              // (blk_wait's barrier: every wavefront is done with x_{t-1} in bufA)
 #pragma unroll
             for (int p = 0; p < PPL; ++p)
                 if (act(p)) bufA[(rl[p] + 1) * L + q] = o[p];
             __syncthreads();
         }
-    }
-    if constexpr (STAMP) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        BLK_STAMP(7);
     }
     fused_exit_reset(ws, gridDim.x, T, blockIdx.x);
 #undef BLK_BOTH
@@ -494,7 +471,7 @@ int launch_block(const float* z, const float* y, const int32_t* idx32, const uin
                  const float* Q, const float* P, int T, float* s, float* xs, unsigned* ws, int nblk, hipStream_t st) {
     dispatch_flag(idx16 != nullptr, [&](auto U16) {
         hipLaunchKernelGGL((mf_block_kernel<H, K, NW, HP, decltype(U16)::value>), dim3((unsigned)nblk), dim3(NW * WAVE), 0, st, y, z, idx32,
-                           idx16, n_tgt, n_src, Q, P, s, xs, m, T, ws, (unsigned long long*)nullptr);
+                           idx16, n_tgt, n_src, Q, P, s, xs, m, T, ws);
     });
     CRF_LAUNCH_CHECK();
     return CRF_OK;
@@ -533,23 +510,6 @@ extern "C" int crfconv_meanfield_forward_block(const float* z, const float* y, c
     BLK_CASE(12, 4);
 #undef BLK_CASE
     CRF_REQUIRE(false, CRF_ERR_UNSUPPORTED, "block-resident mean field: no kernel for %d wavefronts x %d passes", pl.nw, pl.ppl);
-}
-
-/* Diagnostic twin (scratch/mf_block_stamps.py): 100 MHz phase stamps per workgroup in dbg [blocks][64] (u64); 640 rows per workgroup
- * (shape 0: 8 wavefronts x 5 half passes -- the shipped shape; 1: 10 wavefronts x 2 passes), uint16 tables only. */
-extern "C" int crfconv_meanfield_forward_block_stamps(const float* z, const float* y, const int32_t* idx32, const uint16_t* idx16,
-                                                      int n_tgt, int n_src, int64_t m, const float* Q, const float* P, int T, float* s,
-                                                      float* xs, void* ws, int shape, unsigned long long* dbg, crf_stream_t stream) {
-    CRF_REQUIRE(z && y && idx32 && idx16 && Q && P && s && xs && ws && dbg && T >= 1, CRF_ERR_ARG, "null pointer");
-    CRF_REQUIRE(cdiv(m, 640) <= device_cus() && m * 32 * (int64_t)T < ((int64_t)1 << 31) - 4096, CRF_ERR_UNSUPPORTED, "too many rows");
-    if (shape == 1)
-        hipLaunchKernelGGL((mf_block_kernel<8, 16, 10, 4, true, true>), dim3((unsigned)cdiv(m, 640)), dim3(640), 0, as_stream(stream), y, z, idx32, idx16,
-                           n_tgt, n_src, Q, P, s, xs, m, T, reinterpret_cast<unsigned*>(ws), dbg);
-    else
-        hipLaunchKernelGGL((mf_block_kernel<8, 16, 8, 5, true, true>), dim3((unsigned)cdiv(m, 640)), dim3(512), 0, as_stream(stream), y, z, idx32, idx16,
-                           n_tgt, n_src, Q, P, s, xs, m, T, reinterpret_cast<unsigned*>(ws), dbg);
-    CRF_LAUNCH_CHECK();
-    return CRF_OK;
 }
 
 extern "C" int crfconv_block_locality(const int32_t* idx32, int64_t m, int K, int k0, int rows, unsigned long long* count, crf_stream_t stream) {

@@ -288,6 +288,23 @@ class batched_reverse:
         return False
 
 
+def table_from_index(idx32, n_src):
+    """An int32 ``[n_tgt, K]`` tensor of global source rows, -1 where there is no neighbour (what the segmented kNN writes), as a padded
+    NeighborTable: no copy, B = 1, padded = True, the reverse CSR built lazily like every table's (crfconv_reverse_csr skips the
+    negative entries and keeps ascending edge ids).  Nothing is read back: entries outside [0, n_src) are "no neighbour" to the
+    kernels that take padded tables."""
+    require_gpu(idx32)
+    if idx32.dim() != 2 or idx32.dtype != torch.int32 or idx32.shape[1] < 1 or not idx32.is_contiguous():
+        raise ValueError('table_from_index needs a contiguous int32 [n_tgt, K] tensor, K >= 1 (got %s %s)' % (tuple(idx32.shape), idx32.dtype))
+    tab = NeighborTable.__new__(NeighborTable)
+    tab.B, tab.n_tgt, tab.n_src = 1, int(idx32.shape[0]), int(n_src)
+    tab._rev, tab._checked, tab.cache, tab.idx16 = None, True, {}, None
+    tab.padded = True                     # -1 entries: the fast row kernels (no j < 0 test) must not see this table
+    tab._bad = torch.zeros(1, dtype=torch.int32, device=idx32.device)
+    tab.K, tab.n_edges, tab.idx32 = int(idx32.shape[1]), idx32.numel(), idx32
+    return tab
+
+
 def table_from_edges(tgt, src, n_tgt, n_src, max_degree=64):
     """Variable-degree edge list -> padded NeighborTable.
 
@@ -299,14 +316,9 @@ def table_from_edges(tgt, src, n_tgt, n_src, max_degree=64):
     require_gpu(tgt, src)
     E = tgt.numel()
     dev = tgt.device
-    tab = NeighborTable.__new__(NeighborTable)
-    tab.B, tab.n_tgt, tab.n_src = 1, int(n_tgt), int(n_src)
-    tab._rev, tab._checked, tab.cache, tab.idx16 = None, True, {}, None
-    tab.padded = True                     # -1 entries: the fast row kernels (no j < 0 test) must not see this table
-    tab._bad = torch.zeros(1, dtype=torch.int32, device=dev)
     if E == 0:
-        tab.K, tab.n_edges = 1, 0
-        tab.idx32 = torch.full((n_tgt, 1), -1, dtype=torch.int32, device=dev)
+        tab = table_from_index(torch.full((n_tgt, 1), -1, dtype=torch.int32, device=dev), n_src)
+        tab.n_edges = 0
         return tab
     if int(src.min()) < 0 or int(src.max()) >= n_src or int(tgt.min()) < 0 or int(tgt.max()) >= n_tgt:
         raise IndexError('edge endpoints outside [0, n)')
@@ -320,7 +332,8 @@ def table_from_edges(tgt, src, n_tgt, n_src, max_degree=64):
     rank = torch.arange(E, device=dev) - start[ts]
     idx = torch.full((n_tgt, kmax), -1, dtype=torch.int32, device=dev)
     idx[ts, rank] = ss.to(torch.int32)
-    tab.K, tab.n_edges, tab.idx32 = kmax, E, idx
+    tab = table_from_index(idx, n_src)
+    tab.n_edges = E
     return tab
 
 

@@ -8,6 +8,8 @@ the NEAREST `max_num_neighbors` inside the radius (torch_cluster keeps the first
 first point of each cloud unless random_start=True."""
 import torch
 
+from ..graph import table_from_index
+from ..ops.interp import segment_ptr as _ptr
 from ..utils import nearest_neighbors as nn_
 
 
@@ -24,17 +26,8 @@ def _segments(batch, n):
     return out
 
 
-def _ptr(batch, n, clouds, device):
-    """int64 [clouds + 1] row boundaries of a sorted `batch` vector over n rows (None -> one cloud), made on the device."""
-    if batch is None:
-        return torch.tensor([0, n], dtype=torch.int64, device=device)
-    out = torch.zeros(clouds + 1, dtype=torch.int64, device=device)
-    out[1:] = torch.cumsum(torch.bincount(batch, minlength=clouds), 0)
-    return out
-
-
 def _knn_table(x, y, k, batch_x, batch_y):
-    """[Ny, k] global x rows: for every y row the k nearest x rows of the same cloud, nearest first, -1 where the cloud has fewer
+    """int32 [Ny, k] global x rows: for every y row the k nearest x rows of the same cloud, nearest first, -1 where the cloud has fewer
     than k -- ONE search for all clouds (csrc/knn.hip: crfconv_knn_segments_dev)."""
     clouds = 1
     if batch_x is not None or batch_y is not None:
@@ -42,15 +35,22 @@ def _knn_table(x, y, k, batch_x, batch_y):
             raise ValueError('batch_x and batch_y must be given together')
         clouds = int(torch.maximum(batch_x.max(), batch_y.max())) + 1 if batch_x.numel() and batch_y.numel() else 1
     k = min(k, x.shape[0])              # no cloud has more points than that; the columns left out would be -1
-    return nn_.knn_segments_device(x, _ptr(batch_x, x.shape[0], clouds, x.device), y, _ptr(batch_y, y.shape[0], clouds, x.device), k)
+    return nn_.knn_segments_device(x, _ptr(batch_x, x.shape[0], clouds, x.device), y, _ptr(batch_y, y.shape[0], clouds, x.device), k,
+                                   out_dtype=torch.int32)
 
 
 def _knn_segments(x, y, k, batch_x, batch_y):
     """For every y row the k nearest x rows of the same cloud -> (y_index, x_index) global ids, nearest first, cloud by cloud;
     a cloud with fewer than k points gives each of its y rows as many edges as it has points."""
+    row, col, _ = _knn_edges(x, y, k, batch_x, batch_y)
+    return row, col
+
+
+def _knn_edges(x, y, k, batch_x, batch_y):
+    """_knn_segments and the table the edges were read from."""
     idx = _knn_table(x, y, k, batch_x, batch_y)
     row, slot = (idx >= 0).nonzero(as_tuple=True)           # row-major order
-    return row, idx[row, slot]
+    return row, idx[row, slot].long(), idx
 
 
 def knn_dilated(x, y, k, dilation, batch_x=None, batch_y=None, generator=None):
@@ -66,14 +66,17 @@ def knn_dilated(x, y, k, dilation, batch_x=None, batch_y=None, generator=None):
         keep = min(k, have)
         pick = torch.randint(have, (ye - ys, keep), dtype=torch.long, device=x.device, generator=generator)
         rows.append(torch.arange(ys, ye, device=x.device).unsqueeze(1).expand(-1, keep).reshape(-1))
-        cols.append(idx[ys:ye].gather(1, pick).reshape(-1))
+        cols.append(idx[ys:ye].gather(1, pick).reshape(-1).long())
     return torch.cat(rows), torch.cat(cols)
 
 
 def knn(x, y, k, batch_x=None, batch_y=None):
-    """torch_cluster.knn: [2, E] = [y index; x index]."""
-    row, col = _knn_segments(x, y, k, batch_x, batch_y)
-    return torch.stack([row, col])
+    """torch_cluster.knn: [2, E] = [y index; x index].  The search's own int32 table ([Ny, k], -1 = no neighbour) rides on the returned
+    tensor as `_crf_knn_table` (a padded NeighborTable over the x rows): knn_interpolate blends over it without a second search."""
+    row, col, idx = _knn_edges(x, y, k, batch_x, batch_y)
+    edges = torch.stack([row, col])
+    edges._crf_knn_table = table_from_index(idx, x.shape[0])
+    return edges
 
 
 def knn_graph(pos, k, batch=None, loop=False):

@@ -89,12 +89,13 @@ ENC_WIDTHS = (32, 64, 128, 256, 512)
 
 
 def knn_interpolate(x, pos_x, pos_y, batch_x=None, batch_y=None, k=3):
-    """torch_geometric.nn.knn_interpolate: inverse-squared-distance blend of the k nearest source features."""
-    row, col = graph_ops.knn(pos_x, pos_y, k, batch_x, batch_y)                 # y index, x index
-    w = 1.0 / ((pos_y[row] - pos_x[col]) ** 2).sum(1, keepdim=True).clamp_min(1e-16)
-    num = torch.zeros((pos_y.shape[0], x.shape[1]), dtype=x.dtype, device=x.device).index_add_(0, row, x[col] * w)
-    den = torch.zeros((pos_y.shape[0], 1), dtype=x.dtype, device=x.device).index_add_(0, row, w)
-    return num / den
+    """torch_geometric.nn.knn_interpolate: inverse-squared-distance blend of the k nearest source features, one fused launch over the
+    table of its search (ops.interpolate); rows whose cloud has no source are zero."""
+    edges = graph_ops.knn(pos_x, pos_y, k, batch_x, batch_y)                    # [y index; x index]
+    table = getattr(edges, '_crf_knn_table', None)
+    if table is None:                                                           # an edge list from somewhere else: group it by target
+        table = table_from_edges(edges[0], edges[1], pos_y.shape[0], pos_x.shape[0])
+    return ops.interpolate(x, pos_x, pos_y, table)
 
 
 def _lin_bn_act(cin, cout):

@@ -8,17 +8,18 @@
     rows       residual join, LeakyReLU, row gather, neighbour max-pool
     loss       weighted soft-max cross-entropy
     pointconv  rel-pos moments, the PointConv node, the batched BatchNorm-1 prefold
+    interp     kNN interpolation: the inverse-squared-distance blend over a neighbour table and its transpose, the search in front of it
 
 Every op runs hand-written gfx950 kernels; torch supplies device memory, the stream and autograd.  The package namespace carries
 every name of the modules (``ops.point_conv``, ``ops.crf_meanfield``, ... and the private ones the tests reach for); switches that
 are flipped at run time live on ``ops.state``.
 """
-from . import _base, defer, crf, dense, mlp, rows, loss, pointconv      # noqa: F401  (this order: see the modules' last lines)
+from . import _base, defer, crf, dense, mlp, rows, loss, pointconv, interp      # noqa: F401  (this order: see the modules' last lines)
 from ..graph import NeighborTable      # noqa: F401
 
-for _m in (_base, defer, crf, dense, mlp, rows, loss, pointconv):
+for _m in (_base, defer, crf, dense, mlp, rows, loss, pointconv, interp):
     globals().update({_k: _v for _k, _v in vars(_m).items() if not _k.startswith('__')})
 del _m
 
 __all__ = ['linear', 'bn_act', 'crf_meanfield', 'gather_rows', 'neighbor_maxpool', 'relpos_moments', 'point_conv',
-           'point_conv_prefold', 'cross_entropy', 'training_loss', 'NeighborTable']
+           'point_conv_prefold', 'cross_entropy', 'training_loss', 'interpolate', 'knn_interpolate', 'NeighborTable']

@@ -196,11 +196,6 @@ int crfconv_meanfield_forward_block_rows(int64_t m, int H, int K, int k0, int T)
 int crfconv_meanfield_forward_block(const float* z, const float* y, const int32_t* idx32, const uint16_t* idx16,
                                     int n_tgt, int n_src, int K, int k0, int64_t m, int H, const float* Q,
                                     const float* P, int T, float* s, float* xs, void* ws, crf_stream_t stream);
-/* Diagnostic twin: 100 MHz phase stamps per workgroup in dbg [blocks][64] (u64), 640 rows per workgroup, uint16 tables
- * (scratch/mf_block_stamps.py; profiles/r6_block_stamps.md). */
-int crfconv_meanfield_forward_block_stamps(const float* z, const float* y, const int32_t* idx32, const uint16_t* idx16, int n_tgt, int n_src,
-                                           int64_t m, const float* Q, const float* P, int T, float* s, float* xs, void* ws, int shape,
-                                           unsigned long long* dbg, crf_stream_t stream);
 int crfconv_block_locality(const int32_t* idx32, int64_t m, int K, int k0, int rows, unsigned long long* count, crf_stream_t stream);
 
 /* One backward step, edge half:  given G = dL/dx_t and x_{t-1}:
@@ -264,6 +259,15 @@ int crfconv_wide_scatter(const float* src, const float* coef, const int32_t* rev
                          int64_t m_src, int H, const float* add, int similarity, float* out, crf_stream_t stream);
 int crfconv_wide_similarity_bwd(const float* ds, const float* s, const float* y, const int32_t* idx32, int K, int k0,
                                 int64_t m, int H, float* w, float* dy_self, crf_stream_t stream);
+
+/* Inverse-squared-distance blend of the table's rows (torch_geometric.nn.knn_interpolate) and its transpose (csrc/interp.hip).
+ * idx32 [n_y, K]: global rows of x, an entry < 0 or >= n_x = no neighbour; 1 <= K <= 64, any C >= 1, n_y K < 2^31.
+ * rev_ptr == NULL: src = x [n_x, C] -> out [n_y, C]; per row, slots in order: w = 1 / max(|pos_y[i] - pos_x[j]|^2, 1e-16), out = sum w x[j] / sum w;
+ *   coef [n_y, K] (may be NULL) receives w / den, 0 where no neighbour.  A row without any neighbour gives a zero row (not NaN).
+ * rev_ptr != NULL: src = g [n_y, C], coef is read -> out [n_x, C] = sum over rev(j) in stored order; pos_* unused.  No atomics. */
+int crfconv_interpolate(const float* src, const float* pos_x, const float* pos_y, const int32_t* idx32, int K,
+                        int64_t n_y, int64_t n_x, int C, float* coef, const int32_t* rev_ptr, const int32_t* rev_eid,
+                        float* out, crf_stream_t stream);
 
 /* Softmax + distance backward.  In: ds, s.  Out: w [m, K] = 2 * d(loss)/d(dist_ik) (must NOT
  * alias ds), dy_self[i] = sum_k w_ik (y_i - y_j). */
