@@ -89,20 +89,11 @@ __device__ __forceinline__ void narrow_sorted_row(const int64_t* __restrict__ id
             if (idx16 != nullptr) idx16[row * K + k] = (uint16_t)v[k];
         }
 }
-template <int KT>
-__global__ __launch_bounds__(256) void narrow_sorted_kernel(const int64_t* __restrict__ idx64, int64_t rows,
-                                                            int64_t rows_per_cloud, int K, int sort_from,
-                                                            int64_t n_src, int32_t* __restrict__ idx32,
-                                                            uint16_t* __restrict__ idx16, int32_t* __restrict__ bad) {
-    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (row >= rows) return;
-    narrow_sorted_row<KT>(idx64, row, rows_per_cloud, K, sort_from, n_src, idx32, idx16, bad);
-}
 
 // The same for SEVERAL tables in one launch (a batch refresh narrows every table of the batch: 13 for PointConvBig's five
 // levels, most of them a few thousand rows = one launch of ~5 us each).  A workgroup's 256 rows belong to one table, found by
 // a binary search over the chunk prefix; tables that keep their column order (K = 1 up-sampling tables, sort_from >= K - 1)
-// run the same body with nothing to exchange -- identical idx32 / idx16 / bad counts to the one-table entry points.
+// run the same body with nothing to exchange.
 constexpr int NB_MAX = 32;
 struct NarrowBatch {
     const int64_t* idx64[NB_MAX];
@@ -499,7 +490,8 @@ extern "C" int crfconv_copy_jobs(const crf_copy_job* jobs, int njobs, crf_stream
     return CRF_OK;
 }
 
-// The table narrowed with its columns left in place: what crfconv_index_narrow_sorted does when nothing is to be re-ordered.
+// The table narrowed with its columns left in place, one thread per entry: the form of a job wider than the register network
+// (K > 64) inside crfconv_index_narrow_batched.
 static int index_narrow(const int64_t* idx64, int64_t B, int64_t n_tgt, int K, int64_t n_src, int32_t* idx32, uint16_t* idx16,
                         int32_t* bad_count, crf_stream_t stream) {
     CRF_REQUIRE(idx64 && idx32 && bad_count, CRF_ERR_ARG, "null pointer");
@@ -515,32 +507,8 @@ static int index_narrow(const int64_t* idx64, int64_t B, int64_t n_tgt, int K, i
     return CRF_OK;
 }
 
-extern "C" int crfconv_index_narrow_sorted(const int64_t* idx64, int64_t B, int64_t n_tgt, int K,
-                                           int64_t n_src, int sort_from, int32_t* idx32, uint16_t* idx16,
-                                           int32_t* bad_count, crf_stream_t stream) {
-    CRF_REQUIRE(sort_from >= 0, CRF_ERR_ARG, "sort_from=%d < 0", sort_from);
-    if (sort_from >= K - 1 || K > 64)       // nothing to re-order (or wider than the register network)
-        return index_narrow(idx64, B, n_tgt, K, n_src, idx32, idx16, bad_count, stream);
-    CRF_REQUIRE(idx64 && idx32 && bad_count, CRF_ERR_ARG, "null pointer");
-    CRF_REQUIRE(idx16 == nullptr || n_src <= 65536, CRF_ERR_ARG, "uint16 table needs n_src <= 65536");
-    CRF_REQUIRE(B > 0 && n_tgt > 0 && K > 0 && n_src > 0, CRF_ERR_ARG, "empty table");
-    CRF_REQUIRE(B * n_src < ((int64_t)1 << 31) && B * n_tgt * K < ((int64_t)1 << 31), CRF_ERR_UNSUPPORTED,
-                "table too large for int32 rows / edge ids (B=%lld n_src=%lld n_tgt=%lld K=%d)",
-                (long long)B, (long long)n_src, (long long)n_tgt, K);
-    const int64_t rows = B * n_tgt;
-    const dim3 grid((unsigned)cdiv(rows, 256)), blk(256);
-    hipStream_t st = as_stream(stream);
-    if (K <= 16)
-        hipLaunchKernelGGL(narrow_sorted_kernel<16>, grid, blk, 0, st, idx64, rows, n_tgt, K, sort_from, n_src, idx32, idx16, bad_count);
-    else if (K <= 32)
-        hipLaunchKernelGGL(narrow_sorted_kernel<32>, grid, blk, 0, st, idx64, rows, n_tgt, K, sort_from, n_src, idx32, idx16, bad_count);
-    else
-        hipLaunchKernelGGL(narrow_sorted_kernel<64>, grid, blk, 0, st, idx64, rows, n_tgt, K, sort_from, n_src, idx32, idx16, bad_count);
-    CRF_LAUNCH_CHECK();
-    return CRF_OK;
-}
-
-// crfconv_index_narrow_sorted for up to 32 tables in ONE launch (jobs: host array).  K <= 64 for every job.
+// The narrowing of up to 32 tables in ONE launch (jobs: host array).  A job with K > 64 is wider than the register network: it
+// keeps its column order and runs index_narrow, a launch of its own.
 extern "C" int crfconv_index_narrow_batched(const crf_narrow_job* jobs, int njobs, crf_stream_t stream) {
     CRF_REQUIRE(jobs, CRF_ERR_ARG, "null pointer");
     CRF_REQUIRE(njobs >= 1 && njobs <= NB_MAX, CRF_ERR_ARG, "njobs=%d outside [1, %d]", njobs, NB_MAX);
@@ -553,14 +521,16 @@ extern "C" int crfconv_index_narrow_batched(const crf_narrow_job* jobs, int njob
             const crf_narrow_job& jb = jobs[j];
             CRF_REQUIRE(jb.idx64 && jb.idx32 && jb.bad_count, CRF_ERR_ARG, "job %d: null pointer", j);
             CRF_REQUIRE(jb.idx16 == nullptr || jb.n_src <= 65536, CRF_ERR_ARG, "job %d: uint16 table needs n_src <= 65536", j);
-            CRF_REQUIRE(jb.B > 0 && jb.n_tgt > 0 && jb.K > 0 && jb.K <= 64 && jb.n_src > 0 && jb.sort_from >= 0, CRF_ERR_ARG,
+            CRF_REQUIRE(jb.B > 0 && jb.n_tgt > 0 && jb.K > 0 && jb.n_src > 0 && jb.sort_from >= 0, CRF_ERR_ARG,
                         "job %d: bad shape (B=%lld n_tgt=%lld K=%d n_src=%lld sort_from=%d)", j, (long long)jb.B,
                         (long long)jb.n_tgt, jb.K, (long long)jb.n_src, jb.sort_from);
             CRF_REQUIRE(jb.B * jb.n_src < ((int64_t)1 << 31) && jb.B * jb.n_tgt * jb.K < ((int64_t)1 << 31), CRF_ERR_UNSUPPORTED,
                         "job %d: table too large for int32 rows / edge ids", j);
+            const bool wide = jb.K > 64;                 // no rows in the shared launch
             t.idx64[j] = jb.idx64; t.idx32[j] = jb.idx32; t.idx16[j] = jb.idx16; t.bad[j] = jb.bad_count;
-            t.rows[j] = (int)(jb.B * jb.n_tgt); t.rows_per_cloud[j] = (int)jb.n_tgt; t.K[j] = jb.K;
+            t.rows[j] = wide ? 0 : (int)(jb.B * jb.n_tgt); t.rows_per_cloud[j] = (int)jb.n_tgt; t.K[j] = wide ? 1 : jb.K;
             t.sort_from[j] = jb.sort_from; t.n_src[j] = (int)jb.n_src;
+            if (wide) continue;
             chunks += cdiv(jb.B * jb.n_tgt, 256);
             CRF_REQUIRE(chunks < ((int64_t)1 << 31), CRF_ERR_UNSUPPORTED, "batch too large");
             if (jb.K > kmax) kmax = jb.K;
@@ -570,6 +540,13 @@ extern "C" int crfconv_index_narrow_batched(const crf_narrow_job* jobs, int njob
         }
     }
     t.njobs = njobs;
+    for (int j = 0; j < njobs; ++j) {
+        const crf_narrow_job& jb = jobs[j];
+        if (jb.K <= 64) continue;
+        const int rc = index_narrow(jb.idx64, jb.B, jb.n_tgt, jb.K, jb.n_src, jb.idx32, jb.idx16, jb.bad_count, stream);
+        if (rc != CRF_OK) return rc;
+    }
+    if (chunks == 0) return CRF_OK;                      // wide jobs only
     const dim3 grid((unsigned)chunks), blk(256);
     hipStream_t st = as_stream(stream);
     if (kmax <= 16) hipLaunchKernelGGL(narrow_batched_kernel<16>, grid, blk, 0, st, t);

@@ -72,8 +72,7 @@ class NeighborTable:
                       if self.n_src <= 65536 and self.K % 8 == 0 else None)
         # columns 1.. re-ordered by ascending source id (every consumer reduces over a row's columns; column 0,
         # which the CRF layer drops by position, stays): adjacent target rows then gather adjacent source rows
-        _lib.call('crfconv_index_narrow_sorted', ptr(idx64), self.B, self.n_tgt, self.K, self.n_src, 1,
-                  ptr(self.idx32), ptr(self.idx16), ptr(self._bad), stream_ptr())
+        self._narrow(idx64)
         self._rev = None
         self._checked = False
         self.padded = False      # True: entries < 0 mean "no neighbour" (table_from_edges) -> generic kernels only
@@ -83,6 +82,12 @@ class NeighborTable:
             self._validate_later()
         elif check:
             self.validate()
+
+    def _narrow(self, idx64):
+        """idx64 into idx32 / idx16 / the bad count: one job of the batched narrowing (wider than 64 columns: column order kept)."""
+        job = _lib.NarrowJob(idx64.data_ptr(), self.B, self.n_tgt, self.K, self.n_src, 1, self.idx32.data_ptr(),
+                             None if self.idx16 is None else self.idx16.data_ptr(), self._bad.data_ptr())
+        _lib.call('crfconv_index_narrow_batched', (_lib.NarrowJob * 1)(job), 1, stream_ptr())
 
     def _validate_later(self):
         """The range check WITHOUT a host synchronisation: the bad-entry count travels to pinned memory behind the launch and
@@ -117,8 +122,7 @@ class NeighborTable:
             _BATCH['narrow'].append((self, idx64, check))
             check = False                      # ... which also validates, once the counts exist
         else:
-            _lib.call('crfconv_index_narrow_sorted', ptr(idx64), self.B, self.n_tgt, self.K, self.n_src, 1,
-                      ptr(self.idx32), ptr(self.idx16), ptr(self._bad), stream_ptr())
+            self._narrow(idx64)
         self._checked = False
         if self._rev is not None:
             self._build_reverse(*self._rev)
@@ -335,6 +339,90 @@ def table_from_edges(tgt, src, n_tgt, n_src, max_degree=64):
     tab = table_from_index(idx, n_src)
     tab.n_edges = E
     return tab
+
+
+_SELF_MODES = {'keep': 0, 'drop': 1, 'last': 2}
+
+
+def table_from_search(nbr, n_src, *, pos_src=None, pos_tgt=None, radius=None, self_loops='keep', max_degree=64):
+    """A search table finished into the padded NeighborTable `table_from_edges` builds from the corresponding edge list -- ONE launch
+    (csrc/graph_table.hip) and ONE host read (edge count and largest in-degree together), no edge list in between.
+
+    nbr: contiguous int32 [n_tgt, K] CUDA tensor of global source rows, 1 <= K <= 64; an entry outside [0, n_src) is "no neighbour"
+    wherever it sits (the table of the segmented kNN, or the idx32 of a finished table).  radius (with pos_src [n_src, 3] and pos_tgt
+    [n_tgt, 3], float32): keep an entry only if |pos_tgt[i] - pos_src[j]|^2 <= float32(radius * radius).  self_loops: 'keep' the
+    entries as they are, 'drop' those equal to the row's own index, or drop them and append the index 'last' (what
+    DepthwiseSeparablePointConv does to a symmetric graph); the last two need n_src == n_tgt.
+    The table: idx32 [n_tgt, largest in-degree] (the kernel's own output unless the degree is below its width: then one narrowing
+    copy), kept entries first in input order, -1 behind them; n_edges the real count; padded, B = 1.  Without any edge it is
+    [n_tgt, 1] of -1; a degree above `max_degree` raises CrfConvError."""
+    require_gpu(nbr, pos_src, pos_tgt)
+    if nbr.dim() != 2 or nbr.dtype != torch.int32 or not 1 <= nbr.shape[1] <= 64 or not nbr.is_contiguous():
+        raise ValueError('table_from_search needs a contiguous int32 [n_tgt, K] tensor, 1 <= K <= 64 (got %s %s)'
+                         % (tuple(nbr.shape), nbr.dtype))
+    if self_loops not in _SELF_MODES:
+        raise ValueError("self_loops must be 'keep', 'drop' or 'last' (got %r)" % (self_loops,))
+    mode = _SELF_MODES[self_loops]
+    n_tgt, K, n_src = int(nbr.shape[0]), int(nbr.shape[1]), int(n_src)
+    if mode and n_src != n_tgt:
+        raise ValueError("self_loops=%r needs n_src == n_tgt (got %d, %d)" % (self_loops, n_src, n_tgt))
+    r2 = -1.0
+    if radius is not None:
+        if pos_src is None or pos_tgt is None:
+            raise ValueError('a radius needs pos_src and pos_tgt')
+        for p, n in ((pos_src, n_src), (pos_tgt, n_tgt)):
+            if p.dtype != torch.float32 or tuple(p.shape) != (n, 3):
+                raise ValueError('positions must be float32 [n, 3] (got %s %s for n = %d)' % (tuple(p.shape), p.dtype, n))
+        pos_src, pos_tgt = pos_src.detach().contiguous(), pos_tgt.detach().contiguous()
+        r2 = float(torch.tensor(float(radius) * float(radius), dtype=torch.float32))      # what a float32 tensor is compared with
+    else:
+        pos_src = pos_tgt = None
+    dev = nbr.device
+    n_edges = kmax = 0
+    if n_tgt:
+        K_out = K + (mode == 2)
+        out = torch.empty((n_tgt, K_out), dtype=torch.int32, device=dev)
+        counts = torch.zeros(2, dtype=torch.int64, device=dev)
+        _lib.call('crfconv_graph_table', ptr(nbr), n_tgt, K, n_src, ptr(pos_src), ptr(pos_tgt), r2, mode, ptr(out), K_out, ptr(counts),
+                  stream_ptr())
+        n_edges, kmax = counts.tolist()
+    if n_edges == 0:
+        tab = table_from_index(torch.full((n_tgt, 1), -1, dtype=torch.int32, device=dev), n_src)
+        tab.n_edges = 0
+        return tab
+    if kmax > max_degree:
+        raise _lib.CrfConvError('in-degree %d exceeds the supported maximum %d' % (kmax, max_degree))
+    if kmax < K_out:
+        out = out[:, :kmax].contiguous()
+    tab = table_from_index(out, n_src)
+    tab.n_edges = n_edges
+    return tab
+
+
+def attach_table(edges, table, target_row):
+    """`table` rides on the edge tensor `edges` ([2, E]) as ``_crf_graph_table`` = (table, the tensor's version, the row of `edges`
+    that holds the targets): a consumer takes it instead of grouping the edges again (attached_table)."""
+    edges._crf_graph_table = (table, edges._version, int(target_row))
+    return edges
+
+
+def attached_table(edges, target_row):
+    """The finished table an edge-list builder left on `edges`, or None: when there is none, when the tensor was written since, when the
+    consumer's targets are the other row, or under ``ops.state.no_graph_tables``."""
+    from .ops._base import state
+    hit = getattr(edges, '_crf_graph_table', None)
+    if hit is None or state.no_graph_tables or hit[1] != edges._version or hit[2] != target_row:
+        return None
+    return hit[0]
+
+
+def self_last_table(table):
+    """The table of a symmetric graph with every row's self entry moved behind its other entries (added where there was none),
+    memoised on `table`: the two convolutions of a level share one table object, one reverse CSR and one set of rel-pos moments."""
+    hit = table.cache.get('self_last')
+    if hit is None:                        # (in a tuple: NeighborTable.refresh_ calls the refresh_ of what it finds in the cache)
+        hit = table.cache['self_last'] = (table_from_search(table.idx32, table.n_src, self_loops='last'),)
+    return hit[0]
 
 
 def table_of(idx, n_src):

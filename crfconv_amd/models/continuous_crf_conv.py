@@ -9,8 +9,19 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..graph import table_from_edges
+from ..graph import NeighborTable, attached_table, table_from_edges
 from . import graph_ops
+
+
+def _table(edge_index, target_row, n):
+    """The padded table of a graph given as a NeighborTable, as an edge tensor that carries its finished table, or as a plain edge
+    list ([2, E]; `target_row` holds the aggregating nodes), which is grouped by target here."""
+    table = edge_index if isinstance(edge_index, NeighborTable) else attached_table(edge_index, target_row)
+    if table is None:
+        return table_from_edges(edge_index[target_row], edge_index[1 - target_row], n, n)
+    if (table.m_tgt, table.m_src) != (n, n):
+        raise ValueError('the table has %d rows over %d sources, the layer %d points' % (table.m_tgt, table.m_src, n))
+    return table
 
 
 def _lin_bn(cin, cout, act=False):
@@ -26,6 +37,8 @@ def _identity_(param):
 
 
 class GuideGaussianCRFConv(nn.Module):
+    graph_tables = False         # True: the layer's own radius graph as a NeighborTable straight from the search, no edge list
+
     def __init__(self, in_n_channels, in_e_channels, out_channels=None, radius=0.1, kernel_size=32, steps=1):
         super().__init__()
         self.in_n_channels, self.in_e_channels = in_n_channels, in_e_channels
@@ -41,13 +54,13 @@ class GuideGaussianCRFConv(nn.Module):
 
     def forward(self, x, y, pos, batch, edge_index=None):
         """x [N, Cn] unary input, y [N, Ce] guidance, pos [N, 3], batch [N].  The graph is the radius graph of
-        `pos` (reference :53) unless `edge_index` ([2, E]: row 0 = source j, row 1 = target i) is supplied."""
+        `pos` (reference :53) unless `edge_index` ([2, E]: row 0 = source j, row 1 = target i; or a NeighborTable of the target rows)
+        is supplied."""
         if edge_index is None:
-            edge_index = graph_ops.radius_graph(pos, self.radius, batch, loop=False, max_num_neighbors=self.kernel_size)
-        src, tgt = edge_index[0], edge_index[1]
-        n = pos.shape[0]
+            build = graph_ops.radius_graph_table if self.graph_tables else graph_ops.radius_graph
+            edge_index = build(pos, self.radius, batch, loop=False, max_num_neighbors=self.kernel_size)
         field = ops.crf_meanfield(ops.run_lin_bn(self.unary, x), ops.run_lin_bn(self.pairwise, y), self.c,
-                                  table_from_edges(tgt, src, n, n), self.steps, k0=0)
+                                  _table(edge_index, 1, pos.shape[0]), self.steps, k0=0)
         return ops.leaky_relu(field, 0.01)                  # F.leaky_relu's default slope (reference :69)
 
 
@@ -69,9 +82,8 @@ class ContinuousGaussianCRFConv(nn.Module):
         _identity_(self.c)
 
     def forward(self, x, y, pos, edge_index):
-        """Node i = edge_index[0] aggregates from j = edge_index[1] (reference :114, 126)."""
-        n = pos.shape[0]
-        table = table_from_edges(edge_index[0], edge_index[1], n, n)
+        """Node i = edge_index[0] aggregates from j = edge_index[1] (reference :114, 126); or a NeighborTable of the nodes i."""
+        table = _table(edge_index, 0, pos.shape[0])
         field = ops.crf_meanfield(ops.run_lin_bn(self.unary_net, x), ops.run_lin_bn(self.pairwise_net, y), self.c, table,
                                   self.steps, k0=0)
         return ops.run_lin_bn(self.fusion_net, ops.cat2(ops.run_lin_bn(self.mlp, field), y))

@@ -5,10 +5,15 @@ knn_graph, knn, radius_graph, fps -- all on top of the exact HIP grid kNN (csrc/
 Conventions (PyG): an edge_index is [2, E] with row 0 = source j ("col"), row 1 = target i ("row").
 Third-party semantics are unpinned (no version, no tests in the reference): knn_* are exact; radius_graph keeps
 the NEAREST `max_num_neighbors` inside the radius (torch_cluster keeps the first it meets); fps starts from the
-first point of each cloud unless random_start=True."""
+first point of each cloud unless random_start=True.
+
+Every graph also exists as a finished neighbour table made from the search's own table by one launch (graph.table_from_search): the
+`*_table` builders return it without building an edge list, the edge-list builders carry it on the tensor they return
+(`_crf_graph_table`, graph.attached_table), and the sparse layers take either."""
 import torch
 
-from ..graph import table_from_index
+from ..graph import attach_table, table_from_index, table_from_search
+from ..ops._base import state
 from ..ops.interp import segment_ptr as _ptr
 from ..utils import nearest_neighbors as nn_
 
@@ -26,28 +31,75 @@ def _segments(batch, n):
     return out
 
 
-def _knn_table(x, y, k, batch_x, batch_y):
+def _knn_table(x, y, k, batch_x, batch_y, ptr_x=None, ptr_y=None):
     """int32 [Ny, k] global x rows: for every y row the k nearest x rows of the same cloud, nearest first, -1 where the cloud has fewer
-    than k -- ONE search for all clouds (csrc/knn.hip: crfconv_knn_segments_dev)."""
-    clouds = 1
-    if batch_x is not None or batch_y is not None:
-        if batch_x is None or batch_y is None:
-            raise ValueError('batch_x and batch_y must be given together')
-        clouds = int(torch.maximum(batch_x.max(), batch_y.max())) + 1 if batch_x.numel() and batch_y.numel() else 1
+    than k -- ONE search for all clouds (csrc/knn.hip: crfconv_knn_segments_dev).  ptr_x / ptr_y: device int64 [S + 1] row boundaries
+    of the S clouds in place of the batch vectors (no cloud count to read back)."""
+    if (ptr_x is None) != (ptr_y is None):
+        raise ValueError('ptr_x and ptr_y must be given together')
+    if ptr_x is None:
+        clouds = 1
+        if batch_x is not None or batch_y is not None:
+            if batch_x is None or batch_y is None:
+                raise ValueError('batch_x and batch_y must be given together')
+            clouds = int(torch.maximum(batch_x.max(), batch_y.max())) + 1 if batch_x.numel() and batch_y.numel() else 1
+        ptr_x, ptr_y = _ptr(batch_x, x.shape[0], clouds, x.device), _ptr(batch_y, y.shape[0], clouds, x.device)
+    elif batch_x is not None or batch_y is not None:
+        raise ValueError('give the batch vectors or the pointer arrays, not both')
     k = min(k, x.shape[0])              # no cloud has more points than that; the columns left out would be -1
-    return nn_.knn_segments_device(x, _ptr(batch_x, x.shape[0], clouds, x.device), y, _ptr(batch_y, y.shape[0], clouds, x.device), k,
-                                   out_dtype=torch.int32)
+    return nn_.knn_segments_device(x, ptr_x, y, ptr_y, k, out_dtype=torch.int32)
 
 
-def _knn_segments(x, y, k, batch_x, batch_y):
-    """For every y row the k nearest x rows of the same cloud -> (y_index, x_index) global ids, nearest first, cloud by cloud;
-    a cloud with fewer than k points gives each of its y rows as many edges as it has points."""
-    row, col, _ = _knn_edges(x, y, k, batch_x, batch_y)
-    return row, col
+def _finish(idx, n_src, **how):
+    """The search table `idx` as a finished NeighborTable (graph.table_from_search; a search without columns has no edge)."""
+    if idx.shape[1] == 0:
+        idx = torch.full((idx.shape[0], 1), -1, dtype=torch.int32, device=idx.device)
+    return table_from_search(idx, n_src, **how)
+
+
+def _radius_cut(pos, r):
+    pos = pos.detach().to(torch.float32).contiguous()
+    return dict(pos_src=pos, pos_tgt=pos, radius=r)
+
+
+def knn_table(x, y, k, batch_x=None, batch_y=None, *, ptr_x=None, ptr_y=None):
+    """The graph of `knn` as a NeighborTable of the y rows over the x rows: one search, one finishing launch, no edge list.  Equals
+    graph.table_from_edges(e[0], e[1], len(y), len(x)) of e = knn(x, y, k, batch_x, batch_y)."""
+    return _finish(_knn_table(x, y, k, batch_x, batch_y, ptr_x, ptr_y), x.shape[0])
+
+
+def radius_table(x, y, r, k, batch_x=None, batch_y=None, *, ptr_x=None, ptr_y=None):
+    """knn_table cut at the radius r: for every y row its nearest x rows of the same cloud inside r, at most k."""
+    idx = _knn_table(x, y, k, batch_x, batch_y, ptr_x, ptr_y)
+    return _finish(idx, x.shape[0], pos_src=x.detach().to(torch.float32).contiguous(), pos_tgt=y.detach().to(torch.float32).contiguous(),
+                   radius=r)
+
+
+def knn_graph_table(pos, k, batch=None, loop=False, *, ptr=None):
+    """The graph of `knn_graph` as a NeighborTable (targets = row 1 of its edge list): one search, one finishing launch."""
+    idx = _knn_table(pos, pos, k if loop else k + 1, batch, batch, ptr, ptr)
+    return _finish(idx, pos.shape[0], self_loops='keep' if loop else 'drop')
+
+
+def radius_graph_table(pos, r, batch=None, loop=False, max_num_neighbors=32, *, ptr=None):
+    """The graph of `radius_graph` as a NeighborTable (targets = row 1 of its edge list): one search, one finishing launch whose
+    radius cut forms the squared distance like the search does."""
+    idx = _knn_table(pos, pos, max_num_neighbors + (0 if loop else 1), batch, batch, ptr, ptr)
+    return _finish(idx, pos.shape[0], self_loops='keep' if loop else 'drop', **_radius_cut(pos, r))
+
+
+def _carry(edges, target_row, idx, n_src, **how):
+    """`edges` with the finished table of its graph attached -- unless ops.state.no_graph_tables, or the table's edge count is not the
+    list's (a distance within rounding of the radius that the framework's expression and the kernel's cut place on different sides)."""
+    if state.no_graph_tables:
+        return edges
+    table = _finish(idx, n_src, **how)
+    return attach_table(edges, table, target_row) if table.n_edges == edges.shape[1] else edges
 
 
 def _knn_edges(x, y, k, batch_x, batch_y):
-    """_knn_segments and the table the edges were read from."""
+    """For every y row the k nearest x rows of the same cloud -> (y_index, x_index) global ids, nearest first, cloud by cloud (a cloud
+    with fewer than k points gives each of its y rows as many edges as it has points), and the table the edges were read from."""
     idx = _knn_table(x, y, k, batch_x, batch_y)
     row, slot = (idx >= 0).nonzero(as_tuple=True)           # row-major order
     return row, idx[row, slot].long(), idx
@@ -72,31 +124,32 @@ def knn_dilated(x, y, k, dilation, batch_x=None, batch_y=None, generator=None):
 
 def knn(x, y, k, batch_x=None, batch_y=None):
     """torch_cluster.knn: [2, E] = [y index; x index].  The search's own int32 table ([Ny, k], -1 = no neighbour) rides on the returned
-    tensor as `_crf_knn_table` (a padded NeighborTable over the x rows): knn_interpolate blends over it without a second search."""
+    tensor as `_crf_knn_table` (a padded NeighborTable over the x rows): knn_interpolate blends over it without a second search.  The
+    finished table (knn_table) rides on it as well."""
     row, col, idx = _knn_edges(x, y, k, batch_x, batch_y)
     edges = torch.stack([row, col])
     edges._crf_knn_table = table_from_index(idx, x.shape[0])
-    return edges
+    return _carry(edges, 0, idx, x.shape[0])
 
 
 def knn_graph(pos, k, batch=None, loop=False):
     """torch_cluster.knn_graph (flow source_to_target): [2, E] = [neighbour j; node i]."""
-    row, col = _knn_segments(pos, pos, k if loop else k + 1, batch, batch)
+    row, col, idx = _knn_edges(pos, pos, k if loop else k + 1, batch, batch)
     if not loop:
         keep = row != col
         row, col = row[keep], col[keep]
-    return torch.stack([col, row])
+    return _carry(torch.stack([col, row]), 1, idx, pos.shape[0], self_loops='keep' if loop else 'drop')
 
 
 def radius_graph(pos, r, batch=None, loop=False, max_num_neighbors=32):
     """[2, E] = [neighbour j; node i] for |p_i - p_j| <= r, at most max_num_neighbors per node."""
     k = max_num_neighbors + (0 if loop else 1)
-    row, col = _knn_segments(pos, pos, k, batch, batch)
+    row, col, idx = _knn_edges(pos, pos, k, batch, batch)
     d2 = ((pos[row] - pos[col]) ** 2).sum(1)
     keep = d2 <= r * r
     if not loop:
         keep &= row != col
-    return torch.stack([col[keep], row[keep]])
+    return _carry(torch.stack([col[keep], row[keep]]), 1, idx, pos.shape[0], self_loops='keep' if loop else 'drop', **_radius_cut(pos, r))
 
 
 def fps(pos, batch=None, ratio=0.5, random_start=False):

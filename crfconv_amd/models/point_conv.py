@@ -7,7 +7,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
-from ..graph import table_from_edges
+from ..graph import NeighborTable, attach_table, attached_table, self_last_table, table_from_edges
 from . import graph_ops
 from .discrete_crf_conv import DiscreteCRFConv
 
@@ -27,19 +27,29 @@ class DepthwiseSeparablePointConv(nn.Module):
             self.mlp4 = nn.Sequential(nn.Linear(self.in_channels, self.out_channels), nn.BatchNorm1d(self.out_channels))
 
     def forward(self, x, pos, edge_index):
-        """edge_index = [col (source j); row (target i)].  Symmetric graphs (tensor `pos`) get their self loops
-        removed and re-added (point_conv.py:45-47); bipartite graphs take pos = (pos_src, pos_dst)."""
+        """edge_index = [col (source j); row (target i)], or the graph as a NeighborTable of the target rows.  Symmetric graphs (tensor
+        `pos`) get their self loops removed and re-added (point_conv.py:45-47); bipartite graphs take pos = (pos_src, pos_dst).
+        A table -- given, or riding on the edge tensor (graph.attached_table) -- is used as it is; its self-last form for a symmetric
+        graph is one more finishing launch, memoised on the table, so the layers of a level share it and its rel-pos moments."""
         bipartite = not torch.is_tensor(pos)
-        if not bipartite:
-            n = pos.shape[0]
-            keep = edge_index[0] != edge_index[1]
-            loops = torch.arange(n, dtype=edge_index.dtype, device=edge_index.device)
-            edge_index = torch.cat([edge_index[:, keep], torch.stack([loops, loops])], dim=1)
-            pos_src, pos_dst = pos, pos
+        pos_src, pos_dst = pos if bipartite else (pos, pos)
+        table = edge_index if isinstance(edge_index, NeighborTable) else attached_table(edge_index, 1)
+        moments = None
+        if table is not None:
+            if (table.m_tgt, table.m_src) != (pos_dst.shape[0], pos_src.shape[0]):
+                raise ValueError('the table has %d rows over %d sources, the positions %d and %d'
+                                 % (table.m_tgt, table.m_src, pos_dst.shape[0], pos_src.shape[0]))
+            if not bipartite:
+                table = self_last_table(table)
+            moments = self._moments(table, pos_src, pos_dst)
         else:
-            pos_src, pos_dst = pos
-        col, row = edge_index
-        table = table_from_edges(row, col, pos_dst.shape[0], pos_src.shape[0])
+            if not bipartite:
+                n = pos.shape[0]
+                keep = edge_index[0] != edge_index[1]
+                loops = torch.arange(n, dtype=edge_index.dtype, device=edge_index.device)
+                edge_index = torch.cat([edge_index[:, keep], torch.stack([loops, loops])], dim=1)
+            col, row = edge_index
+            table = table_from_edges(row, col, pos_dst.shape[0], pos_src.shape[0])
         residual = x
         if bipartite:
             residual = ops.neighbor_maxpool(residual, table)          # scatter_max(x[col], row)
@@ -47,38 +57,73 @@ class DepthwiseSeparablePointConv(nn.Module):
             residual = ops.run_lin_bn(self.mlp4, residual)
         h = ops.run_lin_bn(self.mlp2, x)
         msg = ops.point_conv(h, pos_src, pos_dst, table, self.mlp1[0].weight, self.mlp1[1], self.mlp1[3].weight,
-                             self.mlp1[4], self.training, slope=self.mlp1[2].negative_slope)
+                             self.mlp1[4], self.training, moments=moments, slope=self.mlp1[2].negative_slope)
         return ops.add_lrelu(ops.run_lin_bn(self.mlp3, msg), residual, 0.01)      # F.leaky_relu default slope
 
+    @staticmethod
+    def _moments(table, pos_src, pos_dst):
+        """The rel-pos moments of `table` over these positions, memoised on the table (the entry keeps the position tensors alive, so
+        an address names them; recomputed when they were written since)."""
+        ps, pt = ops._f32c(pos_src), ops._f32c(pos_dst)
+        key = ('moments', ps.data_ptr(), pt.data_ptr(), tuple(ps.shape), tuple(pt.shape))
+        entry = table.cache.get(key)
+        if entry is None or entry.stale():
+            entry = table.cache[key] = ops.MomentsEntry(ops.relpos_moments(ps, pt, table), ps, pt)
+        return entry
 
-def build_graph(pos, batch, method='radius', r=0.1, k=16, dilation=1, loop=True):
-    """models/point_conv.py:341-366."""
+
+def build_graph(pos, batch, method='radius', r=0.1, k=16, dilation=1, loop=True, as_table=False):
+    """models/point_conv.py:341-366.  as_table: the graph as a NeighborTable of the target rows instead of an edge list (no edge
+    list is built, except for the random dilation, whose picks are made on an edge list)."""
     assert method in ['radius', 'knn']
     if method == 'radius':
+        if as_table:
+            return graph_ops.radius_graph_table(pos, r, batch, loop=loop, max_num_neighbors=k)
         return graph_ops.radius_graph(pos, r, batch, loop=loop, max_num_neighbors=k)
     if dilation > 1:
         row, col = graph_ops.knn_dilated(pos, pos, k, dilation, batch, batch)
         if not loop:
             keep = row != col
             row, col = row[keep], col[keep]
-        return torch.stack([col, row])
+        return table_from_edges(row, col, pos.shape[0], pos.shape[0]) if as_table else torch.stack([col, row])
+    if as_table:
+        return graph_ops.knn_graph_table(pos, k, batch, loop=loop)
     return graph_ops.knn_graph(pos, k, batch, loop=loop)
 
 
-def build_bipartite_graph(pos, batch, ratio, method='radius', r=0.1, k=32, dilation=1):
-    """models/point_conv.py:368-396: fps-sampled targets, each gathering from the full cloud."""
+def build_bipartite_graph(pos, batch, ratio, method='radius', r=0.1, k=32, dilation=1, as_table=False):
+    """models/point_conv.py:368-396: fps-sampled targets, each gathering from the full cloud.  as_table: the graph as a
+    NeighborTable of the sampled rows over the full cloud instead of an edge list."""
     assert method in ['radius', 'knn']
     idx = graph_ops.fps(pos, batch, ratio=ratio)
     sub_pos, sub_batch = pos[idx], (batch[idx] if batch is not None else None)
-    if method == 'radius':
+    table = None
+    if method == 'radius' and (as_table or not ops.state.no_graph_tables):
+        # the search's table through the finishing kernel's radius cut (the squared distance formed as the search forms it)
+        table = graph_ops.radius_table(pos, sub_pos, r, k * dilation, batch, sub_batch)
+        if not as_table:
+            row, slot = (table.idx32 >= 0).nonzero(as_tuple=True)
+            col = table.idx32[row, slot].long()
+    elif method == 'radius':
         row, col = graph_ops.knn(pos, sub_pos, k * dilation, batch, sub_batch)
         keep = ((sub_pos[row] - pos[col]) ** 2).sum(1) <= r * r
         row, col = row[keep], col[keep]
     elif dilation > 1:
         row, col = graph_ops.knn_dilated(pos, sub_pos, k, dilation, batch, sub_batch)
+        if as_table:
+            table = table_from_edges(row, col, sub_pos.shape[0], pos.shape[0])
+    elif as_table:
+        table = graph_ops.knn_table(pos, sub_pos, k, batch, sub_batch)
     else:
-        row, col = graph_ops.knn(pos, sub_pos, k, batch, sub_batch)
-    return torch.stack([col, row], dim=0), sub_pos, sub_batch
+        edges = graph_ops.knn(pos, sub_pos, k, batch, sub_batch)
+        row, col = edges
+        table = attached_table(edges, 0)
+    if as_table:
+        return table, sub_pos, sub_batch
+    edges = torch.stack([col, row], dim=0)
+    if table is not None:
+        attach_table(edges, table, 1)
+    return edges, sub_pos, sub_batch
 
 
 # ---------------------------------------------------------------------------------------------------- networks
@@ -102,8 +147,18 @@ def _lin_bn_act(cin, cout):
     return nn.Sequential(nn.Linear(cin, cout), nn.BatchNorm1d(cout), nn.LeakyReLU(inplace=True))
 
 
+def use_graph_tables(net, on=True):
+    """Sets the `graph_tables` switch of every sparse encoder and CRF layer inside `net`: their graphs are then built as finished
+    neighbour tables (graph_ops.*_table) and no edge list exists in the forward.  Returns `net`."""
+    for mod in net.modules():
+        if hasattr(type(mod), 'graph_tables'):
+            mod.graph_tables = bool(on)
+    return net
+
+
 class _SparseEncoder(nn.Module):
     """conv{l}_1 / conv{l}_2 pairs over an fps pyramid (point_conv.py:84-98, 302-315, 197-264)."""
+    graph_tables = False         # True: the graphs as NeighborTables straight from the search (build_graph(as_table=True)), no edge lists
 
     def __init__(self, in_channels, method, ratio, radius, kernel_size, dilation):
         super().__init__()
@@ -116,24 +171,25 @@ class _SparseEncoder(nn.Module):
             setattr(self, 'conv%d_2' % lvl, DepthwiseSeparablePointConv(width, width))
             cin = width
 
-    def build_graph(self, pos, batch, method='radius', r=0.1, k=16, dilation=1, loop=True):
-        return build_graph(pos, batch, method=method, r=r, k=k, dilation=dilation, loop=loop)
+    def build_graph(self, pos, batch, method='radius', r=0.1, k=16, dilation=1, loop=True, **as_table):
+        return build_graph(pos, batch, method=method, r=r, k=k, dilation=dilation, loop=loop, **as_table)
 
-    def build_bipartite_graph(self, pos, batch, ratio, method='radius', r=0.1, k=32, dilation=1):
-        return build_bipartite_graph(pos, batch, ratio, method=method, r=r, k=k, dilation=dilation)
+    def build_bipartite_graph(self, pos, batch, ratio, method='radius', r=0.1, k=32, dilation=1, **as_table):
+        return build_bipartite_graph(pos, batch, ratio, method=method, r=r, k=k, dilation=dilation, **as_table)
 
     def encode(self, x, pos, batch):
         """-> per level (features, pos, batch), finest first."""
         levels = []
+        how = {'as_table': True} if self.graph_tables else {}
         for lvl in range(len(ENC_WIDTHS)):
             if lvl > 0:
                 ei, pos_c, batch_c = self.build_bipartite_graph(pos, batch, self.ratio[lvl - 1], method=self.method,
                                                                 r=self.radius[lvl - 1], k=self.kernel_size[lvl - 1],
-                                                                dilation=self.dilation[lvl - 1])
+                                                                dilation=self.dilation[lvl - 1], **how)
                 x = getattr(self, 'conv%d_1' % (lvl + 1))(x, (pos, pos_c), ei)
                 pos, batch = pos_c, batch_c
             ei = self.build_graph(pos, batch, method=self.method, r=self.radius[lvl], k=self.kernel_size[lvl],
-                                  dilation=self.dilation[lvl])
+                                  dilation=self.dilation[lvl], **how)
             if lvl == 0:
                 x = self.conv1_1(x, pos, ei)
             x = getattr(self, 'conv%d_2' % (lvl + 1))(x, pos, ei)

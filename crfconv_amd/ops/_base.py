@@ -171,6 +171,9 @@ class _State:
     no_join = False              # tests: True = lin_out, bn_apply and add_lrelu as separate nodes (the fused nodes must give the same results)
     no_fork = False              # tests: True = autograd's own accumulation pass instead of the fork chain
     no_prefold = False           # tests: True = one fold launch inside every PointConv layer
+    # tests: True = the sparse layers group every edge list again (graph.table_from_edges) and the edge-list builders attach no finished
+    # table (graph.table_from_search): the path the tables must reproduce bit for bit
+    no_graph_tables = False
     # the LeakyReLU mask of a ResNet join's backward applied by the kernel that writes the join's gradient (ops.mlp.JoinMask);
     # CRFCONV_NO_MASK_FOLD=1: every join runs its own mask pass again (A/B runs of bench.py)
     no_mask_fold = __import__('os').environ.get('CRFCONV_NO_MASK_FOLD') is not None

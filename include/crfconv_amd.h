@@ -14,7 +14,7 @@
  *        PointConv        <- models/point_conv_big.py:37-58
  *        neighbour max-pool / nearest up-sampling <- models/point_conv_big.py:74-77, 97-101
  *      All tensors are dense row-major fp32; neighbour tables are int32 GLOBAL row ids
- *      (cloud b, local id j  ->  b * n_src + j) produced once per batch by crfconv_index_narrow_sorted.
+ *      (cloud b, local id j  ->  b * n_src + j) produced once per batch by crfconv_index_narrow_batched.
  *
  * Every function returns CRF_OK (0) or a negative error code; crfconv_last_error() gives the
  * message (thread-local).  Device entry points only enqueue work on `stream`; they never
@@ -129,9 +129,23 @@ int64_t crfconv_grid_subsample(const float* points, int64_t N, const float* feat
  * Columns sort_from .. K-1 of every row are re-ordered by ascending source id (sort_from = 1 keeps the
  * self column of a self-query kNN table in place; sort_from >= K - 1 leaves every column where it is).  Consumers reduce over the
  * columns of a row, so the order is free; ascending ids make the k-th gathers of adjacent target rows hit adjacent source rows. */
-int crfconv_index_narrow_sorted(const int64_t* idx64, int64_t B, int64_t n_tgt, int K, int64_t n_src,
-                                int sort_from, int32_t* idx32, uint16_t* idx16, int32_t* bad_count,
-                                crf_stream_t stream);
+typedef struct { const int64_t* idx64; int64_t B; int64_t n_tgt; int K; int64_t n_src; int sort_from; int32_t* idx32;
+                 uint16_t* idx16; int32_t* bad_count; } crf_narrow_job;
+/* Up to 32 tables in ONE launch (a batch refresh narrows every table of the batch; a single table is a batch of one job).  jobs is a
+ * host array.  A job with K > 64 keeps its column order (plain narrowing, in a launch of its own). */
+int crfconv_index_narrow_batched(const crf_narrow_job* jobs, int njobs, crf_stream_t stream);
+
+/* A search table finished into the padded table the sparse layers consume, ONE launch, no workspace.  nbr [n_tgt, K], 1 <= K <= 64:
+ * global source rows; an entry outside [0, n_src) is "no neighbour" wherever it sits in its row (the table of crfconv_knn_segments_dev,
+ * or an already finished table).  r2 >= 0: an entry is kept only if d2 <= r2, d = pos_tgt[i] - pos_src[j], d2 the float32 squared
+ * distance accumulated x, y, z with one rounding per operation (the form of the kNN); r2 < 0: no cut, the positions may be NULL.
+ * self_mode 0 keeps entries as they are, 1 drops the entries equal to the row's own index i, 2 drops them and appends i after the
+ * kept entries (1 and 2 need n_src == n_tgt).  out [n_tgt, K_out], K_out = K + (self_mode == 2): the kept entries in input order, the
+ * appended self, then -1.  counts (device int64 [2], the caller zeroes them): counts[0] += entries written, counts[1] =
+ * max(counts[1], largest row degree) -- integer atomics, one pair per workgroup.  n_tgt == 0 returns CRF_OK without a launch;
+ * n_tgt * K_out < 2^31. */
+int crfconv_graph_table(const int32_t* nbr, int64_t n_tgt, int K, int64_t n_src, const float* pos_src, const float* pos_tgt,
+                        float r2, int self_mode, int32_t* out, int K_out, int64_t* counts, crf_stream_t stream);
 
 /* 30-bit Morton (Z-order) codes of B clouds of npts points (pts [B, npts, 3]): ten bits per axis of
  * clamp((p - lo) / ext * 1023, 0, 1023), lo = the cloud's per-axis minimum, ext = its largest extent.  The device collate sorts
@@ -150,11 +164,6 @@ size_t crfconv_reverse_csr_workspace(int64_t E, int64_t m_src);
 int crfconv_reverse_csr(const int32_t* idx32, int64_t E, int64_t m_src, int32_t* rev_ptr,
                         int32_t* rev_eid, void* workspace, size_t workspace_bytes,
                         crf_stream_t stream);
-/* crfconv_index_narrow_sorted for up to 32 tables in ONE launch (a batch refresh narrows every table of the batch); same idx32 /
- * idx16 / bad counts as the one-table entry point, K <= 64.  jobs is a host array. */
-typedef struct { const int64_t* idx64; int64_t B; int64_t n_tgt; int K; int64_t n_src; int sort_from; int32_t* idx32;
-                 uint16_t* idx16; int32_t* bad_count; } crf_narrow_job;
-int crfconv_index_narrow_batched(const crf_narrow_job* jobs, int njobs, crf_stream_t stream);
 /* The same for up to 32 tables in ONE set of five launches (a batch refresh rebuilds every table's reverse CSR: 14 tables =
  * ~100 launches one by one): identical rev_ptr / rev_eid contents.  jobs is a host array. */
 typedef struct { const int32_t* idx32; int64_t E; int64_t m_src; int32_t* rev_ptr; int32_t* rev_eid; } crf_rev_job;
