@@ -217,7 +217,7 @@ def up_index_from_table(pos, neighbor_idx, choice, rank=None, sub_pos=None):
 
 def _fps_choice(pos, n_sample):
     """[B, n_sample] per-cloud farthest-point picks in pick order, first pick = point 0 -- what the reference's
-    ``tpcuda.furthest_point_sampling(pos, n)`` returns (datasets/semantic3d_dataset.py:520) -- on csrc/collate.hip: fps_kernel
+    ``tpcuda.furthest_point_sampling(pos, n)`` returns (datasets/semantic3d_dataset.py:520) -- on csrc/fps.hip: fps_kernel
     (one workgroup per cloud; ties -> lower index)."""
     from . import _lib
     from .graph import ptr, stream_ptr

@@ -152,26 +152,72 @@ def radius_graph(pos, r, batch=None, loop=False, max_num_neighbors=32):
     return _carry(torch.stack([col[keep], row[keep]]), 1, idx, pos.shape[0], self_loops='keep' if loop else 'drop', **_radius_cut(pos, r))
 
 
-def fps(pos, batch=None, ratio=0.5, random_start=False):
-    """Farthest point sampling per cloud -> sorted global indices (torch_cluster.fps).  One HIP workgroup per cloud
-    (csrc/collate.hip: fps_kernel); the number of picks is ceil(ratio * n) per cloud."""
-    import math
+def pick_counts(n, ratio):
+    """Picks per cloud of n points (int64 tensor, any device): a float ratio gives 0 for an empty cloud, else max(1, ceil(ratio * n)) --
+    the product formed in float64, so that it is Python's math.ceil(ratio * n) -- and an int ratio min(ratio, n); never more than n."""
+    if isinstance(ratio, float):
+        want = torch.ceil(n.to(torch.float64) * ratio).to(torch.int64).clamp_(min=1)
+    else:
+        want = torch.full_like(n, int(ratio))
+    return torch.minimum(want, n).clamp_(min=0)
 
+
+def fps_segments(pos, ptr, ratio, *, first=None, n_out=None, sort=True):
+    """Farthest point sampling of S clouds given by their row boundaries `ptr` (device int64 [S + 1], as knn_segments_device takes them)
+    -> (idx, ptr_out): global rows of the picks, cloud after cloud, and their boundaries [S + 1] (the exclusive scan of pick_counts).
+    first: device int64 [S], each cloud's first pick as a row of the cloud (None: row 0).  sort: each cloud's picks ascending, as `fps`
+    returns them; sort=False leaves them in pick order.  ONE launch, one workgroup per cloud (csrc/fps.hip); an empty cloud gets no pick.
+    The only host read is the total pick count; with n_out (the caller's promise of that total) there is none and the call can be
+    captured and replayed over other positions and other splits with the same total.  Should the promise not hold, picks past n_out
+    are dropped, and entries past the real total hold pos.shape[0] (one past the last row)."""
     from .. import _lib
-    from ..graph import ptr, stream_ptr
-    segs = _segments(batch, pos.shape[0])
-    dev = pos.device
-    counts = [e - s for s, e in segs]
-    picks = [max(1, int(math.ceil(ratio * n))) if isinstance(ratio, float) else min(int(ratio), n) for n in counts]
-    starts = torch.tensor([s for s, _ in segs], dtype=torch.int64, device=dev)
-    cnt = torch.tensor(counts, dtype=torch.int64, device=dev)
-    npick = torch.tensor(picks, dtype=torch.int64, device=dev)
-    ostart = torch.cumsum(npick, 0) - npick
-    first = (torch.stack([torch.randint(0, n, (1,)) for n in counts]).reshape(-1).to(dev) if random_start
-             else torch.zeros(len(segs), dtype=torch.int64, device=dev))
-    p = pos.detach().to(torch.float32).contiguous()
-    out = torch.empty(sum(picks), dtype=torch.int64, device=dev)
-    ws = torch.empty(pos.shape[0], dtype=torch.float32, device=dev)
-    _lib.call('crfconv_fps', ptr(p), len(segs), ptr(starts), ptr(cnt), ptr(ostart), ptr(npick), ptr(first), ptr(ws),
-              ptr(out), stream_ptr())
-    return out.sort().values            # picks are global rows and clouds are contiguous: one sort orders every cloud's picks
+    from ..graph import ptr as dptr, stream_ptr
+    dev, N, S = pos.device, pos.shape[0], ptr.numel() - 1
+    n = ptr[1:] - ptr[:-1]
+    ptr_out = torch.zeros(S + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(pick_counts(n, ratio), 0, out=ptr_out[1:])
+    if n_out is None:
+        total = int(ptr_out[-1]) if S else 0
+        out = torch.empty(total, dtype=torch.int64, device=dev)
+    else:
+        total = int(n_out)
+        ptr_out.clamp_(max=total)                             # no pick is written past the end of `out`, whatever the promise
+        out = torch.full((total,), N, dtype=torch.int64, device=dev)
+    if S and total:
+        npick = ptr_out[1:] - ptr_out[:-1]
+        starts, ostart = ptr[:-1].contiguous(), ptr_out[:-1].contiguous()
+        first = torch.zeros(S, dtype=torch.int64, device=dev) if first is None else first.to(torch.int64).contiguous()
+        p = pos.detach().to(torch.float32).contiguous()
+        ws = torch.empty(max(N, 1), dtype=torch.float32, device=dev)      # the running distances of a cloud above 65 536 points
+        _lib.call('crfconv_fps', dptr(p), S, dptr(starts), dptr(n.contiguous()), dptr(ostart), dptr(npick.contiguous()), dptr(first),
+                  dptr(ws), dptr(out), stream_ptr())
+    if not sort or not total:
+        return out, ptr_out
+    if n_out is None:
+        return out.sort().values, ptr_out           # picks are global rows and clouds are contiguous: one sort orders every cloud's picks
+    # the same order without torch.sort (not known to replay from a captured graph): count the picks of every row, scan, and entry j is
+    # the first row whose running count is above j -- a row picked twice (duplicate points) appears twice, as in the sort
+    count = torch.zeros(N + 1, dtype=torch.int64, device=dev).index_add_(0, out, torch.ones_like(out))
+    return torch.searchsorted(torch.cumsum(count, 0), torch.arange(total, dtype=torch.int64, device=dev), right=True), ptr_out
+
+
+def random_first(ptr, generator=None):
+    """A uniformly drawn row of every cloud, int64 [S] on ptr's device, in one device op: floor(rand * n), clamped into the cloud
+    (0 for an empty one).  generator: a generator of that device."""
+    n = ptr[1:] - ptr[:-1]
+    u = torch.rand(n.numel(), dtype=torch.float64, device=ptr.device, generator=generator)
+    return torch.minimum(torch.floor(u * n).to(torch.int64), n - 1).clamp_(min=0)
+
+
+def fps(pos, batch=None, ratio=0.5, random_start=False, *, ptr=None, n_out=None, generator=None):
+    """Farthest point sampling per cloud -> sorted global indices (torch_cluster.fps).  One HIP workgroup per cloud
+    (csrc/fps.hip); the number of picks is ceil(ratio * n) per cloud.  The clouds are given by the sorted `batch` vector (its cloud count
+    is one host read), by ptr (device int64 [S + 1] row boundaries) or are one cloud; n_out as in fps_segments.  random_start draws
+    every cloud's first row in one device op, floor(rand * n), from `generator` (a device generator) if given."""
+    if ptr is None:
+        clouds = int(batch.max()) + 1 if batch is not None and batch.numel() else 1
+        ptr = _ptr(batch, pos.shape[0], clouds, pos.device)
+    elif batch is not None:
+        raise ValueError('give the batch vector or the pointer array, not both')
+    first = random_first(ptr, generator) if random_start else None
+    return fps_segments(pos, ptr, ratio, first=first, n_out=n_out)[0]

@@ -91,10 +91,20 @@ def build_graph(pos, batch, method='radius', r=0.1, k=16, dilation=1, loop=True,
     return graph_ops.knn_graph(pos, k, batch, loop=loop)
 
 
-def build_bipartite_graph(pos, batch, ratio, method='radius', r=0.1, k=32, dilation=1, as_table=False):
+def build_bipartite_graph(pos, batch, ratio, method='radius', r=0.1, k=32, dilation=1, as_table=False, ptr=None, n_out=None):
     """models/point_conv.py:368-396: fps-sampled targets, each gathering from the full cloud.  as_table: the graph as a
-    NeighborTable of the sampled rows over the full cloud instead of an edge list."""
+    NeighborTable of the sampled rows over the full cloud instead of an edge list.  ptr (device int64 [S + 1] row boundaries of the clouds,
+    in place of `batch`; as_table only): -> (table, sub_pos, sub_ptr) through graph_ops.fps_segments and the ptr forms of the table
+    builders.  Its only host reads are the total pick count -- none with n_out, the caller's promise of it -- and the finishing launch's."""
     assert method in ['radius', 'knn']
+    if ptr is not None:
+        if batch is not None or not as_table or dilation > 1:
+            raise ValueError('ptr= stands in place of batch, for as_table=True and dilation 1')
+        idx, sub_ptr = graph_ops.fps_segments(pos, ptr, ratio, n_out=n_out)
+        sub_pos = pos[idx]
+        if method == 'radius':
+            return graph_ops.radius_table(pos, sub_pos, r, k, ptr_x=ptr, ptr_y=sub_ptr), sub_pos, sub_ptr
+        return graph_ops.knn_table(pos, sub_pos, k, ptr_x=ptr, ptr_y=sub_ptr), sub_pos, sub_ptr
     idx = graph_ops.fps(pos, batch, ratio=ratio)
     sub_pos, sub_batch = pos[idx], (batch[idx] if batch is not None else None)
     table = None

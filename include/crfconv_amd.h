@@ -106,7 +106,11 @@ int crfconv_knn_segments_dev(const float* pts, const int64_t* pts_ptr, const flo
 /* Farthest point sampling per cloud (torch_cluster.fps as called at models/point_conv.py:381).  All descriptor arrays
  * are device int64 [n_clouds]: seg_start / seg_count = the cloud's rows in pos [N, 3]; n_sample = picks per cloud
  * (<= seg_count); first = local index of the first pick; out_start = offset of the cloud's picks in out.  Picks are
- * GLOBAL row ids in selection order; ties in the arg-max go to the lower index.  dist_ws: float [N] scratch. */
+ * GLOBAL row ids in selection order; ties in the arg-max go to the lower index.  dist_ws: float [N] scratch.
+ * csrc/fps.hip: one workgroup per cloud, which branches on its cloud's size (a device value): up to 16 384 points x, y, z and the
+ * running minimum distances stay in registers for all picks, up to 65 536 the distances do, larger clouds use dist_ws.  One
+ * distance function for all sizes, so the picks do not depend on the form.  On the device n_sample is clamped to [0, seg_count] and
+ * first to [0, seg_count); an empty cloud or no pick writes nothing. */
 int crfconv_fps(const float* pos, int n_clouds, const int64_t* seg_start, const int64_t* seg_count,
                 const int64_t* out_start, const int64_t* n_sample, const int64_t* first, float* dist_ws,
                 int64_t* out, crf_stream_t stream);
