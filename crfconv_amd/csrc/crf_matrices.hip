@@ -72,12 +72,6 @@ __global__ __launch_bounds__(256) void spd_inverse_kernel(const float* __restric
         }
 }
 
-__global__ __launch_bounds__(CMF_BLOCK) void crf_matrices_kernel(const float* __restrict__ cmat, int H,
-                                                           float* __restrict__ Qout, float* __restrict__ Pout) {
-    __shared__ __attribute__((aligned(16))) char lds[CMF_LDS_BYTES];
-    crf_matrices_body(cmat, H, Qout, Pout, lds);
-}
-
 // All CRF layers of a network in ONE launch (one workgroup each; CrfMatJobs: crf_matrices_body.hpp)
 __global__ __launch_bounds__(CMF_BLOCK) void crf_matrices_batched_kernel(const CrfMatJobs j) {
     const int b = blockIdx.x;
@@ -165,14 +159,6 @@ extern "C" int crfconv_spd_inverse(const float* M, int H, float* Q, crf_stream_t
     CRF_REQUIRE(M && Q, CRF_ERR_ARG, "null pointer");
     CRF_REQUIRE(H >= 1 && H <= 64, CRF_ERR_UNSUPPORTED, "H=%d outside [1, 64]", H);
     hipLaunchKernelGGL(crf::spd_inverse_kernel, dim3(1), dim3(256), 0, crf::as_stream(stream), M, H, Q);
-    CRF_LAUNCH_CHECK();
-    return CRF_OK;
-}
-
-extern "C" int crfconv_crf_matrices(const float* c, int H, float* Q, float* P, crf_stream_t stream) {
-    CRF_REQUIRE(c && Q && P, CRF_ERR_ARG, "null pointer");
-    CRF_REQUIRE(H >= 1 && H <= 64, CRF_ERR_UNSUPPORTED, "H=%d outside [1, 64]", H);
-    hipLaunchKernelGGL(crf::crf_matrices_kernel, dim3(1), dim3(crf::CMF_BLOCK), 0, crf::as_stream(stream), c, H, Q, P);
     CRF_LAUNCH_CHECK();
     return CRF_OK;
 }

@@ -1,5 +1,5 @@
 // The forward of the CRF layers' two loop-invariant matrices as a device function over caller-provided LDS, so that its workgroups can
-// run as a launch of their own (crf_matrices.hip: crf_matrices_kernel / crf_matrices_batched_kernel) or ride along in a long launch whose
+// run as a launch of their own (crf_matrices.hip: crf_matrices_batched_kernel, one layer being a batch of one) or ride along in a long launch whose
 // inputs do not depend on them (pointconv.hip: the first PointConv's statistics pass, crfconv_pointconv_uvstats_hosting).  The same for
 // the backward: crf_matrices_bwd_slab and its job table (crf_matrices_bwd_jobs) serve crf_matrices.hip's own launches and the
 // end-of-pass dW launch that carries the slabs (mlp_bwd.hip: mlp_dw_jobs_hosting_kernel).

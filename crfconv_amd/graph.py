@@ -399,6 +399,57 @@ def table_from_search(nbr, n_src, *, pos_src=None, pos_tgt=None, radius=None, se
     return tab
 
 
+def table_from_search_dilated(nbr, n_src, k, *, seed, counter, salt, self_loops='keep', max_degree=64, read_counts=True):
+    """The reference's random dilation (models/point_conv.py:356-364, 385-393) drawn on the search table `nbr` and finished into a padded
+    NeighborTable -- ONE launch (csrc/graph_table.hip: crfconv_graph_table_dilated) and ONE host read, like `table_from_search`.
+
+    nbr: contiguous int32 [n_tgt, K] CUDA tensor of global source rows (the search of k * dilation neighbours), 1 <= K <= 64; entries
+    outside [0, n_src) are "no neighbour".  Every row keeps min(k, its valid entries) picks, drawn with replacement from its valid
+    entries (duplicates stay) by a counter-based hash of (seed, counter, salt, row, pick): seed a Python int (its low 64 bits), counter a
+    device int64 tensor of one word that only the kernel reads -- advance it between the replays of a captured call for fresh draws --,
+    salt >= 0 an int that tells the graphs of one forward apart.  The row is the GLOBAL row: a ragged batch does not draw what its
+    clouds would draw alone.  self_loops as in `table_from_search`, applied to the picks ('last': k + 1 <= 64 columns).
+    The table: idx32 [n_tgt, largest in-degree], kept picks in pick order, -1 behind them; n_edges the real count; padded, B = 1; without
+    any edge [n_tgt, 1] of -1.  read_counts=False makes no host read (a captured call): -> (table, counts) with the table at its full
+    width k (+ 1), n_edges the number of its slots, and counts the device int64 [2] = (edges, largest in-degree)."""
+    require_gpu(nbr, counter)
+    if nbr.dim() != 2 or nbr.dtype != torch.int32 or not 1 <= nbr.shape[1] <= 64 or not nbr.is_contiguous():
+        raise ValueError('table_from_search_dilated needs a contiguous int32 [n_tgt, K] tensor, 1 <= K <= 64 (got %s %s)'
+                         % (tuple(nbr.shape), nbr.dtype))
+    if self_loops not in _SELF_MODES:
+        raise ValueError("self_loops must be 'keep', 'drop' or 'last' (got %r)" % (self_loops,))
+    if counter.dtype != torch.int64 or counter.numel() != 1:
+        raise ValueError('counter must be one int64 word on the device (got %s %s)' % (tuple(counter.shape), counter.dtype))
+    mode = _SELF_MODES[self_loops]
+    n_tgt, K, n_src, k, salt = int(nbr.shape[0]), int(nbr.shape[1]), int(n_src), int(k), int(salt)
+    K_out = k + (mode == 2)
+    if k < 1 or K_out > 64:
+        raise ValueError('k = %d picks (%d columns) outside [1, 64]' % (k, K_out))
+    if mode and n_src != n_tgt:
+        raise ValueError("self_loops=%r needs n_src == n_tgt (got %d, %d)" % (self_loops, n_src, n_tgt))
+    if salt < 0:
+        raise ValueError('salt must not be negative (got %d)' % salt)
+    dev = nbr.device
+    out = torch.empty((n_tgt, K_out), dtype=torch.int32, device=dev)
+    counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    _lib.call('crfconv_graph_table_dilated', ptr(nbr), n_tgt, K, n_src, k, int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(counter), salt, mode,
+              ptr(out), K_out, ptr(counts), stream_ptr())
+    if not read_counts:
+        return table_from_index(out, n_src), counts
+    n_edges, kmax = counts.tolist() if n_tgt else (0, 0)
+    if n_edges == 0:
+        tab = table_from_index(torch.full((n_tgt, 1), -1, dtype=torch.int32, device=dev), n_src)
+        tab.n_edges = 0
+        return tab
+    if kmax > max_degree:
+        raise _lib.CrfConvError('in-degree %d exceeds the supported maximum %d' % (kmax, max_degree))
+    if kmax < K_out:
+        out = out[:, :kmax].contiguous()
+    tab = table_from_index(out, n_src)
+    tab.n_edges = n_edges
+    return tab
+
+
 def attach_table(edges, table, target_row):
     """`table` rides on the edge tensor `edges` ([2, E]) as ``_crf_graph_table`` = (table, the tensor's version, the row of `edges`
     that holds the targets): a consumer takes it instead of grouping the edges again (attached_table)."""

@@ -9,10 +9,11 @@ first point of each cloud unless random_start=True.
 
 Every graph also exists as a finished neighbour table made from the search's own table by one launch (graph.table_from_search): the
 `*_table` builders return it without building an edge list, the edge-list builders carry it on the tensor they return
-(`_crf_graph_table`, graph.attached_table), and the sparse layers take either."""
+(`_crf_graph_table`, graph.attached_table), and the sparse layers take either.  The random dilation has two builders: knn_dilated
+(torch.randint on an edge list, cloud by cloud) and knn_dilated_table (drawn by the finishing launch, keyed by a DilationDraw)."""
 import torch
 
-from ..graph import attach_table, table_from_index, table_from_search
+from ..graph import attach_table, table_from_index, table_from_search, table_from_search_dilated
 from ..ops._base import state
 from ..ops.interp import segment_ptr as _ptr
 from ..utils import nearest_neighbors as nn_
@@ -120,6 +121,46 @@ def knn_dilated(x, y, k, dilation, batch_x=None, batch_y=None, generator=None):
         rows.append(torch.arange(ys, ye, device=x.device).unsqueeze(1).expand(-1, keep).reshape(-1))
         cols.append(idx[ys:ye].gather(1, pick).reshape(-1).long())
     return torch.cat(rows), torch.cat(cols)
+
+
+class DilationDraw:
+    """The key of the device-side dilation draws (knn_dilated_table): a seed, ONE int64 counter word on the device that only the
+    kernels read, and a host count of the salts handed out.  Every graph takes the next salt(), so the graphs of a forward draw
+    apart; step() advances the device word by a device op -- between forwards, or between the replays of a captured forward, whose
+    recorded launches then draw afresh.  Two objects of the same seed that see the same sequence of calls give the same graphs."""
+
+    def __init__(self, seed, device):
+        self.seed = int(seed)
+        self.counter = torch.zeros(1, dtype=torch.int64, device=device)
+        self._salts = 0
+
+    def salt(self):
+        """The next salt; never repeats within this object."""
+        s = self._salts
+        self._salts += 1
+        return s
+
+    def step(self):
+        self.counter.add_(1)
+        return self
+
+
+def knn_dilated_table(x, y, k, dilation, batch_x=None, batch_y=None, *, draw, ptr_x=None, ptr_y=None, self_loops='keep', read_counts=True):
+    """The graph of `knn_dilated` as a NeighborTable of the y rows over the x rows, drawn on the device: ONE search of
+    min(k * dilation, len(x)) columns and one finishing launch (graph.table_from_search_dilated) that keeps k entries per row, drawn with
+    replacement from the row's neighbours -- a row whose cloud has fewer than k points keeps as many picks as the cloud has points.  No
+    edge list, no loop over the clouds; with ptr_x / ptr_y (as in `knn_table`) the only host read is the finishing launch's.
+    draw: a DilationDraw; the call takes its next salt.  The draws are keyed by the global row, so a batch does not draw what its clouds
+    would draw alone, and they are not torch.randint's: `knn_dilated` stays the builder that follows a torch generator.
+    self_loops ('keep' / 'drop' / 'last') is applied to the picks, as the reference applies loop=False after its draw.
+    read_counts=False: no host read at all -> (full-width table, device counts), for a captured call (graph.table_from_search_dilated)."""
+    if k * dilation > 64:
+        raise ValueError('k * dilation = %d exceeds the 64 columns of a search' % (k * dilation))
+    idx = _knn_table(x, y, k * dilation, batch_x, batch_y, ptr_x, ptr_y)
+    if idx.shape[1] == 0:
+        idx = torch.full((idx.shape[0], 1), -1, dtype=torch.int32, device=idx.device)
+    return table_from_search_dilated(idx, x.shape[0], k, seed=draw.seed, counter=draw.counter, salt=draw.salt(), self_loops=self_loops,
+                                     read_counts=read_counts)
 
 
 def knn(x, y, k, batch_x=None, batch_y=None):

@@ -72,10 +72,20 @@ class DepthwiseSeparablePointConv(nn.Module):
         return entry
 
 
-def build_graph(pos, batch, method='radius', r=0.1, k=16, dilation=1, loop=True, as_table=False):
+def _device_draw(draw, as_table, method, dilation):
+    """True when the graph is the device-drawn dilated table: a draw was given (tables only), and the graph is a dilated kNN graph."""
+    if draw is not None and not as_table:
+        raise ValueError('draw= makes tables only: pass as_table=True')
+    return draw is not None and method == 'knn' and dilation > 1
+
+
+def build_graph(pos, batch, method='radius', r=0.1, k=16, dilation=1, loop=True, as_table=False, draw=None):
     """models/point_conv.py:341-366.  as_table: the graph as a NeighborTable of the target rows instead of an edge list (no edge
-    list is built, except for the random dilation, whose picks are made on an edge list)."""
+    list is built -- for the random dilation only with draw, a graph_ops.DilationDraw: the picks are then made by the finishing launch,
+    graph_ops.knn_dilated_table; without it they are torch.randint's, made on an edge list)."""
     assert method in ['radius', 'knn']
+    if _device_draw(draw, as_table, method, dilation):
+        return graph_ops.knn_dilated_table(pos, pos, k, dilation, batch, batch, draw=draw, self_loops='keep' if loop else 'drop')
     if method == 'radius':
         if as_table:
             return graph_ops.radius_graph_table(pos, r, batch, loop=loop, max_num_neighbors=k)
@@ -91,22 +101,29 @@ def build_graph(pos, batch, method='radius', r=0.1, k=16, dilation=1, loop=True,
     return graph_ops.knn_graph(pos, k, batch, loop=loop)
 
 
-def build_bipartite_graph(pos, batch, ratio, method='radius', r=0.1, k=32, dilation=1, as_table=False, ptr=None, n_out=None):
+def build_bipartite_graph(pos, batch, ratio, method='radius', r=0.1, k=32, dilation=1, as_table=False, ptr=None, n_out=None, draw=None):
     """models/point_conv.py:368-396: fps-sampled targets, each gathering from the full cloud.  as_table: the graph as a
     NeighborTable of the sampled rows over the full cloud instead of an edge list.  ptr (device int64 [S + 1] row boundaries of the clouds,
     in place of `batch`; as_table only): -> (table, sub_pos, sub_ptr) through graph_ops.fps_segments and the ptr forms of the table
-    builders.  Its only host reads are the total pick count -- none with n_out, the caller's promise of it -- and the finishing launch's."""
+    builders.  Its only host reads are the total pick count -- none with n_out, the caller's promise of it -- and the finishing launch's.
+    draw (a graph_ops.DilationDraw; as_table only): the random dilation of a kNN graph is drawn by the finishing launch
+    (graph_ops.knn_dilated_table) -- the only form of it the ptr= path takes."""
     assert method in ['radius', 'knn']
+    drawn = _device_draw(draw, as_table, method, dilation)
     if ptr is not None:
-        if batch is not None or not as_table or dilation > 1:
-            raise ValueError('ptr= stands in place of batch, for as_table=True and dilation 1')
+        if batch is not None or not as_table or (dilation > 1 and not drawn):
+            raise ValueError('ptr= stands in place of batch, for as_table=True and dilation 1 (a dilated kNN graph: with draw=)')
         idx, sub_ptr = graph_ops.fps_segments(pos, ptr, ratio, n_out=n_out)
         sub_pos = pos[idx]
+        if drawn:
+            return graph_ops.knn_dilated_table(pos, sub_pos, k, dilation, draw=draw, ptr_x=ptr, ptr_y=sub_ptr), sub_pos, sub_ptr
         if method == 'radius':
             return graph_ops.radius_table(pos, sub_pos, r, k, ptr_x=ptr, ptr_y=sub_ptr), sub_pos, sub_ptr
         return graph_ops.knn_table(pos, sub_pos, k, ptr_x=ptr, ptr_y=sub_ptr), sub_pos, sub_ptr
     idx = graph_ops.fps(pos, batch, ratio=ratio)
     sub_pos, sub_batch = pos[idx], (batch[idx] if batch is not None else None)
+    if drawn:
+        return graph_ops.knn_dilated_table(pos, sub_pos, k, dilation, batch, sub_batch, draw=draw), sub_pos, sub_batch
     table = None
     if method == 'radius' and (as_table or not ops.state.no_graph_tables):
         # the search's table through the finishing kernel's radius cut (the squared distance formed as the search forms it)
@@ -166,9 +183,22 @@ def use_graph_tables(net, on=True):
     return net
 
 
+def use_device_dilation(net, seed=0):
+    """Turns `graph_tables` on (use_graph_tables) and gives every sparse encoder inside `net` a fresh graph_ops.DilationDraw of `seed`
+    on the device of its parameters: the randomly dilated kNN graphs are then drawn by their finishing launch
+    (graph_ops.knn_dilated_table) -- no edge list, no loop over the clouds, reproducible from the seed and the draw's device counter
+    (`mod.dilation_draw.step()` between forwards draws afresh).  Call it after moving `net` to its device.  Returns `net`."""
+    use_graph_tables(net)
+    for mod in net.modules():
+        if hasattr(type(mod), 'dilation_draw'):
+            mod.dilation_draw = graph_ops.DilationDraw(seed, next(mod.parameters()).device)
+    return net
+
+
 class _SparseEncoder(nn.Module):
     """conv{l}_1 / conv{l}_2 pairs over an fps pyramid (point_conv.py:84-98, 302-315, 197-264)."""
     graph_tables = False         # True: the graphs as NeighborTables straight from the search (build_graph(as_table=True)), no edge lists
+    dilation_draw = None         # a graph_ops.DilationDraw (use_device_dilation): with graph_tables, dilated graphs are drawn on the device
 
     def __init__(self, in_channels, method, ratio, radius, kernel_size, dilation):
         super().__init__()
@@ -191,6 +221,8 @@ class _SparseEncoder(nn.Module):
         """-> per level (features, pos, batch), finest first."""
         levels = []
         how = {'as_table': True} if self.graph_tables else {}
+        if self.graph_tables and self.dilation_draw is not None:
+            how['draw'] = self.dilation_draw
         for lvl in range(len(ENC_WIDTHS)):
             if lvl > 0:
                 ei, pos_c, batch_c = self.build_bipartite_graph(pos, batch, self.ratio[lvl - 1], method=self.method,

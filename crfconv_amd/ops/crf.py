@@ -201,7 +201,8 @@ class _SpdInverse(torch.autograd.Function):
 
 
 class _CrfMatrices(torch.autograd.Function):
-    """c [H, H] -> Q = (I + c^T c)^-1, P = c^T c Q = I - Q: one workgroup forward, one backward (csrc/crf_matrices.hip)."""
+    """c [H, H] -> Q = (I + c^T c)^-1, P = c^T c Q = I - Q: one workgroup forward (the batched entry with one job), one backward
+    (csrc/crf_matrices.hip)."""
 
     @staticmethod
     def forward(ctx, c):
@@ -209,7 +210,8 @@ class _CrfMatrices(torch.autograd.Function):
         cc = _f32c(c)
         Q = torch.empty_like(cc)
         P = torch.empty_like(cc)
-        _lib.call('crfconv_crf_matrices', ptr(cc), cc.shape[0], ptr(Q), ptr(P), stream_ptr())
+        _lib.call('crfconv_crf_matrices_batched', _ptr_array([cc]), (ctypes.c_int * 1)(cc.shape[0]), 1, _ptr_array([Q]), _ptr_array([P]),
+                  stream_ptr())
         ctx.save_for_backward(cc, Q)
         return Q, P
 

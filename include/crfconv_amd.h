@@ -150,6 +150,17 @@ int crfconv_index_narrow_batched(const crf_narrow_job* jobs, int njobs, crf_stre
  * n_tgt * K_out < 2^31. */
 int crfconv_graph_table(const int32_t* nbr, int64_t n_tgt, int K, int64_t n_src, const float* pos_src, const float* pos_tgt,
                         float r2, int self_mode, int32_t* out, int K_out, int64_t* counts, crf_stream_t stream);
+/* The random dilation of a kNN graph (models/point_conv.py:356-364, 385-393: search k * dilation, keep k per row, drawn with
+ * replacement) as the same finishing launch.  nbr, n_src, self_mode, out and counts as above.  Per row i: valid = its in-range entries
+ * in column order, have = |valid|, n_pick = min(k_pick, have); pick t < n_pick is valid[((h(i, t) >> 32) * have) >> 32] (64-bit
+ * unsigned; within have / 2^32 of uniform), duplicates stay; self_mode 1 / 2 then drops the picks equal to i.  out [n_tgt, K_out],
+ * K_out = k_pick + (self_mode == 2) <= 64: the kept picks in pick order, i itself (self_mode 2), then -1.  h is splitmix64's finisher
+ * over  (seed ^ 0xA0761D6478BD642F) + 0x9E3779B97F4A7C15 (*counter + 1) + 0xC2B2AE3D27D4EB4F salt + 0xD1B54A32D192ED03 (64 i + t)
+ * (mod 2^64): counter is one int64 word in DEVICE memory, read by the kernel only -- a captured launch draws afresh once it was
+ * advanced --, salt >= 0 tells the graphs of one forward apart, i is the global row. */
+int crfconv_graph_table_dilated(const int32_t* nbr, int64_t n_tgt, int K, int64_t n_src, int k_pick, uint64_t seed,
+                                const int64_t* counter, int64_t salt, int self_mode, int32_t* out, int K_out, int64_t* counts,
+                                crf_stream_t stream);
 
 /* 30-bit Morton (Z-order) codes of B clouds of npts points (pts [B, npts, 3]): ten bits per axis of
  * clamp((p - lo) / ext * 1023, 0, 1023), lo = the cloud's per-axis minimum, ext = its largest extent.  The device collate sorts
@@ -739,14 +750,14 @@ int crfconv_spd_inverse(const float* M, int H, float* Q, crf_stream_t stream);
 /* The same for 64 < H <= 512 (the wide CRF stages of the sparse networks, models/point_conv.py:318-339): Gauss-Jordan without
  * pivoting on one workgroup, matrix in global memory; M symmetric positive definite (M = I + c^T c), M != Q. */
 int crfconv_spd_inverse_wide(const float* M, int H, float* Q, crf_stream_t stream);
-/* Both loop-invariant matrices of a CRF layer from its compatibility factor c [H, H] (C = c^T c) in one launch:
+/* Both loop-invariant matrices of a CRF layer from its compatibility factor c [H, H] (C = c^T c):
  *   Q = (I + C)^-1,  P = C Q = I - Q          (continuous_crf_conv_big.py:67-72: (z + m C)(I + C)^-1 = z Q + m P)
- * and the matching backward: dc from dQ / dP (either may be NULL). */
-int crfconv_crf_matrices(const float* c, int H, float* Q, float* P, crf_stream_t stream);
+ * The forward is the batched entry below (one layer = a batch of one); this is the backward of one layer: dc from dQ / dP (either
+ * may be NULL). */
 int crfconv_crf_matrices_backward(const float* c, const float* Q, const float* dQ, const float* dP, int H,
                                   float* dc, crf_stream_t stream);
-/* The same for n <= 8 layers in ONE launch each way (one workgroup per layer: the Gauss-Jordan sweep is a ~20 us latency
- * chain whatever H is).  Host arrays of n device pointers / sizes; gQ[i] / gP[i] may be NULL (= zero). */
+/* Q and P of n <= 8 layers in ONE launch, and their backward in one (one workgroup per layer: the Gauss-Jordan sweep is a ~20 us
+ * latency chain whatever H is).  Host arrays of n device pointers / sizes; gQ[i] / gP[i] may be NULL (= zero). */
 int crfconv_crf_matrices_batched(const float* const* c, const int* H, int n, float* const* Q, float* const* P,
                                  crf_stream_t stream);
 int crfconv_crf_matrices_backward_batched(const float* const* c, const float* const* Q, const float* const* gQ,
