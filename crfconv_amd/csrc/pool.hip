@@ -1,5 +1,6 @@
-// Neighbour max-pooling (strided ResNet shortcut, point_conv_big.py:74-77) and nearest
-// up-sampling (row gather, :97-101 / continuous_crf_conv_big.py:60), forward and backward.
+// Neighbour pooling over a table -- max (strided ResNet shortcut, point_conv_big.py:74-77), sum, mean and min
+// (scatter(x[j], i, reduce=), models/common.py:9-23) -- and nearest up-sampling (row gather, :97-101 /
+// continuous_crf_conv_big.py:60), forward and backward.
 // One thread per (row, 4-channel quad): 16-byte loads, a row's C/4 quads are adjacent lanes.
 #include "common.hpp"
 
@@ -47,6 +48,71 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const float* __restric
     if (who.x < 0) best = make_float4(0.f, 0.f, 0.f, 0.f);      // empty group -> 0 (scatter_max convention)
     st4(out + t * 4, best);
     *reinterpret_cast<int4*>(arg + t * 4) = who;
+}
+
+enum { POOL_SUM = 0, POOL_MEAN = 1, POOL_MAX = 2, POOL_MIN = 3 };
+
+// The other reductions of scatter(x[j], i, reduce=) over the same trip (max is maxpool_fwd_kernel<false>).  Sum: a float accumulator
+// from 0 over the valid columns in column order; mean: that sum, then one division by the degree; min: strict <, the first valid
+// column that attains it wins (arg as the max writes it).  A row without a valid entry gives 0 (arg -1).  count (may be NULL): the
+// row's degree, written by the row's first quad.
+template <int REDUCE>
+__global__ __launch_bounds__(256) void pool_fwd_kernel(const float* __restrict__ x,
+                                                       const int32_t* __restrict__ idx, int K,
+                                                       int64_t m_tgt, int C4,
+                                                       float* __restrict__ out,
+                                                       int32_t* __restrict__ arg,
+                                                       int32_t* __restrict__ count) {
+    const int64_t t = (int64_t)xcd_block_id() * 256 + threadIdx.x;
+    if (t >= m_tgt * C4) return;
+    const int64_t i = t / C4;
+    const int q = (int)(t - i * C4);
+    const int32_t* irow = idx + i * K;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);              // the running sum, or the running minimum once who >= 0
+    int4 who = make_int4(-1, -1, -1, -1);
+    int deg = 0;
+    for (int k0 = 0; k0 < K; k0 += 4) {                         // four neighbours per trip: index entries, then rows
+        int jn[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) jn[u] = k0 + u < K ? irow[k0 + u] : -1;
+        float4 vn[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) vn[u] = ld4(x + ((int64_t)(jn[u] < 0 ? 0 : jn[u]) * C4 + q) * 4);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (jn[u] < 0) continue;                             // "no neighbour" entry of a padded table
+            const float4 v = vn[u];
+            ++deg;
+            if constexpr (REDUCE == POOL_MIN) {
+                const int k = k0 + u;
+                if (v.x < acc.x || who.x < 0) { acc.x = v.x; who.x = k; }
+                if (v.y < acc.y || who.y < 0) { acc.y = v.y; who.y = k; }
+                if (v.z < acc.z || who.z < 0) { acc.z = v.z; who.z = k; }
+                if (v.w < acc.w || who.w < 0) { acc.w = v.w; who.w = k; }
+            } else {
+                acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+            }
+        }
+    }
+    if constexpr (REDUCE == POOL_MEAN) {
+        if (deg > 0) {
+            const float n = (float)deg;
+            acc = make_float4(acc.x / n, acc.y / n, acc.z / n, acc.w / n);
+        }
+    }
+    st4(out + t * 4, acc);                                       // (an empty row never left the 0 it started from)
+    if constexpr (REDUCE == POOL_MIN) *reinterpret_cast<int4*>(arg + t * 4) = who;
+    if (count != nullptr && q == 0) count[i] = deg;
+}
+
+// count[i] = valid entries of row i, for the max, whose kernel does not count: one thread per row.
+__global__ __launch_bounds__(256) void pool_count_kernel(const int32_t* __restrict__ idx, int K, int64_t m_tgt,
+                                                         int32_t* __restrict__ count) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= m_tgt) return;
+    int deg = 0;
+    for (int k = 0; k < K; ++k) deg += idx[i * K + k] >= 0 ? 1 : 0;
+    count[i] = deg;
 }
 
 __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const float* __restrict__ gout,
@@ -102,11 +168,16 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restric
     st4(out + t * 4, ld4(x + ((int64_t)idx[i] * C4 + q) * 4));
 }
 
-__global__ __launch_bounds__(256) void gather_rows_bwd_kernel(const float* __restrict__ gout,
-                                                              const int32_t* __restrict__ rev_ptr,
-                                                              const int32_t* __restrict__ rev_eid,
-                                                              int64_t m_src, int C4,
-                                                              float* __restrict__ dx) {
+// The backward of the sum and the mean over a table: dx[j] = sum over the reverse row's edges e = i K + k of gout[i] (MEAN: of
+// gout[i] / (float)count[i]).  K1: a K = 1 table (ops.gather_rows, nearest up-sampling), whose edge id IS the target row -- its own
+// instantiation, so that no division by K enters it.
+template <bool K1, bool MEAN>
+__global__ __launch_bounds__(256) void pool_bwd_kernel(const float* __restrict__ gout,
+                                                       const int32_t* __restrict__ count,
+                                                       const int32_t* __restrict__ rev_ptr,
+                                                       const int32_t* __restrict__ rev_eid, int K,
+                                                       int64_t m_src, int C4,
+                                                       float* __restrict__ dx) {
     const int64_t t = (int64_t)xcd_block_id() * 256 + threadIdx.x;
     if (t >= m_src * C4) return;
     const int64_t j = t / C4;
@@ -117,6 +188,7 @@ __global__ __launch_bounds__(256) void gather_rows_bwd_kernel(const float* __res
     // 1031 edges -- stays within a 64-term sum's rounding.
     double tx = 0.0, ty = 0.0, tz = 0.0, tw = 0.0;
     const int beg = rev_ptr[j], end = rev_ptr[j + 1];
+    [[maybe_unused]] const int kshift = (K & (K - 1)) == 0 ? __ffs(K) - 1 : -1;
     for (int p0 = beg; p0 < end; p0 += 64) {
         const int pe = min(p0 + 64, end);
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -125,11 +197,20 @@ __global__ __launch_bounds__(256) void gather_rows_bwd_kernel(const float* __res
 #pragma unroll
             for (int u = 0; u < 4; ++u) e[u] = p + u < pe ? rev_eid[p + u] : -1;
             float4 g[4];
+            [[maybe_unused]] float cn[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) g[u] = ld4(gout + ((int64_t)(e[u] < 0 ? 0 : e[u]) * C4 + q) * 4);
+            for (int u = 0; u < 4; ++u) {
+                int i = e[u] < 0 ? 0 : e[u];
+                if constexpr (!K1) i = kshift >= 0 ? (i >> kshift) : (i / K);
+                g[u] = ld4(gout + ((int64_t)i * C4 + q) * 4);
+                if constexpr (MEAN) cn[u] = (float)count[i];
+            }
 #pragma unroll
             for (int u = 0; u < 4; ++u)
-                if (e[u] >= 0) { acc.x += g[u].x; acc.y += g[u].y; acc.z += g[u].z; acc.w += g[u].w; }
+                if (e[u] >= 0) {
+                    if constexpr (MEAN) { acc.x += g[u].x / cn[u]; acc.y += g[u].y / cn[u]; acc.z += g[u].z / cn[u]; acc.w += g[u].w / cn[u]; }
+                    else { acc.x += g[u].x; acc.y += g[u].y; acc.z += g[u].z; acc.w += g[u].w; }
+                }
         }
         tx += acc.x; ty += acc.y; tz += acc.z; tw += acc.w;
     }
@@ -182,13 +263,41 @@ __global__ __launch_bounds__(256) void add_mask_kernel(const float* __restrict__
 
 using namespace crf;
 
-extern "C" int crfconv_neighbor_maxpool_forward(const float* x, const int32_t* idx32, int K, int64_t m_tgt,
-                                                int C, float* out, int32_t* arg, crf_stream_t stream) {
-    if (int rc = check(m_tgt, C)) return rc;
-    CRF_REQUIRE(x && idx32 && out && arg && K >= 1, CRF_ERR_ARG, "null pointer / K");
+// The two entries of the pooling family refuse everything with CRF_ERR_ARG.
+static int check_pool(int64_t rows, int C, int K) {
+    CRF_REQUIRE(rows > 0 && rows < ((int64_t)1 << 31), CRF_ERR_ARG, "rows=%lld out of range", (long long)rows);
+    CRF_REQUIRE(C > 0 && C % 4 == 0, CRF_ERR_ARG, "channels C=%d must be a positive multiple of 4", C);
+    CRF_REQUIRE(K >= 1, CRF_ERR_ARG, "K=%d must be at least 1", K);
+    return CRF_OK;
+}
+
+extern "C" int crfconv_neighbor_pool_forward(const float* x, const int32_t* idx32, int K, int64_t m_tgt, int C, int reduce,
+                                             float* out, int32_t* arg, int32_t* count, crf_stream_t stream) {
+    if (int rc = check_pool(m_tgt, C, K)) return rc;
+    CRF_REQUIRE(reduce >= POOL_SUM && reduce <= POOL_MIN, CRF_ERR_ARG, "reduce=%d is none of 0 (sum), 1 (mean), 2 (max), 3 (min)", reduce);
+    CRF_REQUIRE(x && idx32 && out, CRF_ERR_ARG, "null pointer");
+    CRF_REQUIRE(arg || reduce < POOL_MAX, CRF_ERR_ARG, "max and min need arg");
+    CRF_REQUIRE(count || reduce != POOL_MEAN, CRF_ERR_ARG, "mean needs count");
     const int64_t n = m_tgt * (C / 4);
-    hipLaunchKernelGGL(maxpool_fwd_kernel<false>, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, as_stream(stream), x,
-                       idx32, K, m_tgt, C / 4, out, arg, (const float*)nullptr);
+    const dim3 grid((unsigned)cdiv(n, 256)), block(256);
+    switch (reduce) {
+    case POOL_SUM:
+        hipLaunchKernelGGL(pool_fwd_kernel<POOL_SUM>, grid, block, 0, as_stream(stream), x, idx32, K, m_tgt, C / 4, out, arg, count);
+        break;
+    case POOL_MEAN:
+        hipLaunchKernelGGL(pool_fwd_kernel<POOL_MEAN>, grid, block, 0, as_stream(stream), x, idx32, K, m_tgt, C / 4, out, arg, count);
+        break;
+    case POOL_MIN:
+        hipLaunchKernelGGL(pool_fwd_kernel<POOL_MIN>, grid, block, 0, as_stream(stream), x, idx32, K, m_tgt, C / 4, out, arg, count);
+        break;
+    default:
+        hipLaunchKernelGGL(maxpool_fwd_kernel<false>, grid, block, 0, as_stream(stream), x, idx32, K, m_tgt, C / 4, out, arg,
+                           (const float*)nullptr);
+        if (count) {
+            CRF_LAUNCH_CHECK();
+            hipLaunchKernelGGL(pool_count_kernel, dim3((unsigned)cdiv(m_tgt, 256)), block, 0, as_stream(stream), idx32, K, m_tgt, count);
+        }
+    }
     CRF_LAUNCH_CHECK();
     return CRF_OK;
 }
@@ -228,14 +337,15 @@ extern "C" int crfconv_gather_rows(const float* x, const int32_t* idx32, int64_t
     return CRF_OK;
 }
 
-extern "C" int crfconv_gather_rows_backward(const float* gout, const int32_t* rev_ptr,
-                                            const int32_t* rev_eid, int64_t m_src, int C, float* dx,
-                                            crf_stream_t stream) {
-    if (int rc = check(m_src, C)) return rc;
+extern "C" int crfconv_neighbor_pool_backward(const float* gout, const int32_t* count, const int32_t* rev_ptr,
+                                              const int32_t* rev_eid, int K, int64_t m_src, int C, float* dx, crf_stream_t stream) {
+    if (int rc = check_pool(m_src, C, K)) return rc;
     CRF_REQUIRE(gout && rev_ptr && rev_eid && dx, CRF_ERR_ARG, "null pointer");
     const int64_t n = m_src * (C / 4);
-    hipLaunchKernelGGL(gather_rows_bwd_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, as_stream(stream),
-                       gout, rev_ptr, rev_eid, m_src, C / 4, dx);
+    const dim3 grid((unsigned)cdiv(n, 256)), block(256);
+    auto kernel = K == 1 ? (count ? pool_bwd_kernel<true, true> : pool_bwd_kernel<true, false>)
+                         : (count ? pool_bwd_kernel<false, true> : pool_bwd_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, grid, block, 0, as_stream(stream), gout, count, rev_ptr, rev_eid, K, m_src, C / 4, dx);
     CRF_LAUNCH_CHECK();
     return CRF_OK;
 }

@@ -1,11 +1,43 @@
 """Building blocks with the reference's names, signatures and state_dict layout
-(models/common.py:26-40, 89-97).  FastBatchNorm1d mirrors the torch_points3d module the
+(models/common.py:9-40, 89-97).  FastBatchNorm1d mirrors the torch_points3d module the
 reference imports (BatchNorm1d kept as ``.batch_norm``, statistics over every leading dim)."""
 import torch
 import torch.nn as nn
 
 from .. import ops
 from ..graph import require_gpu
+from . import graph_ops
+
+
+def _fps_graph(pos, batch, k, r, ptr):
+    """(idx, table, clouds): the farthest point picks of every cloud, the NeighborTable of the picks over all points (their k nearest
+    of the same cloud; -1 where a cloud has fewer) and the picks' cloud description -- batch[idx], None for one cloud, or with `ptr`
+    (device int64 [S + 1] in place of `batch`) the picks' own ptr, without a cloud count read back."""
+    require_gpu(pos)
+    if ptr is not None:
+        if batch is not None:
+            raise ValueError('give the batch vector or the pointer array, not both')
+        idx, ptr_out = graph_ops.fps_segments(pos, ptr, r)
+        return idx, graph_ops.knn_table(pos, pos[idx], k, ptr_x=ptr, ptr_y=ptr_out), ptr_out
+    idx = graph_ops.fps(pos, batch, ratio=r)
+    sub = None if batch is None else batch[idx]
+    return idx, graph_ops.knn_table(pos, pos[idx], k, batch, sub), sub
+
+
+def fps_pooling(pos, x, edge_attr, batch=None, k=16, r=0.5, reduce='sum', *, ptr=None):
+    """models/common.py:9-15: farthest point sampling at ratio r, then every pick pools the features of its k nearest points with
+    `reduce` -> (x, pos, edge_attr, batch) of the picks.  The graph is a NeighborTable and the reduction ops.neighbor_pool: no edge
+    list.  batch=None is one cloud (the returned batch is None); with `ptr` the last item is the picks' ptr."""
+    if reduce not in ('max', 'mean', 'add', 'sum'):
+        raise ValueError("fps_pooling: reduce must be one of 'max', 'mean', 'add', 'sum' (got %r)" % (reduce,))
+    idx, table, sub = _fps_graph(pos, batch, k, r, ptr)
+    return ops.neighbor_pool(x, table, reduce), pos[idx], edge_attr[idx], sub
+
+
+def fps_max_pooling(pos, x, batch=None, k=16, r=0.5, *, ptr=None):
+    """models/common.py:18-23: fps_pooling with the max, without edge attributes -> (x, pos, batch)."""
+    idx, table, sub = _fps_graph(pos, batch, k, r, ptr)
+    return ops.neighbor_pool(x, table, 'max'), pos[idx], sub
 
 
 class FastBatchNorm1d(nn.Module):

@@ -5,7 +5,7 @@
     crf        continuous CRF mean field (dense / wide), its matrices and their riders, the discrete CRF layer
     dense      per-point Linear and the weight gradient of a plain product (now or deferred), BatchNorm step counters, BatchNorm (+ LeakyReLU)
     mlp        Linear -> BatchNorm -> LeakyReLU blocks as single nodes (row-streaming, classifier head, coarse-level forms, groups)
-    rows       residual join, LeakyReLU, row gather, neighbour max-pool
+    rows       residual join, LeakyReLU, row gather, neighbour pooling over a table (sum, mean, max, min)
     loss       weighted soft-max cross-entropy
     pointconv  rel-pos moments, the PointConv node, the batched BatchNorm-1 prefold
     interp     kNN interpolation: the inverse-squared-distance blend over a neighbour table and its transpose, the search in front of it
@@ -21,5 +21,5 @@ for _m in (_base, defer, crf, dense, mlp, rows, loss, pointconv, interp):
     globals().update({_k: _v for _k, _v in vars(_m).items() if not _k.startswith('__')})
 del _m
 
-__all__ = ['linear', 'bn_act', 'crf_meanfield', 'gather_rows', 'neighbor_maxpool', 'relpos_moments', 'point_conv',
+__all__ = ['linear', 'bn_act', 'crf_meanfield', 'gather_rows', 'neighbor_maxpool', 'neighbor_pool', 'relpos_moments', 'point_conv',
            'point_conv_prefold', 'cross_entropy', 'training_loss', 'interpolate', 'knn_interpolate', 'NeighborTable']

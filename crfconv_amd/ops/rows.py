@@ -1,4 +1,4 @@
-"""Residual join, LeakyReLU, row gather, neighbour max-pool."""
+"""Residual join, LeakyReLU, row gather, neighbour pooling (max, and the sum / mean / max / min family)."""
 import ctypes
 
 import torch
@@ -93,7 +93,7 @@ class _GatherRows(torch.autograd.Function):
         g = _f32c(gout)
         rev_ptr, rev_eid = table.reverse
         dx = torch.empty((ctx.m_src, g.shape[1]), dtype=torch.float32, device=g.device)
-        _lib.call('crfconv_gather_rows_backward', ptr(g), ptr(rev_ptr), ptr(rev_eid), ctx.m_src, g.shape[1],
+        _lib.call('crfconv_neighbor_pool_backward', ptr(g), None, ptr(rev_ptr), ptr(rev_eid), 1, ctx.m_src, g.shape[1],
                   ptr(dx), stream_ptr())
         return dx, None
 
@@ -116,8 +116,8 @@ class _MaxPool(torch.autograd.Function):
         C = x.shape[1]
         out = torch.empty((table.m_tgt, C), dtype=torch.float32, device=x.device)
         arg = torch.empty((table.m_tgt, C), dtype=torch.int32, device=x.device)
-        _lib.call('crfconv_neighbor_maxpool_forward', ptr(x), ptr(table.idx32), table.K, table.m_tgt, C, ptr(out),
-                  ptr(arg), stream_ptr())
+        _lib.call('crfconv_neighbor_pool_forward', ptr(x), ptr(table.idx32), table.K, table.m_tgt, C, 2, ptr(out),      # reduce = 2: max
+                  ptr(arg), None, stream_ptr())
         ctx.table, ctx.m_src = table, x.shape[0]
         ctx.save_for_backward(arg)
         return out
@@ -139,4 +139,59 @@ def neighbor_maxpool(x, table):
     C = x.shape[1]
     Cp = (C + 3) // 4 * 4
     out = _MaxPool.apply(_pad_channels(x, Cp), table)
+    return out[:, :C] if Cp != C else out
+
+
+# ------------------------------------------------------------------------------ sum / mean / max / min over a table
+POOL_REDUCE = {'sum': 0, 'add': 0, 'mean': 1, 'max': 2, 'min': 3}      # the `reduce` codes of crfconv_neighbor_pool_forward
+
+
+class _NeighborPool(torch.autograd.Function):
+    """scatter(x[j], i, dim=0, reduce=) over a NeighborTable: one launch each way, no edge list, no atomics.  Sum and mean go back
+    through the table's reverse CSR (the mean with the degrees the forward counted), max and min through their winning columns."""
+
+    @staticmethod
+    def forward(ctx, x, table, reduce):
+        require_gpu(x)
+        x = _f32c(x)
+        C = x.shape[1]
+        out = torch.empty((table.m_tgt, C), dtype=torch.float32, device=x.device)
+        arg = torch.empty((table.m_tgt, C), dtype=torch.int32, device=x.device) if reduce >= POOL_REDUCE['max'] else None
+        count = torch.empty(table.m_tgt, dtype=torch.int32, device=x.device) if reduce == POOL_REDUCE['mean'] else None
+        _lib.call('crfconv_neighbor_pool_forward', ptr(x), ptr(table.idx32), table.K, table.m_tgt, C, reduce, ptr(out), ptr(arg),
+                  ptr(count), stream_ptr())
+        ctx.table, ctx.m_src, ctx.extreme = table, x.shape[0], arg is not None
+        ctx.save_for_backward(arg if arg is not None else count)      # (None for the sum)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        (saved,) = ctx.saved_tensors
+        table = ctx.table
+        g = _f32c(gout)
+        rev_ptr, rev_eid = table.reverse
+        dx = torch.empty((ctx.m_src, g.shape[1]), dtype=torch.float32, device=g.device)
+        if ctx.extreme:
+            _lib.call('crfconv_neighbor_maxpool_backward', ptr(g), ptr(saved), ptr(rev_ptr), ptr(rev_eid), table.K,
+                      ctx.m_src, g.shape[1], ptr(dx), stream_ptr())
+        else:
+            _lib.call('crfconv_neighbor_pool_backward', ptr(g), ptr(saved), ptr(rev_ptr), ptr(rev_eid), table.K,
+                      ctx.m_src, g.shape[1], ptr(dx), stream_ptr())
+        return dx, None, None
+
+
+def neighbor_pool(x, table, reduce='sum'):
+    """out[i] = reduce_k x[table[i, k]] over the row's valid entries: torch_scatter's scatter(x[j], i, dim=0, reduce=reduce) for the
+    graph the table holds (models/common.py:13, 21).  x [m_src, C] float32, any C; reduce 'sum' (= 'add'), 'mean', 'max' or 'min'; a
+    target without a neighbour gets 0.  Dense and padded tables alike; deterministic forward and backward."""
+    if reduce not in POOL_REDUCE:
+        raise ValueError("neighbor_pool: reduce must be one of 'sum', 'add', 'mean', 'max', 'min' (got %r)" % (reduce,))
+    require_gpu(x)
+    if x.dim() != 2 or x.shape[0] != table.m_src:
+        raise ValueError('neighbor_pool: x must be [m_src = %d, C], got %s' % (table.m_src, tuple(x.shape)))
+    C = x.shape[1]
+    if table.m_tgt == 0 or table.m_src == 0 or C == 0:
+        return x.new_zeros((table.m_tgt, C), dtype=torch.float32)      # nothing to pool: no library call
+    Cp = (C + 3) // 4 * 4
+    out = _NeighborPool.apply(_pad_channels(x, Cp), table, POOL_REDUCE[reduce])
     return out[:, :C] if Cp != C else out

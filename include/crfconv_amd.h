@@ -765,9 +765,16 @@ int crfconv_crf_matrices_backward_batched(const float* const* c, const float* co
                                           crf_stream_t stream);
 
 /* ===================================================================== (B) pooling / up-sampling
- * out[i,c] = max_k x[idx32[i,k], c];  arg [m_tgt, C] int32 = winning k (first maximum). */
-int crfconv_neighbor_maxpool_forward(const float* x, const int32_t* idx32, int K, int64_t m_tgt,
-                                     int C, float* out, int32_t* arg, crf_stream_t stream);
+ * out[i] = reduce_k x[idx32[i,k]] over the row's valid entries (an entry < 0 is "no neighbour"): scatter(x[j], i, dim=0, reduce=)
+ * over a neighbour table.  reduce: 0 sum, 1 mean, 2 max, 3 min.
+ *   sum   a float accumulator from 0 adds the valid entries in column order (a source named twice counts twice);
+ *   mean  that sum, then one division by (float)degree;
+ *   max / min  strict comparison, the first valid column that attains the extreme wins; arg [m_tgt, C] int32 = its column.
+ * A row without a valid entry gives 0 and arg -1.  arg: required for max and min, unused (may be NULL) for sum and mean.
+ * count [m_tgt] int32 = the row's degree: required for mean, optional (may be NULL) otherwise.  C % 4 == 0; anything else is
+ * CRF_ERR_ARG. */
+int crfconv_neighbor_pool_forward(const float* x, const int32_t* idx32, int K, int64_t m_tgt, int C, int reduce,
+                                  float* out, int32_t* arg, int32_t* count, crf_stream_t stream);
 /* The strided shortcut of a ResNet block (models/point_conv_big.py:74-83: shortcut MLP, then max over the sub_idx
  * neighbours) without the normalised fine-level tensor: out[i,c] = max_k (a[c] x[idx32[i,k], c] + b[c]) with coef = the
  * [4, C] block of crfconv_bn_coef_from_records for x.  arg as above; the backward is crfconv_neighbor_maxpool_backward. */
@@ -780,10 +787,12 @@ int crfconv_neighbor_maxpool_backward(const float* gout, const int32_t* arg,
 /* out[i] = x[idx32[i]]  (K = 1 table: nearest up-sampling, point_conv_big.py:97-101). */
 int crfconv_gather_rows(const float* x, const int32_t* idx32, int64_t m_tgt, int C, float* out,
                         crf_stream_t stream);
-/* dx[j] = sum_{i in rev(j)} gout[i]. */
-int crfconv_gather_rows_backward(const float* gout, const int32_t* rev_ptr,
-                                 const int32_t* rev_eid, int64_t m_src, int C, float* dx,
-                                 crf_stream_t stream);
+/* The backward of the sum and the mean (that of max and min is crfconv_neighbor_maxpool_backward), without atomics:
+ * dx[j] = sum over the edges e = i K + k of reverse row j of gout[i] (count == NULL: sum) or of gout[i] / (float)count[i] (mean; count
+ * as the forward wrote it) -- in edge order, 64 edges per float partial sum, the partial sums added in double.  K = 1, count == NULL is
+ * the backward of crfconv_gather_rows: dx[j] = sum_{i in rev(j)} gout[i]. */
+int crfconv_neighbor_pool_backward(const float* gout, const int32_t* count, const int32_t* rev_ptr, const int32_t* rev_eid,
+                                   int K, int64_t m_src, int C, float* dx, crf_stream_t stream);
 
 /* out = lrelu(a + b, slope) over n floats (n % 4 == 0): the residual join of the ResNet block
  * (point_conv_big.py:86-88); backward gin = gout * (out > 0 ? 1 : slope), shared by both addends. */
