@@ -53,6 +53,42 @@ def test_meanfield_width_list_has_no_default_case():
     assert lib.crfconv_wide_similarity(None, None, 16, 0, 10, 128, None, None) == -1      # a wide width: on to the null-pointer check
 
 
+def test_kernel_weights_entries_check_their_arguments():
+    """crfconv_kernel_weights_forward / _backward (csrc/discrete.hip) refuse before any HIP call: row and degree range (-1), kernel count
+    and hidden width outside what is compiled (-3), null pointers and dfk aliasing dfk_self (-1); the float64 dW partials are one slab of
+    DW_GMAX = 8 per workgroup of DW_ROWS = 4 rows."""
+    from crfconv_amd import _lib
+    lib = _lib.load()
+
+    def fwd(K=16, G=5, H=64, m=10, p=None):
+        return lib.crfconv_kernel_weights_forward(p, p, K, p, G, H, m, p, None)
+
+    def bwd(K=16, G=5, H=64, m=10, p=None, dfk=None):
+        return lib.crfconv_kernel_weights_backward(p, p, p, p, p, K, p, G, H, m, p, p if dfk is None else dfk, p, None)
+
+    for f in (fwd, bwd):
+        assert f() == -1 and b'null pointer' in lib.crfconv_last_error()
+        for G in (0, 9):
+            assert f(G=G) == -3 and (b'num_kernels=%d' % G) in lib.crfconv_last_error()
+        for H in (0, 257):
+            assert f(H=H) == -3 and (b'hidden_channels=%d' % H) in lib.crfconv_last_error()
+        for K in (0, 65):
+            assert f(K=K) == -1 and (b'K=%d' % K) in lib.crfconv_last_error()
+        for m in (0, -1):
+            assert f(m=m) == -1 and b'out of range' in lib.crfconv_last_error()
+        assert f(K=64, m=2 ** 31 // 64) == -1 and b'out of range' in lib.crfconv_last_error()       # m * K == 2^31: edge ids leave int32
+        assert f(K=64, m=2 ** 31 // 64 - 1) == -1 and b'null pointer' in lib.crfconv_last_error()   # the largest table passes the range check
+        for G, H, K in ((1, 1, 1), (8, 256, 64)):                                                   # the corners of what is compiled
+            assert f(G=G, H=H, K=K) == -1 and b'null pointer' in lib.crfconv_last_error()
+    # never dereferenced: the alias check refuses in front of the first launch
+    import ctypes
+    a, b = ctypes.create_string_buffer(64), ctypes.create_string_buffer(64)
+    pa, pb = ctypes.addressof(a), ctypes.addressof(b)
+    assert bwd(p=pa) == -1 and b'alias' in lib.crfconv_last_error()
+    assert bwd(p=pa, dfk=pb, G=9) == -3
+    assert [lib.crfconv_kernel_weights_partials(m) for m in (1, 4, 5)] == [8, 8, 16]
+
+
 def test_state_dict_layout_matches_reference(golden):
     from crfconv_amd import models
     g = golden('g5_pointconvbig.npz')
