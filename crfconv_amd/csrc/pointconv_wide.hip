@@ -1,4 +1,4 @@
-// Parameter gradients of the WIDE PointConv layers (d = 32, 64: the 10 240- and 2 560-point levels of PointConvBig) on the
+// Parameter gradients of the WIDE PointConv layers (d = 32, 64, 128: the 10 240-, 2 560- and 640-point levels of PointConvBig) on the
 // matrix pipe, in one pass over the edges and without any per-edge tensor in memory.
 //
 // What is computed (models/point_conv_big.py:20-23, 37-58, backward of the weight MLP's second layer and of its first layer's
@@ -25,6 +25,7 @@
 // reductions at the end of the backward pass (crfconv_reduce_jobs, crfconv_reduce_jobs_f64).
 #include "common.hpp"
 #include "gridsync.hpp"
+#include "wgrad_body.hpp"
 
 namespace crf {
 
@@ -254,16 +255,225 @@ __device__ __forceinline__ void wide_params_body(const WideJobs& t, const int jo
     }
 }
 
-// Both widths in ONE launch (round 5): the d = 32 layers (854 workgroups at config 2) and the d = 64 ones (214) used to be two launches
-// of ~41 us each at the end of the backward pass, neither of which fills the chip; a workgroup looks its job up and dispatches on the
-// job's width.
+// d = 128 (the 640-point level): the same pass with a PAIR of wavefronts per target point.  One wavefront would hold (d/16)^2 = 64
+// dW2 tiles = 256 accumulators beside everything else and spill; here wavefront `half` of a pair evaluates products (1) and (3) for the
+// column tiles 4 half .. 4 half + 3 and product (5) for the row tiles 4 half .. 4 half + 3 (accW: 4 x 8 tiles = 128 registers).  Both
+// evaluate layer 1 for every k-step (it IS the A fragment of (1)); each stores its half of the H1 tile and its columns of the GH2
+// tile, and the pair reads the other half back from LDS.  Every pair of a workgroup walks the same number of points (a pair past the
+// end of the range runs a point with sixteen missing edges: zeros into every sum), so the exchange is a workgroup barrier.
+// The [d, 4] sums of a pair live in LDS, in float64, not in registers (accW leaves none to spare): each wavefront adds a point's sums to
+// its channels.  Every product keeps the summation order of the pass it replaces (the dump, crfconv_gemm_jobs, the a1 slab pass and the
+// weight-gradient partial pass over the dumped rows), so a training step computes what it computed on that path, bit for bit.
+// LDS: W2 (D x (D + 4)) + one GH2 / H1 / rel tile set and one [D, 4] float64 sum per pair: 159 KB at four pairs.
+constexpr int WP_PAIRS = WP_WAVES / 2;
+template <int D>
+constexpr int wide_params_pair_lds_floats() {
+    return D * (D + 4) + 4 * D + 3 * D + WP_PAIRS * 16 * (D + 4) + WP_PAIRS * 16 * (D + 16) + 4 * WP_PAIRS * 16 + 2 * WP_PAIRS * 4 * D;
+}
+template <int D>
+__device__ __forceinline__ void wide_params_pair_body(const WideJobs& t, const int job, const int blk, float* __restrict__ lds) {
+    constexpr int T16 = D / 16, TH = T16 / 2, S4 = D / 4, LDW = D + 4, LDG = D + 4, LDH = D + 16, K = 16;
+    constexpr int UNR = 4;
+    static_assert(T16 % 2 == 0, "tile halves");
+    float* const s_w2 = lds;
+    float4* const s_a1 = reinterpret_cast<float4*>(s_w2 + D * LDW);
+    float* const s_coef = reinterpret_cast<float*>(s_a1 + D);
+    float (*s_g)[K * LDG] = reinterpret_cast<float (*)[K * LDG]>(s_coef + 3 * D);
+    float (*s_h)[K * LDH] = reinterpret_cast<float (*)[K * LDH]>(s_coef + 3 * D + WP_PAIRS * K * LDG);
+    float4 (*s_rel)[K] = reinterpret_cast<float4 (*)[K]>(s_coef + 3 * D + WP_PAIRS * K * (LDG + LDH));
+    double (*s_sum)[4 * D] = reinterpret_cast<double (*)[4 * D]>(s_coef + 3 * D + WP_PAIRS * K * (LDG + LDH) + 4 * WP_PAIRS * K);      // dA1 | db1 of the pair's points, float64
+    float* s_red = s_w2;
+    const int nblk = t.nblk[job], m = t.m_tgt[job];
+    const float* __restrict__ x = t.x[job];
+    const float* __restrict__ gout = t.gout[job];
+    const float* __restrict__ pos_src = t.pos_src[job];
+    const float* __restrict__ pos_tgt = t.pos_tgt[job];
+    const int32_t* __restrict__ idx = t.idx[job];
+    const float slope = t.slope[job];
+    {
+        for (int i = threadIdx.x; i < WP_PAIRS * 4 * D; i += WP_BLOCK) s_sum[0][i] = 0.0;
+        const float* __restrict__ W2 = t.W2[job];
+        // 64 KB per workgroup: sixteen bytes per lane where W2 allows it (a slice of a flat parameter vector may start anywhere)
+        if ((reinterpret_cast<uintptr_t>(W2) & 15) == 0) {
+            for (int i = threadIdx.x; i < D * D / 4; i += WP_BLOCK)
+                *reinterpret_cast<float4*>(s_w2 + (i / (D / 4)) * LDW + 4 * (i % (D / 4))) = reinterpret_cast<const float4*>(W2)[i];
+        } else {
+            for (int i = threadIdx.x; i < D * D; i += WP_BLOCK) s_w2[(i / D) * LDW + (i % D)] = W2[i];
+        }
+        const float* __restrict__ A1 = t.A1[job];
+        const float* __restrict__ b1 = t.b1[job];
+        for (int c = threadIdx.x; c < D; c += WP_BLOCK) {
+            s_a1[c] = make_float4(A1[3 * c], A1[3 * c + 1], A1[3 * c + 2], b1[c]);
+            s_coef[c] = t.ca[job][c];
+            s_coef[D + c] = t.cb[job][c];
+            s_coef[2 * D + c] = t.cc[job][c];
+        }
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, pair = wave >> 1, half = wave & 1;
+    const int e = lane & 15, kq = lane >> 4;
+    const int t0 = TH * half;                             // this wavefront's first column tile of (1), (3) and row tile of (5)
+    float* tg = s_g[pair];
+    float* th = s_h[pair];
+    float4* trel = s_rel[pair];
+    f32x4w accW[TH][T16];
+#pragma unroll
+    for (int a = 0; a < TH; ++a)
+#pragma unroll
+        for (int b = 0; b < T16; ++b) accW[a][b] = f32x4w{0.f, 0.f, 0.f, 0.f};
+
+    const int per = (m + nblk - 1) / nblk;
+    const int p0 = blk * per, p1 = p0 + per < m ? p0 + per : m;
+    for (int pb = p0; pb < p1; pb += WP_PAIRS) {          // the same trip count for every pair: workgroup barriers inside
+        const bool active = pb + pair < p1;
+        const int p = active ? pb + pair : p0;
+        const int jraw = idx[(int64_t)p * K + e];
+        const bool live = active && jraw >= 0;
+        const int64_t j = live ? jraw : 0;
+        const float rx = pos_tgt[3 * (int64_t)p] - pos_src[3 * j], ry = pos_tgt[3 * (int64_t)p + 1] - pos_src[3 * j + 1],
+                    rz = pos_tgt[3 * (int64_t)p + 2] - pos_src[3 * j + 2];
+        int jr[4];
+        bool lr[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            jr[r] = __shfl((int)j, 4 * kq + r, WAVE);
+            lr[r] = __shfl(live ? 1 : 0, 4 * kq + r, WAVE) != 0;
+        }
+        if (half == 0 && kq == 0) trel[e] = live ? make_float4(rx, ry, rz, 1.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+        // ---- (1) H2 = H1 W2^T for this wavefront's column tiles; it stores the H1 channels of its half of the k-steps
+        f32x4w acc[TH];
+#pragma unroll
+        for (int tj = 0; tj < TH; ++tj) acc[tj] = f32x4w{0.f, 0.f, 0.f, 0.f};
+#pragma unroll UNR
+        for (int s = 0; s < S4; ++s) {
+            const float4 a = s_a1[4 * s + kq];
+            const float pre = fmaf(a.x, rx, fmaf(a.y, ry, fmaf(a.z, rz, a.w)));
+            const float h = live ? (pre > 0.f ? pre : slope * pre) : 0.f;
+            if ((s >= S4 / 2) == (half != 0)) th[e * LDH + 4 * s + kq] = h;
+#pragma unroll
+            for (int tj = 0; tj < TH; ++tj)
+                acc[tj] = __builtin_amdgcn_mfma_f32_16x16x4f32(h, s_w2[(16 * (t0 + tj) + e) * LDW + 4 * s + kq], acc[tj], 0, 0, 0);
+        }
+        // ---- (2) gh2 for this wavefront's columns
+#pragma unroll
+        for (int tj = 0; tj < TH; ++tj) {
+            const int c = 16 * (t0 + tj) + e;
+            const float va = s_coef[c], vb = s_coef[D + c], vc = s_coef[2 * D + c];
+            // (issued ahead of product (1), as the narrower widths do, these rows measured no faster: 121.0 us either way)
+            const float gic = gout[(int64_t)p * D + c];
+            float xc[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) xc[r] = x[(int64_t)jr[r] * D + c];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float gh = fmaf(va, gic * xc[r], fmaf(vb, acc[tj][r], vc));
+                tg[(4 * kq + r) * LDG + c] = lr[r] ? gh : 0.f;
+            }
+        }
+        __syncthreads();                                         // both halves of the pair's GH2, H1 and rel tiles are written
+        // ---- (3) GW = GH2 W2 for this wavefront's column tiles (c').  The k index of lane group kq in instruction e of sixteen-channel
+        // step s is 16 s + 4 kq + e: gemm_tile's order (the product crfconv_gemm_jobs formed from the dumped g_h2), bit for bit
+#pragma unroll
+        for (int tj = 0; tj < TH; ++tj) acc[tj] = f32x4w{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 2
+        for (int s = 0; s < D / 16; ++s) {
+            const float4 a4 = *reinterpret_cast<const float4*>(tg + e * LDG + 16 * s + 4 * kq);
+            const float av[4] = {a4.x, a4.y, a4.z, a4.w};
+#pragma unroll
+            for (int ee = 0; ee < 4; ++ee)
+#pragma unroll
+                for (int tj = 0; tj < TH; ++tj)
+                    acc[tj] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[ee], s_w2[(16 * s + 4 * kq + ee) * LDW + 16 * (t0 + tj) + e], acc[tj], 0, 0, 0);
+        }
+        // ---- (4) gp = GW lrelu'(H1) in float; its products with {rel, 1} and their sums in float64, as a1_reduce_body forms them from the
+        // dumped tensors: over the four rows here, over kq by shuffles, into the pair's LDS sums
+        {
+            float4 rl[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) rl[r] = trel[4 * kq + r];
+#pragma unroll
+            for (int tj = 0; tj < TH; ++tj) {
+                double v[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float h = th[(4 * kq + r) * LDH + 16 * (t0 + tj) + e];
+                    const double gp = (double)(acc[tj][r] * (h > 0.f ? 1.f : slope));
+                    v[0] += gp * (double)rl[r].x; v[1] += gp * (double)rl[r].y; v[2] += gp * (double)rl[r].z; v[3] += gp * (double)rl[r].w;
+                }
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    v[c] += __shfl_xor(v[c], 16, WAVE);
+                    v[c] += __shfl_xor(v[c], 32, WAVE);
+                }
+                if (kq == 0) {
+                    double* const dst = &s_sum[pair][4 * (16 * (t0 + tj) + e)];
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) dst[c] += v[c];
+                }
+            }
+        }
+        // ---- (5) dW2 += GH2^T H1: this wavefront's row tiles (c) against every column tile (c')
+#pragma unroll 2
+        for (int s = 0; s < 4; ++s) {
+            float af[TH], bf[T16];
+#pragma unroll
+            for (int ti = 0; ti < TH; ++ti) af[ti] = tg[(4 * s + kq) * LDG + 16 * (t0 + ti) + e];
+#pragma unroll
+            for (int tj = 0; tj < T16; ++tj) bf[tj] = th[(4 * s + kq) * LDH + 16 * tj + e];
+#pragma unroll
+            for (int ti = 0; ti < TH; ++ti)
+#pragma unroll
+                for (int tj = 0; tj < T16; ++tj)
+                    accW[ti][tj] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[ti], bf[tj], accW[ti][tj], 0, 0, 0);
+        }
+        __syncthreads();                                         // the next point overwrites the tiles (after the last: everyone is done with W2)
+    }
+    // ---- block sums.  accW[ti][tj][r] = dW2[c = 16 (t0 + ti) + 4 kq + r][c' = 16 tj + e]: the two wavefronts of a pair own disjoint
+    // rows; the pairs add in turn, ((p0 + p1) + p2) + p3 -- wgrad_body's order over its four wavefronts, which walk the sixteen-row groups
+    // (= points) of a row slice as the pairs walk the points here.  Rows of LDW floats: the four k-groups of a wavefront in different banks
+    for (int q = 0; q < WP_PAIRS; ++q) {
+        if (pair == q) {
+#pragma unroll
+            for (int ti = 0; ti < TH; ++ti)
+#pragma unroll
+                for (int tj = 0; tj < T16; ++tj)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int o = (16 * (t0 + ti) + 4 * kq + r) * LDW + 16 * tj + e;
+                        s_red[o] = (q == 0 ? 0.f : s_red[o]) + accW[ti][tj][r];
+                    }
+        }
+        __syncthreads();
+    }
+    {
+        float* __restrict__ out = t.dw2_partial[job] + (int64_t)blk * D * D;
+        for (int i = threadIdx.x; i < D * D; i += WP_BLOCK) out[i] = s_red[(i / D) * LDW + (i % D)];
+    }
+    // [d, 4] sums: over the pairs in float64 (every wavefront left s_sum before the loop's last barrier)
+    {
+        double* __restrict__ outd = t.a1_partial[job] + (int64_t)blk * 4 * D;
+        for (int i = threadIdx.x; i < 4 * D; i += WP_BLOCK) {
+            double a = 0.0;
+#pragma unroll
+            for (int w = 0; w < WP_PAIRS; ++w) a += s_sum[w][i];
+            outd[i] = a;
+        }
+    }
+}
+
+// Every width in ONE launch (round 5: d = 32 and 64; d = 128 since the pair form): the d = 32 layers (854 workgroups at config 2) and
+// the d = 64 ones (214) used to be two launches of ~41 us each at the end of the backward pass, neither of which fills the chip; a
+// workgroup looks its job up and dispatches on the job's width.  One LDS buffer of the largest width: one workgroup per CU, as the
+// d = 64 buffer already meant.
 __global__ __launch_bounds__(WP_BLOCK) void wide_params_any_kernel(const WideJobs t) {
-    __shared__ __attribute__((aligned(16))) float lds[wide_params_lds_floats<64>()];
+    __shared__ __attribute__((aligned(16))) float lds[wide_params_pair_lds_floats<128>()];
+    static_assert(wide_params_pair_lds_floats<128>() >= wide_params_lds_floats<64>(), "the buffer of the largest width");
     int job = 0;
     while (job + 1 < t.njobs && t.blk_base[job + 1] <= (int)blockIdx.x) ++job;
     const int blk = (int)blockIdx.x - t.blk_base[job];
     if (t.d[job] == 32) wide_params_body<32>(t, job, blk, lds);
-    else wide_params_body<64>(t, job, blk, lds);
+    else if (t.d[job] == 64) wide_params_body<64>(t, job, blk, lds);
+    else wide_params_pair_body<128>(t, job, blk, lds);
 }
 
 // ------------------------------------------------------------------ forward statistics pass of the wide layers on the matrix pipe
@@ -422,9 +632,11 @@ int uvstats_mfma_launch(const float* x, const float* pos_src, const float* pos_t
     return CRF_OK;
 }
 
+// The d = 128 parameter pass (wide_params_pair_body; not the forward kernels' table above) takes the partition of the weight-gradient pass
+// over the m_tgt * 16 dumped edge rows it replaces (wg_plan: 256-row slices = 16 points per workgroup, four per pair, at the 640-point
+// level): same slabs, same sums -- dW2 comes out bit-identical to the dump + GEMM path's.
 static int64_t wide_nblk(int64_t m_tgt, int d) {
-    (void)d;
-    int64_t nb = cdiv(m_tgt, wide_points_per_wave(m_tgt) * WP_WAVES);
+    int64_t nb = d == 128 ? wg_plan(m_tgt * 16, 128, 128).nblk : cdiv(m_tgt, wide_points_per_wave(m_tgt) * WP_WAVES);
     if (nb < 1) nb = 1;
     if (nb > 2048) nb = 2048;
     return nb;
@@ -435,9 +647,9 @@ static int64_t wide_nblk(int64_t m_tgt, int d) {
 using namespace crf;
 
 extern "C" int crfconv_pointconv_wide_params_supported(int64_t m_tgt, int K, int d) {
-    // (d = 128 compiles to 256 + 256 registers with a few spilled to scratch -- and scratch kernels cannot sit in a replayed hipGraph
-    // on ROCm 7.2: the 640-point level keeps the dump + GEMM passes)
-    return (K == 16 && (d == 32 || d == 64) && m_tgt > 0 && m_tgt < ((int64_t)1 << 27)) ? 1 : 0;
+    // (d = 128: a pair of wavefronts per point -- one wavefront per point compiles to 256 + 256 registers with a few spilled to scratch,
+    // and scratch kernels cannot sit in a replayed hipGraph on ROCm 7.2)
+    return (K == 16 && (d == 32 || d == 64 || d == 128) && m_tgt > 0 && m_tgt < ((int64_t)1 << 27)) ? 1 : 0;
 }
 
 extern "C" int64_t crfconv_pointconv_wide_params_nblk(int64_t m_tgt, int d) {
@@ -451,16 +663,16 @@ extern "C" int crfconv_pointconv_wide_params_jobs(const crf_pc_wide_job* jobs, i
     for (int j = 0; j < njobs; ++j) {
         const crf_pc_wide_job& jb = jobs[j];
         CRF_REQUIRE(crfconv_pointconv_wide_params_supported(jb.m_tgt, jb.K, jb.d) == 1, CRF_ERR_UNSUPPORTED,
-                    "job %d: K=%d d=%d m_tgt=%lld outside the matrix-pipe parameter pass (K = 16, d in {32, 64})", j, jb.K, jb.d,
+                    "job %d: K=%d d=%d m_tgt=%lld outside the matrix-pipe parameter pass (K = 16, d in {32, 64, 128})", j, jb.K, jb.d,
                     (long long)jb.m_tgt);
         CRF_REQUIRE(jb.x && jb.gout && jb.pos_src && jb.pos_tgt && jb.idx32 && jb.A1 && jb.b1 && jb.W2 && jb.ca && jb.cb && jb.cc &&
                         jb.dw2_partial && jb.a1_partial, CRF_ERR_ARG, "job %d: null pointer", j);
     }
-    // the jobs in the caller's order, WP_MAX per launch, both widths together (the longest-running width first: its workgroups start first)
-    int order[2] = {64, 32};
+    // the jobs in the caller's order, WP_MAX per launch, all widths together (the longest-running width first: its workgroups start first)
+    int order[3] = {128, 64, 32};
     int idx[64];
     int nidx = 0;
-    for (int w = 0; w < 2; ++w)
+    for (int w = 0; w < 3; ++w)
         for (int j = 0; j < njobs && nidx < 64; ++j)
             if (jobs[j].d == order[w]) idx[nidx++] = j;
     CRF_REQUIRE(nidx == njobs, CRF_ERR_UNSUPPORTED, "at most 64 jobs per call");

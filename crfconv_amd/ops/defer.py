@@ -235,9 +235,11 @@ def _flush_pc_wide():
         return
     st = stream_ptr()
     lib = _lib.load()
-    # d = 32 / 64 with K = 16: the whole pass on the matrix pipe, no per-edge tensor (csrc/pointconv_wide.hip) -- one launch per width;
-    # its per-workgroup slabs join the batched sums below (dW2: crfconv_reduce_jobs, dA1 | db1: crfconv_reduce_jobs_f64)
-    mfma = [w for w in wide if lib.crfconv_pointconv_wide_params_supported(w['m_tgt'], w['K'], w['d']) == 1]
+    # d = 32 / 64 / 128 with K = 16: the whole pass on the matrix pipe, no per-edge tensor (csrc/pointconv_wide.hip) -- one launch for
+    # all widths; its per-workgroup slabs join the batched sums below (dW2: crfconv_reduce_jobs, dA1 | db1: crfconv_reduce_jobs_f64).
+    # Every other (K, d), and d = 128 under state.no_wide128: dump + GEMM below
+    mfma = [w for w in wide if lib.crfconv_pointconv_wide_params_supported(w['m_tgt'], w['K'], w['d']) == 1
+            and not (state.no_wide128 and w['d'] == 128)]
     if mfma:
         wide = [w for w in wide if not any(w is v for v in mfma)]
         jobs, keep_m = [], []

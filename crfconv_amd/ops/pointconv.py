@@ -275,7 +275,7 @@ class _PointConv(torch.autograd.Function):
 
 
 _PC_D = (4, 8, 16, 32, 64, 128)
-_PC_PARAMS_INKERNEL_MAX_D = 16          # wider: the matrix-pipe parameter pass (d = 32, 64) / per-edge dump + MFMA reductions (d = 128)
+_PC_PARAMS_INKERNEL_MAX_D = 16          # wider: the matrix-pipe parameter pass (K = 16: d = 32, 64, 128) / per-edge dump + MFMA reductions (any other K; d = 128 under state.no_wide128)
 
 
 def pack_moments(moments):
