@@ -7,14 +7,9 @@
 #include "pointconv_common.hpp"
 #include "crf_matrices_body.hpp"
 #include "uv_fold.hpp"
+#include "pointconv_wide.hpp"      // uvstats_mfma_ok / uvstats_mfma_launch: the matrix-pipe statistics pass of the wide layers
 
 namespace crf {
-
-// matrix-pipe forms of the wide layers (pointconv_wide.hip)
-bool uvstats_mfma_ok(int K, int d);
-int uvstats_mfma_launch(const float* x, const float* pos_src, const float* pos_tgt, const int32_t* idx32, int64_t m_tgt, int d,
-                        const float* A1, const float* b1, const float* W2, float slope, const float* mean_rel3, float* shift, float* U,
-                        float* V, float* partial, int64_t max_blocks, int64_t* nblk_out, unsigned* ticket, double* stats, hipStream_t st);
 
 // ------------------------------------------------------------------ forward
 template <int D>
@@ -445,7 +440,7 @@ extern "C" int crfconv_pointconv_forward_uv(const float* x, const float* pos_src
     hipStream_t st = as_stream(stream);
     float* partial = reinterpret_cast<float*>(workspace);
     if (uvstats_mfma_ok(K, d) && m_tgt < ((int64_t)1 << 27)) {
-        // wide layers, K = 16: layer 2 of a point's sixteen edges on the matrix pipe (pointconv_wide.hip)
+        // wide layers, K = 16: layer 2 of a point's sixteen edges on the matrix pipe (pointconv_wide_stats.hip)
         const int64_t room = (int64_t)(workspace_bytes / (sizeof(float) * 2 * d));
         if (int rc = uvstats_mfma_launch(x, pos_src, pos_tgt, idx32, m_tgt, d, A1, b1, W2, slope, mean_rel3, shift, U, V, partial, room, &nblk, ticket, stats, st)) return rc;
         return ticket != nullptr ? CRF_OK : reduce_partials(partial, nblk, 2 * d, stats, st);

@@ -73,7 +73,7 @@ __global__ __launch_bounds__(PBLOCK) void bwd_params_kernel(const float* __restr
                                                             const float* __restrict__ cc,
                                                             float* __restrict__ partial,
                                                             double* __restrict__ partial_d) {
-    static_assert(D <= 16, "wider layers go through bwd_dump_kernel / a1_reduce_kernel or pointconv_wide.hip");
+    static_assert(D <= 16, "wider layers go through bwd_dump_kernel / a1_reduce_kernel or pointconv_wide_params.hip");
     constexpr int L = PC<D>::L;
     // dW2 = sum_e g_h2^T h1 -- a reduction over edges of d x d outer products: for d in {8, 16} on the MATRIX pipe (OuterAcc:
     // the wave's g_h2 / h1 rows of one edge per point through a per-wave LDS tile that IS the 16x16x4 fragment layout, four

@@ -189,7 +189,7 @@ class _State:
     small_bwd_one_launch = __import__('os').environ.get('CRFCONV_SMALL_BWD_TWO_LAUNCHES') is None
     # the backward of the CRF layers' matrices as riders of the MLP blocks' end-of-pass weight-gradient launch (defer._flush_mlp_dw)
     dw_hosts_mats = __import__('os').environ.get('CRFCONV_NO_TAIL_RIDERS') is None
-    # the d = 128 PointConv layers' parameter pass on the matrix pipe beside d = 32 / 64 (csrc/pointconv_wide.hip: a pair of wavefronts per
+    # the d = 128 PointConv layers' parameter pass on the matrix pipe beside d = 32 / 64 (csrc/pointconv_wide_params.hip: a pair of wavefronts per
     # point); CRFCONV_NO_WIDE128=1: the dump + GEMM + a1 passes for them again (A/B runs of bench.py)
     no_wide128 = __import__('os').environ.get('CRFCONV_NO_WIDE128') is not None
     # below this many rows the tiled product (gemm.hip, gemm_stats.hip) and the small-MLP nodes; swept on the step: 4096 -> 4.733 ms, 12288 (the

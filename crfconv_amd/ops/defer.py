@@ -235,7 +235,7 @@ def _flush_pc_wide():
         return
     st = stream_ptr()
     lib = _lib.load()
-    # d = 32 / 64 / 128 with K = 16: the whole pass on the matrix pipe, no per-edge tensor (csrc/pointconv_wide.hip) -- one launch for
+    # d = 32 / 64 / 128 with K = 16: the whole pass on the matrix pipe, no per-edge tensor (csrc/pointconv_wide_params.hip) -- one launch for
     # all widths; its per-workgroup slabs join the batched sums below (dW2: crfconv_reduce_jobs, dA1 | db1: crfconv_reduce_jobs_f64).
     # Every other (K, d), and d = 128 under state.no_wide128: dump + GEMM below
     mfma = [w for w in wide if lib.crfconv_pointconv_wide_params_supported(w['m_tgt'], w['K'], w['d']) == 1

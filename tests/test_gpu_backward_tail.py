@@ -1,6 +1,7 @@
-"""-m gpu: the end-of-backward parameter pass of the wide PointConv layers on the matrix pipe (csrc/pointconv_wide.hip), driven through
-crfconv_pointconv_wide_params_jobs and the slab sums directly: d = 128 (a pair of wavefronts per target point) against a float64
-restatement on the edge list, the three widths in one launch against one launch each, and a d = 128 layer against the dump path."""
+"""-m gpu: the end-of-backward parameter pass of the wide PointConv layers on the matrix pipe (csrc/pointconv_wide_params.hip; shared
+steps: csrc/pointconv_wide.hpp), driven through crfconv_pointconv_wide_params_jobs and the slab sums directly: d = 128 (a pair of
+wavefronts per target point) and d = 32 / 64 (one wavefront per point) against a float64 restatement on the edge list, the three widths
+in one launch against one launch each, and a d = 128 layer against the dump path."""
 import functools
 
 import pytest
@@ -69,21 +70,16 @@ def _run(jobs):
     _lib.call('crfconv_pointconv_wide_params_jobs', (_lib.PcWideJob * len(jobs))(*jobs), len(jobs), stream_ptr())
 
 
-@pytest.mark.parametrize('m_tgt,n_src,ragged,seed', [(1, 40, False, 3), (9, 40, False, 1), (333, 517, True, 6)],
-                         ids=['one-point', 'nine-points', 'ragged-333'])
-def test_wide_params_d128_vs_float64(m_tgt, n_src, ragged, seed):
-    """dW2 and dA1 | db1 of the d = 128 pass, summed over its slabs by the batched sum entries, against float64: one point (three pairs
-    of the workgroup idle), nine (an odd count over the pairs of a workgroup), 333 on a padded ragged table (a count no partition
-    divides: a short last workgroup).  No pre-activation of the float64 reference lies within 1e-5 of the LeakyReLU kink, so nothing is masked out."""
+def _check_vs_float64(d, m_tgt, n_src, ragged, seed):
+    """One pass of width d alone: its slabs summed by the batched sum entries, dW2 and dA1 | db1 against the float64 of _case."""
     from crfconv_amd import _lib
     from crfconv_amd.graph import stream_ptr
-    inp, dW2, dA1b1, margin = _case(128, m_tgt, n_src, ragged, seed)
+    inp, dW2, dA1b1, margin = _case(d, m_tgt, n_src, ragged, seed)
     assert margin > 1e-5, 'seed %d puts a layer-1 pre-activation %.3e from the kink' % (seed, margin)
     if ragged:
         assert bool((inp['idx'] < 0).any())
     job, pw, pa, nb, keep = _job(inp)
     _run([job])
-    d = 128
     gw = torch.empty(d * d, dtype=torch.float32, device=DEV)
     ga = torch.empty(4 * d, dtype=torch.float64, device=DEV)
     _lib.call('crfconv_reduce_jobs', (_lib.ReduceJob * 1)(_lib.ReduceJob(pw.data_ptr(), gw.data_ptr(), nb, d * d)), 1, stream_ptr())
@@ -92,6 +88,26 @@ def test_wide_params_d128_vs_float64(m_tgt, n_src, ragged, seed):
     assert bool(torch.isfinite(pw).all()) and bool(torch.isfinite(pa).all()), 'a slab was left unwritten'
     assert_close(gw.view(d, d), dW2, GRAD_TOL, 'dW2')
     assert_close(ga.view(d, 4), dA1b1, GRAD_TOL, 'dA1|db1')
+
+
+@pytest.mark.parametrize('m_tgt,n_src,ragged,seed', [(1, 40, False, 3), (9, 40, False, 1), (333, 517, True, 6)],
+                         ids=['one-point', 'nine-points', 'ragged-333'])
+def test_wide_params_d128_vs_float64(m_tgt, n_src, ragged, seed):
+    """dW2 and dA1 | db1 of the d = 128 pass, summed over its slabs by the batched sum entries, against float64: one point (three pairs
+    of the workgroup idle), nine (an odd count over the pairs of a workgroup), 333 on a padded ragged table (a count no partition
+    divides: a short last workgroup).  No pre-activation of the float64 reference lies within 1e-5 of the LeakyReLU kink, so nothing is masked out."""
+    _check_vs_float64(128, m_tgt, n_src, ragged, seed)
+
+
+@pytest.mark.parametrize('d,m_tgt,n_src,ragged,seed',
+                         [(32, 1, 40, False, 3), (64, 1, 40, False, 3), (32, 9, 40, False, 1), (64, 9, 40, False, 1),
+                          (32, 333, 517, True, 6), (64, 333, 517, True, 7)],
+                         ids=['32-one-point', '64-one-point', '32-nine-points', '64-nine-points', '32-ragged-333', '64-ragged-333'])
+def test_wide_params_d32_d64_vs_float64(d, m_tgt, n_src, ragged, seed):
+    """The same for the one-wavefront-per-point pass of d = 32 and 64: one point (seven of the eight wavefronts idle), nine (two workgroups
+    of five and four points, idle wavefronts in both), 333 on a padded ragged table (42 workgroups, a short last one).  Margins of the float64 reference from
+    the kink (asserted > 1e-5): 2.3e-3 / 3.4e-3, 1.7e-5 / 3.9e-5, 3.6e-5 (seed 6) / 1.95e-5 (seed 7; seed 6 gives 3.5e-6 at d = 64)."""
+    _check_vs_float64(d, m_tgt, n_src, ragged, seed)
 
 
 def test_wide_params_three_widths_in_one_call_match_one_call_each():

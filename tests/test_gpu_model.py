@@ -432,7 +432,8 @@ def test_pointconv_module_golden(golden, form, mode):
 def test_pointconv_widths_vs_oracle(d, deferred, mode):
     """PointConv forward, input gradient and every parameter gradient against the float32 oracle anchored on float64, all widths.
     deferred: the backward under ops.deferred_weight_grads -- the wide layers' parameter pass then runs at the end of the pass, at
-    d = 32 / 64 as ONE matrix-pipe launch without per-edge tensors (csrc/pointconv_wide.hip), at d = 128 as dump + GEMM passes.
+    d = 32 / 64 / 128 as ONE matrix-pipe launch without per-edge tensors (csrc/pointconv_wide_params.hip; d = 128 with a pair of
+    wavefronts per point, the dump + GEMM passes only under ops.state.no_wide128).
     mode 'eval': running statistics instead of batch statistics -- the entries a training step never takes (forward_kernel,
     bwd_reduce_kernel, the input gradient without its riding reduction, fold2 / fold2_bwd), at every width."""
     training = mode == 'train'
@@ -482,8 +483,8 @@ def test_pointconv_widths_vs_oracle(d, deferred, mode):
 @pytest.mark.parametrize('d', [32, 64, 128])
 @pytest.mark.parametrize('deferred', [False, True])
 def test_pointconv_wide_layers_on_a_padded_table_with_missing_edges(d, deferred):
-    """The matrix-pipe kernels of the wide layers (csrc/pointconv_wide.hip: forward statistics pass at d >= 32, parameter pass at d = 32 / 64
-    under deferred weight gradients) take one target point = sixteen table entries per MFMA tile; entries < 0 (a padded, variable-degree
+    """The matrix-pipe kernels of the wide layers (csrc/pointconv_wide_stats.hip: forward statistics pass at d >= 32; csrc/pointconv_wide_params.hip:
+    parameter pass at d = 32 / 64 / 128 under deferred weight gradients) take one target point = sixteen table entries per MFMA tile; entries < 0 (a padded, variable-degree
     table: graph.table_from_edges) must contribute nothing.  Ragged in-degrees 3 .. 16, a target count that no workgroup partition divides,
     separate source / target point sets; checked against a float64 restatement of models/point_conv_big.py:37-58 on the edge list."""
     from crfconv_amd import ops
