@@ -89,6 +89,77 @@ def test_kernel_weights_entries_check_their_arguments():
     assert [lib.crfconv_kernel_weights_partials(m) for m in (1, 4, 5)] == [8, 8, 16]
 
 
+def test_meanfield_backward_entry_checks_its_arguments():
+    """crfconv_meanfield_backward (csrc/crf_bwd.hip) refuses before any HIP call -- every call here is refused, none launches: T = 0 and
+    shapes outside the fast ones (-3), the operands of the width's dP / dQ form missing (H = 8 / 16: dP, dQ and the ticket; other widths:
+    mts and sumG), a workspace one byte short or not 16-byte aligned (-1).  The workspace grows by one dP and one dQ slab of H x H
+    floats where the edge pass gains a workgroup (Geo<H>::PPB = 64 / (H / 4) x 4 rows each)."""
+    import ctypes
+    from crfconv_amd import _lib
+    lib = _lib.load()
+    buf = ctypes.create_string_buffer(256)
+    p = (ctypes.addressof(buf) + 15) & ~15                 # never dereferenced
+
+    def bwd(H=8, K=16, k0=1, m=10, T=2, mts=p, sumG=p, dP=p, dQ=p, ticket=p, ws=p, short=0, first=p):
+        need = lib.crfconv_meanfield_backward_workspace(m, H, K)
+        return lib.crfconv_meanfield_backward(first, p, p, p, p, p, None, 1, 1, p, p, K, k0, m, H, p, p, T, p, p, mts, sumG, p, p, p, p, dP, dQ,
+                                              ws, need - short, ticket, None)
+
+    for H in (4, 8, 16, 32, 64):
+        assert bwd(H=H, T=0) == -3 and b'T=0' in lib.crfconv_last_error()
+        assert bwd(H=H, K=16, k0=0) == -3 and bwd(H=H, K=9) == -3 and bwd(H=H, K=64) == -3
+        assert bwd(H=H, K=65) == -1 and bwd(H=H, m=0) == -1
+        assert bwd(H=H, first=None) == -1 and b'null pointer' in lib.crfconv_last_error()
+        assert bwd(H=H, ws=None) == -1 and b'null pointer' in lib.crfconv_last_error()
+        inside = lib.crfconv_meanfield_backward_param_grads_inside(H) == 1
+        assert inside == (H in (8, 16))
+        for missing in ((dict(dP=None), dict(dQ=None), dict(ticket=None)) if inside else (dict(mts=None), dict(sumG=None))):
+            assert bwd(H=H, **missing) == -1 and b'required' in lib.crfconv_last_error()
+        # what the other form takes may be absent: the call gets as far as the workspace check
+        other = dict(mts=None, sumG=None) if inside else dict(dP=None, dQ=None, ticket=None)
+        assert bwd(H=H, short=1, **other) == -1 and b'workspace' in lib.crfconv_last_error()
+        assert bwd(H=H, short=1) == -1 and b'workspace' in lib.crfconv_last_error()
+        assert bwd(H=H, ws=p + 4) == -1 and b'workspace' in lib.crfconv_last_error()
+        assert bwd(H=H, ws=p + 8, K=32) == -1 and b'workspace' in lib.crfconv_last_error()
+    assert bwd(H=12) == -3 and b'H=12' in lib.crfconv_last_error()
+    for H in (8, 16, 32, 64):                               # (H = 4: a slab of 64 bytes disappears in the 256-byte rounding)
+        ppb = 64 // (H // 4) * 4
+        ws = lambda m: lib.crfconv_meanfield_backward_workspace(m, H, 16)
+        for blocks in (1, 127, 128):
+            m0 = blocks * ppb                               # even: m0 x 16 records of 8 bytes are whole 256-byte units
+            assert ws(m0) - ws(m0 - 2) == 256 and ws(m0 + 2) - ws(m0) == 256 + 2 * H * H * 4, (H, blocks)
+
+
+def test_wide_meanfield_entries_check_their_arguments():
+    """The five crfconv_wide_* entries (csrc/crf_wide.hip) refuse before any HIP call: K = 65, k0 = K, m = 0 and null pointers (-1), an
+    output aliasing its input (aggregate: out == x; scatter: out == src; similarity_bwd: w == ds) (-1), H = 64 (-3)."""
+    import ctypes
+    from crfconv_amd import _lib
+    lib = _lib.load()
+    a, b = ctypes.create_string_buffer(64), ctypes.create_string_buffer(64)
+    p, o = ctypes.addressof(a), ctypes.addressof(b)        # never dereferenced
+    entries = dict(
+        similarity=lambda K=16, k0=0, m=10, H=128, p=p, out=o: lib.crfconv_wide_similarity(p, p, K, k0, m, H, out, None),
+        aggregate=lambda K=16, k0=0, m=10, H=128, p=p, out=o: lib.crfconv_wide_aggregate(p, p, p, K, k0, m, H, out, None),
+        bwd_edge=lambda K=16, k0=0, m=10, H=128, p=p, out=o: lib.crfconv_wide_bwd_edge(p, p, p, K, k0, m, H, out, 0, None),
+        scatter=lambda K=16, k0=0, m=10, H=128, p=p, out=o: lib.crfconv_wide_scatter(p, p, p, p, K, m, H, None, 0, out, None),
+        similarity_bwd=lambda K=16, k0=0, m=10, H=128, p=p, out=o: lib.crfconv_wide_similarity_bwd(p, p, p, p, K, k0, m, H, out, o, None))
+    for name, f in entries.items():
+        for H in (128, 256):
+            assert f(H=H, K=65) == -1 and b'K=65' in lib.crfconv_last_error(), name
+            assert f(H=H, K=0) == -1 and f(H=H, m=0) == -1, name
+            if name != 'scatter':                           # (the scatter walks the reverse list: it has no k0)
+                assert f(H=H, k0=16) == -1 and b'k0=16' in lib.crfconv_last_error(), name
+                assert f(H=H, K=64, k0=64) == -1, name
+            assert f(H=H, p=None) == -1 and b'null pointer' in lib.crfconv_last_error(), name
+            assert f(H=H, out=None) == -1 and b'null pointer' in lib.crfconv_last_error(), name
+            assert f(H=H, K=64, k0=0, p=None) == -1 and b'null pointer' in lib.crfconv_last_error(), name      # the corner of what is compiled
+        for H in (64, 0, 129, 512):
+            assert f(H=H) == -3 and (b'got %d' % H) in lib.crfconv_last_error(), name
+    for name in ('aggregate', 'scatter', 'similarity_bwd'):          # out == x, out == src, w == ds
+        assert entries[name](out=p) == -1 and b'alias' in lib.crfconv_last_error(), name
+
+
 def test_state_dict_layout_matches_reference(golden):
     from crfconv_amd import models
     g = golden('g5_pointconvbig.npz')
