@@ -160,6 +160,88 @@ def test_wide_meanfield_entries_check_their_arguments():
         assert entries[name](out=p) == -1 and b'alias' in lib.crfconv_last_error(), name
 
 
+def test_pointconv_entries_check_their_arguments():
+    """The crfconv_pointconv_* entries (csrc/pointconv.hip, pointconv_bwd.hip, pointconv_fold.hip, pointconv_wide_params.hip) refuse before
+    any HIP call: K = 0 and K = 65 (-1), m = 0 (-1), a width outside {4, 8, 16, 32, 64, 128} (-3, "unsupported"), null pointers (-1), a
+    workspace that is too small (-4: forward_uv, bwd_reduce, bwd_params, bwd_input_reduce, bwd_a1, moments_packed), bwd_input_reduce
+    without a ticket, combine with one running tensor of the pair, bwd_params beyond d = 16 and with one output of the pair,
+    forward_uv_hosting at a non-hosting width; wide_params_supported / wide_params_nblk outside the matrix-pipe pass."""
+    import ctypes
+    from crfconv_amd import _lib
+    lib = _lib.load()
+    a = ctypes.create_string_buffer(64)
+    p = ctypes.addressof(a)                                  # never dereferenced
+    big = 1 << 30
+    err = lib.crfconv_last_error
+    E = dict(
+        forward=lambda K=16, m=10, d=8, p=p, o=p: lib.crfconv_pointconv_forward(p, p, p, p, K, m, d, p, p, p, 0.1, p, p, o, None),
+        forward_uv=lambda K=16, m=10, d=8, p=p, o=p, ws=big: lib.crfconv_pointconv_forward_uv(p, p, p, p, K, m, d, p, p, p, 0.1, p, p, p, p, o, p, ws, p, None),
+        bwd_input=lambda K=16, m=10, d=8, p=p, o=p: lib.crfconv_pointconv_bwd_input(p, p, p, p, p, K, m, d, p, p, p, 0.1, p, p, o, None),
+        bwd_input_reduce=lambda K=16, m=10, d=8, p=p, o=p, ws=big, tk=p, mt=10: lib.crfconv_pointconv_bwd_input_reduce(
+            p, p, p, p, p, K, m, mt, d, p, p, p, 0.1, p, p, o, p, p, p, p, p, 160.0, 1, p, p, p, p, p, p, ws, tk, None),
+        bwd_reduce=lambda K=16, m=10, d=8, p=p, o=p, ws=big: lib.crfconv_pointconv_bwd_reduce(p, p, p, p, p, K, m, d, p, p, p, 0.1, p, o, p, ws, None),
+        bwd_params=lambda K=16, m=10, d=8, p=p, o=p, ws=big, o1=p, o2=p: lib.crfconv_pointconv_bwd_params(p, p, p, p, p, K, m, d, p, p, p, 0.1, p, p, p, o1, o2,
+                                                                                                       o, ws, None),      # (o: the workspace)
+        bwd_dump=lambda K=16, m=10, d=32, p=p, o=p: lib.crfconv_pointconv_bwd_dump(p, p, p, p, p, K, m, d, p, p, p, 0.1, p, p, p, p, p, o, None),
+        moments_packed=lambda K=16, m=10, d=4, p=p, o=p, ws=big, n=160.0: lib.crfconv_pointconv_moments_packed(p, p, p, K, m, n, p, p, p, o, p, ws, None))
+    for name, f in E.items():
+        assert f(K=0) == -1 and b'K=0' in err(), name
+        assert f(K=65) == -1 and b'K=65' in err(), name
+        assert f(K=64, m=0) == -1 and b'rows=0' in err(), name
+        assert f(m=1 << 31) == -1, name
+        assert f(p=None) == -1 and b'null pointer' in err(), name
+        assert f(o=None) == -1 and b'null pointer' in err(), name
+        assert f(K=1, m=1, p=None) == -1 and f(K=64, o=None) == -1, name          # the corners of what is accepted
+        if name != 'moments_packed':                                                # (the moments have no width)
+            for d in (0, 2, 12, 24, 48, 96, 256):
+                assert f(d=d) == -3 and (b'd=%d' % d) in err(), (name, d)
+        if name != 'bwd_dump':
+            for d in ((4, 8, 16) if name == 'bwd_params' else (4, 8, 16, 32, 64, 128)):
+                assert f(d=d, K=65) == -1 and f(d=d, p=None) == -1, (name, d)
+    for name in ('forward_uv', 'bwd_reduce', 'bwd_params', 'bwd_input_reduce', 'moments_packed'):
+        for d in ((4, 16) if name in ('bwd_params', 'moments_packed') else (4, 32, 128)):      # (d = 32, 128 at K = 16: the matrix-pipe branch of forward_uv)
+            assert E[name](d=d, ws=0) == -4 and b'workspace too small' in err(), (name, d)
+            assert E[name](d=d, ws=7, m=5000) == -4, (name, d)
+    assert E['bwd_input_reduce'](tk=None) == -1 and b'null pointer' in err()
+    assert E['bwd_input_reduce'](mt=0) == -1 and b'rows=0' in err()                  # the target count is checked on its own
+    assert E['bwd_params'](d=32) == -3 and b'd <= 16' in err()
+    assert E['bwd_params'](o1=None) == -1 and E['bwd_params'](o2=None) == -1 and b'both or neither' in err()
+    assert E['moments_packed'](n=0.0) == -1 and b'n_edges' in err()
+    assert E['bwd_dump'](K=64, m=1 << 25) == -1 and b'too many edges' in err()
+
+    def combine(m=10, d=8, p=p, o=p, rm=p, rv=p):
+        return lib.crfconv_pointconv_combine(p, p, p, p, p, p, 160.0, rm, rv, 0.1, 1e-5, m, d, p, p, p, o, None)
+    assert combine(rm=None) == -1 and b'pair' in err() and combine(rv=None) == -1 and b'pair' in err()
+    assert combine(m=0) == -1 and combine(d=12) == -3 and combine(p=None) == -1 and combine(o=None) == -1 and b'null pointer' in err()
+
+    def a1(n=160, d=32, p=p, o=p, ws=big):
+        return lib.crfconv_pointconv_bwd_a1(p, p, p, n, d, 0.1, o, p, ws, None)
+    assert a1(p=None) == -1 and b'null pointer' in err()
+    assert a1(n=0) == -1 and a1(n=1 << 31) == -1 and b'n_edges' in err()
+    for d in (4, 12, 256):                                   # (d = 4 has no dump path)
+        assert a1(d=d) == -3 and (b'd=%d' % d) in err()
+    for d in (8, 16, 32, 64, 128):
+        assert a1(d=d, ws=0) == -4 and a1(d=d, ws=lib.crfconv_pointconv_bwd_a1_workspace(160, d) - 1) == -4 and b'workspace too small' in err()
+
+    def hosting(K=16, m=10, d=8, p=p, n=1):
+        return lib.crfconv_pointconv_forward_uv_hosting(p, p, p, p, K, m, d, p, p, p, 0.1, p, p, p, p, p, p, big, p, p, p, n, p, p, None)
+    for d in (4, 16, 32, 64, 128):
+        assert lib.crfconv_pointconv_forward_uv_hosts(16, d) == 0 and hosting(d=d) == -3 and b'not a hosting width' in err(), d
+    assert lib.crfconv_pointconv_forward_uv_hosts(16, 8) == 1 and lib.crfconv_pointconv_forward_uv_hosts(5, 8) == 1
+    assert hosting(K=65) == -1 and hosting(m=0) == -1 and hosting(p=None) == -1 and hosting(n=0) == -1 and b'n=0' in err()
+
+    for d in (32, 64, 128):
+        assert lib.crfconv_pointconv_wide_params_supported(640, 16, d) == 1 and lib.crfconv_pointconv_wide_params_nblk(640, d) > 0
+        for K in (1, 4, 15, 17, 32, 64):
+            assert lib.crfconv_pointconv_wide_params_supported(640, K, d) == 0, (K, d)
+        assert lib.crfconv_pointconv_wide_params_supported(0, 16, d) == 0 and lib.crfconv_pointconv_wide_params_supported(1 << 27, 16, d) == 0
+        assert lib.crfconv_pointconv_wide_params_nblk(0, d) == 0 and lib.crfconv_pointconv_wide_params_nblk(-5, d) == 0
+    for d in (4, 8, 16, 48, 256):
+        assert lib.crfconv_pointconv_wide_params_supported(640, 16, d) == 0, d
+    job = _lib.PcWideJob(p, p, p, p, p, 5, 640, 32, p, p, p, 0.1, p, p, p, p, p)        # K = 5: the jobs entry refuses what `supported` does
+    assert lib.crfconv_pointconv_wide_params_jobs((_lib.PcWideJob * 1)(job), 1, None) == -3 and b'K=5' in err()
+
+
 def test_state_dict_layout_matches_reference(golden):
     from crfconv_amd import models
     g = golden('g5_pointconvbig.npz')
