@@ -242,6 +242,130 @@ def test_pointconv_entries_check_their_arguments():
     assert lib.crfconv_pointconv_wide_params_jobs((_lib.PcWideJob * 1)(job), 1, None) == -3 and b'K=5' in err()
 
 
+def test_streaming_mlp_entries_check_their_arguments():
+    """The entries of the row-streaming dense stack (csrc/linear.hip, mlp_bwd.hip, bn_records.hip, wgrad.hip) refuse before any HIP call
+    -- every call here is refused, none launches: null pointers (-1), M <= 0 (-1; the fused backward answers through its `supported`
+    query: -3), a width whose weight slab does not fit LDS (-3), a split that is not a multiple of 4 or lies outside (0, Ci) (-1), a
+    dropout probability outside [0, 1) (-1), Co % 4 != 0 where the entry needs it (-3), a workspace one byte short (-4), more than BA_MAX = 4
+    jobs (-1).  The `_supported` and `_workspace` queries answer 0 for non-positive shapes."""
+    import ctypes
+    from crfconv_amd import _lib
+    lib = _lib.load()
+    a = ctypes.create_string_buffer(1024)
+    p = (ctypes.addressof(a) + 255) & ~255                   # never dereferenced; 256-byte aligned for the partial pass
+    err = lib.crfconv_last_error
+    big = 1 << 40
+
+    # ---- the forward entries: (X, W, Y) null, M, the slab, the split, p, Co % 4
+    def fwd(M=10, Ci=16, Co=16, x=p, w=p, y=p):
+        return lib.crfconv_linear_forward(x, w, p, M, Ci, Co, 0, y, p, None)
+
+    def drop(M=10, Ci=16, Co=16, x=p, w=p, y=p, prob=0.5, ctr=p):
+        return lib.crfconv_linear_forward_dropout(x, w, M, Ci, Co, 1, prob, 7, ctr, y, None)
+
+    def cat(M=10, Ci=16, Co=16, x=p, w=p, y=p, xb=p, split=8):
+        return lib.crfconv_linear_forward_cat(x, xb, split, w, p, M, Ci, Co, y, p, None)
+
+    def bna(M=10, Ci=16, Co=16, x=p, w=p, y=p, xb=None, split=0, coef=p):
+        return lib.crfconv_linear_bn_act(x, xb, split, w, p, coef, p, 0.1, M, Ci, Co, y, None)
+    for name, f in (('forward', fwd), ('dropout', drop), ('cat', cat), ('bn_act', bna)):
+        for missing in (dict(x=None), dict(w=None), dict(y=None)):
+            assert f(**missing) == -1 and b'null pointer' in err(), (name, missing)
+        for M in (0, -3):
+            assert f(M=M) == -1 and b'M must be positive' in err(), (name, M)
+        for Ci, Co in ((1012, 16), (2048, 64), (0, 16), (16, 0), (-4, 16)):        # (1008 inputs are the last that fit beside 16 outputs)
+            assert f(Ci=Ci, Co=Co) == -3 and b'does not fit LDS' in err(), (name, Ci, Co)
+        assert f(Ci=1008, Co=16, x=None) == -1 and f(Ci=512, Co=1024, y=None) == -1 and b'null pointer' in err(), name
+    assert drop(ctr=None) == -1 and b'null pointer' in err()
+    for prob in (1.0, 1.5, -0.1):
+        assert drop(prob=prob) == -1 and b'outside [0, 1)' in err(), prob
+    assert cat(xb=None) == -1 and b'null pointer' in err()
+    for Ci, split in ((16, 0), (16, 16), (16, 20), (16, -4), (16, 6), (30, 8), (18, 9)):
+        assert cat(Ci=Ci, split=split) == -1 and b'two-operand form' in err(), (Ci, split)
+        assert bna(Ci=Ci, split=split, xb=p) == -1 and b'two-operand form' in err(), (Ci, split)
+    assert bna(coef=None) == -1 and b'null pointer' in err()
+    for Co in (13, 18, 2):
+        assert bna(Co=Co) == -3 and b'multiple of 4' in err(), Co
+    for Ci, Co in ((0, 16), (16, 0), (-1, 16), (16, -1), (1012, 16)):
+        assert lib.crfconv_linear_forward_supported(Ci, Co) == 0, (Ci, Co)
+    assert lib.crfconv_linear_forward_supported(1008, 16) == 1 and lib.crfconv_linear_forward_supported(1, 1) == 1
+
+    # ---- the fused backward: four entries over one implementation
+    def ws_of(M, Ci, Co):
+        return lib.crfconv_mlp_backward_workspace(M, Ci, Co)
+
+    def plain(M=10, Ci=16, Co=16, q=p, dx=p, ws=p, short=0, **_):
+        return lib.crfconv_mlp_backward(q, q, q, q, q, 0.1, M, Ci, Co, dx, p, p, p, ws, ws_of(M, Ci, Co) - short, p, None)
+
+    def add(M=10, Ci=16, Co=16, q=p, dx=p, ws=p, short=0, extra=p):
+        return lib.crfconv_mlp_backward_add(q, q, q, q, q, 0.1, M, Ci, Co, extra, dx, p, p, p, ws, ws_of(M, Ci, Co) - short, p, None)
+
+    def masked(M=10, Ci=16, Co=16, q=p, dx=p, ws=p, short=0, extra=p):
+        return lib.crfconv_mlp_backward_add_mask(q, q, q, q, q, 0.1, M, Ci, Co, extra, 0.1, dx, p, p, p, ws, ws_of(M, Ci, Co) - short, p, None)
+
+    def cat_bwd(M=10, Ci=16, Co=16, q=p, dx=p, ws=p, short=0, xb=p, split=8, dxb=p):
+        return lib.crfconv_mlp_backward_cat(q, q, q, xb, split, q, q, 0.1, M, Ci, Co, dx, dxb, p, p, p, ws, ws_of(M, Ci, Co) - short, p, None)
+    for name, f in (('plain', plain), ('add', add), ('masked', masked), ('cat', cat_bwd)):
+        assert f(q=None) == -1 and f(ws=None) == -1 and b'null pointer' in err(), name
+        for M in (0, -2):
+            assert f(M=M) == -3 and b'not supported' in err(), (name, M)
+        for Ci, Co in ((16, 18), (16, 2)):                                      # Co % 4: the masked form says so itself
+            assert f(Ci=Ci, Co=Co) == (-1 if name == 'masked' else -3), (name, Ci, Co)
+            assert (b'multiples of 4' if name == 'masked' else b'not supported') in err(), (name, Ci, Co)
+        for Ci, Co in ((16, 0), (16, 1028), (16, 784), (1028, 16)):      # Co < 4, the ranges, the dX slab of Co inputs (768 fit)
+            assert f(Ci=Ci, Co=Co) == -3 and b'not supported' in err(), (name, Ci, Co)
+        assert f(short=1) == -4 and b'workspace too small' in err(), name
+        assert f(Ci=1008, Co=16, short=1) == -4 and f(Ci=16, Co=768, short=1) == -4, name                 # the corners of what is accepted
+    assert add(dx=None) == -1 and b'dX_add without dX' in err()
+    assert masked(dx=None) == -1 and b'masked form' in err()
+    for Ci in (6, 18):
+        assert masked(Ci=Ci) == -1 and b'masked form' in err(), Ci
+    assert cat_bwd(xb=None) == -1 and b'two-operand form' in err()
+    assert cat_bwd(dxb=None) == -1 and cat_bwd(dx=None) == -1 and b'both or neither' in err()
+    for Ci, split in ((16, 0), (16, 16), (16, 20), (16, 6), (30, 8)):
+        assert cat_bwd(Ci=Ci, split=split) == -1 and b'two-operand form' in err(), (Ci, split)
+    for M, Ci, Co in ((0, 16, 16), (-1, 16, 16), (10, 0, 16), (10, 16, 0), (10, -8, 16), (10, 16, -8)):
+        assert lib.crfconv_mlp_backward_supported(M, Ci, Co) == 0 and lib.crfconv_mlp_backward_workspace(M, Ci, Co) == 0, (M, Ci, Co)
+        assert lib.crfconv_linear_wgrad_workspace(M, Co, Ci) == 0 and lib.crfconv_linear_wgrad_nblk(M, Co, Ci) == 0, (M, Ci, Co)
+    assert lib.crfconv_mlp_backward_supported(10, 16, 768) == 1 and lib.crfconv_mlp_backward_supported(10, 1008, 16) == 1
+    assert lib.crfconv_mlp_backward_supported(10, 6, 16) == 1 and ws_of(10, 16, 16) > 0
+
+    # ---- BatchNorm from the records
+    def coef(M=10, C=16, q=p, out=p):
+        return lib.crfconv_bn_coef_from_records(q, M, C, q, q, p, p, 0.1, 1e-5, out, None)
+
+    def apply(M=10, C=16, q=p, out=p, nrec=1):
+        return lib.crfconv_bn_apply_from_records(q, nrec, q, M, C, q, q, p, p, 0.1, 1e-5, None, 0.1, out, out, None)
+    for name, f in (('coef', coef), ('apply', apply)):
+        assert f(q=None) == -1 and f(out=None) == -1 and b'null pointer' in err(), name
+        for bad in (dict(M=0), dict(M=-1), dict(C=0), dict(C=-4)):
+            assert f(**bad) == -1 and b'bad shape' in err(), (name, bad)
+    for bad in (dict(C=2), dict(C=18), dict(nrec=0), dict(nrec=-1), dict(nrec=1 << 31)):
+        assert apply(**bad) == -1 and b'bad shape' in err(), bad
+
+    def jobs(n, M=10, C=16, q=p, nrec=1, arr=True):
+        rec = (_lib.BnApplyJob * max(n, 1))(*[_lib.BnApplyJob(q, nrec, q, M, C, q, q, p, p, 0.1, 1e-5, None, 0.1, q, q) for _ in range(max(n, 1))])
+        return lib.crfconv_bn_apply_from_records_jobs(rec if arr else None, n, None)
+    for n in (0, -1, 5, 64):
+        assert jobs(n) == -1 and (b'1 .. 4 jobs (got %d)' % n) in err(), n
+    assert jobs(1, arr=False) == -1 and b'1 .. 4 jobs' in err()
+    for n in (1, 4):
+        assert jobs(n, q=None) == -1 and b'job 0: null pointer' in err(), n
+        for bad in (dict(M=0), dict(C=0), dict(C=6), dict(nrec=0), dict(nrec=1 << 31)):
+            assert jobs(n, **bad) == -1 and b'job 0: bad shape' in err(), (n, bad)
+
+    # ---- the partial pass of the plain weight gradient
+    def partial(M=10, Co=16, Ci=16, g=p, ws=p, short=0, nblk=p):
+        return lib.crfconv_linear_wgrad_partial(g, g, M, Co, Ci, 1, ws, lib.crfconv_linear_wgrad_workspace(M, Co, Ci) - short if M > 0 and Co > 0 and Ci > 0 else big,
+                                                nblk, None)
+    assert partial(g=None) == -1 and partial(ws=None) == -1 and partial(nblk=None) == -1 and b'null pointer' in err()
+    for bad in (dict(M=0), dict(M=-1), dict(Co=0), dict(Ci=0), dict(Co=4097), dict(Ci=4097)):
+        assert partial(**bad) == -1 and b'bad shape' in err(), bad
+    assert partial(ws=p + 16) == -1 and b'256-byte aligned' in err()
+    assert partial(short=1) == -4 and b'workspace too small' in err()
+    assert partial(Co=4096, Ci=4096, short=1) == -4 and partial(Co=5, Ci=7, short=1) == -4
+
+
 def test_state_dict_layout_matches_reference(golden):
     from crfconv_amd import models
     g = golden('g5_pointconvbig.npz')
