@@ -16,80 +16,11 @@
 // bitwise deterministic, capturable).  Both go through aug_rotate_scale, singly rounded operations (no FMA contraction): a flipped
 // cloud's minimum is then exactly 0 without noise.  A lane owns four consecutive points: 3 x 16-byte loads of pos (6 of x at C = 6)
 // when the rows are 16-byte aligned (N % 4 == 0), per-point dwords otherwise.
-#include <cmath>
-
-#include "common.hpp"
+#include "augment_common.hpp"
 
 namespace crf {
 
 constexpr int AUG_NT = 256, AUG_PPT = 4, AUG_PPB = AUG_NT * AUG_PPT;
-constexpr unsigned long long AUG_DOMAIN = 0xA0761D6478BD642Full;       // separates these draws from the subsets' / dropout's
-constexpr int AUG_SLOT_NOISE = 8;                                      // slots 0 .. 7 per cloud, 8 + 3 point + axis per point
-
-__device__ __forceinline__ unsigned long long aug_hash(unsigned long long seed, unsigned long long ctr, unsigned long long cloud,
-                                                       unsigned long long slot) {
-    unsigned long long z = (seed ^ AUG_DOMAIN) + 0x9E3779B97F4A7C15ull * (ctr + 1ull) + cloud * 0xC2B2AE3D27D4EB4Full
-                           + slot * 0xD1B54A32D192ED03ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-__device__ __forceinline__ float aug_u24(unsigned long long h) { return (float)(unsigned)(h >> 40) * 5.9604644775390625e-8f; }   // [0, 1)
-
-struct AugParams {
-    float c, s, sc0, sc1, sc2;
-    int flip, keep;
-};
-
-// What cloud b applies: the draws, or params_in [B, 8] when given; a disabled step is the identity.
-__device__ __forceinline__ AugParams aug_cloud_params(const crf_augment_spec& sp, unsigned long long seed, unsigned long long ctr, int b,
-                                                     const float* __restrict__ params_in) {
-    AugParams P{1.f, 0.f, 1.f, 1.f, 1.f, 0, 1};
-    if (params_in != nullptr) {
-        const float* q = params_in + (size_t)b * 8;
-        if (sp.rotate_axis >= 0) { P.c = q[0]; P.s = q[1]; }
-        if (sp.scale) { P.sc0 = q[2]; P.sc1 = q[3]; P.sc2 = q[4]; }
-        P.flip = (int)q[5] & sp.flip_axes;
-        if (sp.drop) P.keep = q[6] != 0.f ? 1 : 0;
-        return P;
-    }
-    if (sp.rotate_axis >= 0) {            // double: the host twin's float64 cos / sin give the same float32 (to an ulp)
-        const double u = (double)aug_u24(aug_hash(seed, ctr, b, 0));
-        const double deg = (double)sp.deg_lo + ((double)sp.deg_hi - (double)sp.deg_lo) * u;
-        const double rad = deg * 0.017453292519943295;
-        P.c = (float)cos(rad);
-        P.s = (float)sin(rad);
-    }
-    if (sp.scale) {
-        P.sc0 = add_rn(sp.scale_lo, mul_rn(aug_u24(aug_hash(seed, ctr, b, 1)), sp.scale_span));
-        P.sc1 = add_rn(sp.scale_lo, mul_rn(aug_u24(aug_hash(seed, ctr, b, 2)), sp.scale_span));
-        P.sc2 = add_rn(sp.scale_lo, mul_rn(aug_u24(aug_hash(seed, ctr, b, 3)), sp.scale_span));
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-        if (((sp.flip_axes >> i) & 1) && aug_u24(aug_hash(seed, ctr, b, 4 + i)) < 0.5f) P.flip |= 1 << i;
-    if (sp.drop) P.keep = aug_u24(aug_hash(seed, ctr, b, 7)) < sp.drop_p ? 0 : 1;
-    return P;
-}
-
-// pos @ M (PyG's matrix about `axis`: x_a' = c x_a - s x_b, x_b' = s x_a + c x_b with (a, b) = (axis + 1, axis + 2) mod 3), then the
-// scales.  ONE instruction sequence for both launches (singly rounded: the max pass and the apply pass agree bit for bit).
-__device__ __forceinline__ void aug_rotate_scale(const crf_augment_spec& sp, const AugParams& P, float& x, float& y, float& z) {
-    const int ax = sp.rotate_axis;
-    if (ax >= 0) {
-        const float xa = ax == 2 ? x : (ax == 0 ? y : z), xb = ax == 2 ? y : (ax == 0 ? z : x);
-        const float ra = sub_rn(mul_rn(P.c, xa), mul_rn(P.s, xb)), rb = add_rn(mul_rn(P.s, xa), mul_rn(P.c, xb));
-        const float nx = ax == 2 ? ra : (ax == 1 ? rb : x);
-        const float ny = ax == 2 ? rb : (ax == 0 ? ra : y);
-        const float nz = ax == 0 ? rb : (ax == 1 ? ra : z);
-        x = nx; y = ny; z = nz;
-    }
-    if (sp.scale) {
-        x = mul_rn(x, P.sc0);
-        y = mul_rn(y, P.sc1);
-        z = mul_rn(z, P.sc2);
-    }
-}
 
 // the lane's points [4 g, 4 g + 4) of cloud b (n of them valid): 12 floats of a [.., 3] row block, vector loads when aligned
 __device__ __forceinline__ void aug_load3(const float* __restrict__ base, int n, bool vec, float (&v)[12]) {
@@ -202,12 +133,8 @@ __global__ __launch_bounds__(AUG_NT) void aug_apply_kernel(float* __restrict__ p
     if (sp.noise) {
         if (noise_in == nullptr) {
 #pragma unroll
-            for (int k = 0; k < 12; ++k) {           // Box-Muller: u1 in (0, 1], u2 in [0, 1)
-                const unsigned long long h = aug_hash(seed, ctr, b, AUG_SLOT_NOISE + 3ull * (unsigned long long)i0 + k);
-                const float u1 = (float)((unsigned)(h >> 40) + 1u) * 5.9604644775390625e-8f;
-                const float u2 = (float)((unsigned)(h >> 8) & 0xFFFFFFu) * 5.9604644775390625e-8f;
-                nz[k] = sp.sigma * (sqrtf(-2.f * __logf(u1)) * __cosf(6.283185307179586f * u2));
-            }
+            for (int k = 0; k < 12; ++k)             // Box-Muller of (cloud, point, axis): augment_common.hpp
+                nz[k] = aug_noise_draw(sp.sigma, seed, ctr, b, AUG_SLOT_NOISE + 3ull * (unsigned long long)i0 + k);
         }
     }
 #pragma unroll
@@ -218,9 +145,9 @@ __global__ __launch_bounds__(AUG_NT) void aug_apply_kernel(float* __restrict__ p
         if (P.flip & 2) py = sub_rn(cm1, py);
         if (P.flip & 4) pz = sub_rn(cm2, pz);
         if (sp.noise) {
-            px = add_rn(px, fminf(fmaxf(nz[3 * j], -sp.clip), sp.clip));
-            py = add_rn(py, fminf(fmaxf(nz[3 * j + 1], -sp.clip), sp.clip));
-            pz = add_rn(pz, fminf(fmaxf(nz[3 * j + 2], -sp.clip), sp.clip));
+            px = aug_add_noise(px, nz[3 * j], sp.clip);
+            py = aug_add_noise(py, nz[3 * j + 1], sp.clip);
+            pz = aug_add_noise(pz, nz[3 * j + 2], sp.clip);
         }
         v[3 * j] = px; v[3 * j + 1] = py; v[3 * j + 2] = pz;
     }

@@ -15,6 +15,10 @@ torch's or Python's ``random`` draws: every parameter is a counter-based hash of
 laws is the reference's semantics.  Supported: any subsequence of RandomRotate -> RandomScaleAnisotropic -> RandomSymmetry ->
 RandomNoise -> DropFeature('rgb'), ending with an optional AddFeatsByKeys of 'pos' / 'rgb'; anything else raises
 NotImplementedError.  Importing this module, building a ``Compose`` and ``Compose.draws`` need neither a GPU nor the library.
+
+Ragged batches (pos [N, 3] + ptr [S + 1], the sparse networks' input: ShapeNet-Part with normals) go through ``SegmentCompose``
+further down: ``FixedPoints``, ``Center`` and ``NormalizeScale`` (torch_geometric's, as trainval.py:10 imports them) ahead of the same
+augmentation, with ``data.norm`` carried along; csrc/augment_segments.hip.  ``Compose`` itself still refuses ``data.norm``.
 """
 import ctypes
 
@@ -315,3 +319,288 @@ class Compose:
         self._counter_value = int(sd['counter'])
         if self._counter is not None:
             self._counter.fill_(self._counter_value)
+
+
+# ------------------------------------------------------------------------------------------------ ragged batches (pos [N, 3] + ptr)
+_FXP_DOMAIN = 0x8CB92BA72F3D8DD7          # csrc/augment_segments.hip: FXP_DOMAIN
+
+
+class _SegmentTransform:
+    """A lone ragged-batch transform applies as a SegmentCompose of one."""
+
+    def __call__(self, data):
+        if getattr(self, '_compose', None) is None:
+            self._compose = SegmentCompose([self])
+        return self._compose(data)
+
+
+class Center(_SegmentTransform):
+    """torch_geometric.transforms.Center: pos <- pos - mean(pos), per cloud.  The mean is summed in float64 and rounded once."""
+
+    def __repr__(self):
+        return 'Center()'
+
+
+class NormalizeScale(_SegmentTransform):
+    """torch_geometric.transforms.NormalizeScale: centres the cloud, then pos <- pos * (1 / max |pos|) * 0.999999, into (-1, 1).
+    A cloud whose centred maximum is 0 (one point, or coincident points) comes out all zero; PyG writes NaN there."""
+
+    def __repr__(self):
+        return 'NormalizeScale()'
+
+
+class FixedPoints(_SegmentTransform):
+    """torch_geometric.transforms.FixedPoints per cloud: `num` rows of every cloud, drawn with replacement (replace=True); without
+    (replace=False: min(num, n) rows, in ascending row order); or, with allow_duplicates=True, floor(num / n) whole copies of the cloud
+    and a subset for the remainder.  The picks are a counter-based hash of (seed, counter, cloud, index), not torch's draws; any draw
+    from the stated law is the reference's semantics.  An EMPTY cloud has no row to pick: its picks are -1 and the gather clamps them."""
+
+    def __init__(self, num, replace=True, allow_duplicates=False):
+        if int(num) < 1:
+            raise ValueError('FixedPoints: num must be >= 1, got %r' % (num,))
+        self.num, self.replace, self.allow_duplicates = int(num), bool(replace), bool(allow_duplicates)
+
+    def __repr__(self):
+        return 'FixedPoints(%d, replace=%s, allow_duplicates=%s)' % (self.num, self.replace, self.allow_duplicates)
+
+    @property
+    def mode(self):
+        """The kernel's mode: 0 replace, 1 without replacement, 2 allow_duplicates (replace wins, as in PyG)."""
+        return 0 if self.replace else (2 if self.allow_duplicates else 1)
+
+    def counts(self, sizes):
+        """Picks per cloud for the cloud sizes `sizes`: num, or min(num, n) without replacement."""
+        sizes = np.asarray(sizes, dtype=np.int64)
+        return np.minimum(self.num, sizes) if self.mode == 1 else np.full(sizes.shape, self.num, np.int64)
+
+    def draws(self, seed, counter, sizes):
+        """Host twin of crfconv_fixed_points for the call with (seed, counter) on clouds of `sizes` rows, numpy, exact: dict of
+        index [M] (GLOBAL rows, cloud after cloud; -1 for an empty cloud) and out_ptr [S + 1]."""
+        sizes = np.asarray(sizes, dtype=np.int64)
+        starts = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        out_ptr = np.concatenate([[0], np.cumsum(self.counts(sizes))]).astype(np.int64)
+        index = np.full(int(out_ptr[-1]), -1, np.int64)
+        mode = self.mode
+        for b, n in enumerate(sizes.tolist()):
+            m = int(out_ptr[b + 1] - out_ptr[b])
+            if m == 0 or n == 0:
+                continue
+            key = (((int(seed) & _M64) ^ _FXP_DOMAIN) + 0x9E3779B97F4A7C15 * (int(counter) + 1) + b * 0xC2B2AE3D27D4EB4F) & _M64
+
+            def h(count):
+                with np.errstate(over='ignore'):
+                    return _splitmix(np.uint64(key) + np.arange(count, dtype=np.uint64) * np.uint64(0xD1B54A32D192ED03))
+            if mode == 0:
+                pick = (((h(m) >> np.uint64(32)) * np.uint64(n)) >> np.uint64(32)).astype(np.int64)
+            else:
+                whole = (m // n) * n if mode == 2 else 0
+                r = min(m - whole, n)
+                subset = np.sort(np.argsort(h(n), kind='stable')[:r]).astype(np.int64)      # the r smallest keys, ties to the lower row
+                pick = np.concatenate([np.arange(whole, dtype=np.int64) % n, subset])
+            index[out_ptr[b]:out_ptr[b] + len(pick)] = starts[b] + pick
+        return {'index': index, 'out_ptr': out_ptr}
+
+
+_SEG_ORDER = (FixedPoints, Center, NormalizeScale) + _ORDER
+_ROW_KEYS = ('pos', 'norm', 'rgb', 'x', 'y')           # the per-row attributes FixedPoints gathers; anything else on the data stays as it is
+_SEG_SLOTS = ('fixed', 'center', 'normalize', 'rotate', 'scale', 'symmetry', 'noise', 'drop', 'add')
+
+
+class SegmentCompose(Compose):
+    """The chain ahead of the sparse networks on a RAGGED batch (pos [N, 3] + ptr [S + 1]; csrc/augment_segments.hip), validated and
+    lowered to a constant number of launches whatever the number of clouds: crfconv_fixed_points + one gather of every row attribute
+    (with FixedPoints), then ONE crfconv_augment_segments.  Supported: any subsequence of FixedPoints -> Center | NormalizeScale ->
+    RandomRotate -> RandomScaleAnisotropic -> RandomSymmetry -> RandomNoise -> DropFeature('rgb') -> AddFeatsByKeys of 'pos' / 'rgb'
+    or 'pos' / 'norm'; anything else raises NotImplementedError.
+
+    data.norm rides along (the library's own semantics; parity with the third-party transforms is unpinned, as for the rest):
+    a rotation rotates it, an anisotropic scale s divides it by s and renormalises it to unit length (a zero normal stays zero), a
+    flip of axis i negates component i; Center, NormalizeScale and RandomNoise leave it alone.  Cloud b applies the parameters
+    ``draws(seed, counter, S)`` predicts for row b, whatever the other clouds hold.
+
+    Seed, device counter, ``state_dict()`` / ``load_state_dict()`` as on ``Compose``; one counter step per call serves the picks and
+    the augmentation (two hash domains)."""
+
+    def __init__(self, transforms, generator=None):
+        flat = []
+        for t in transforms:
+            flat.extend(t.transforms if isinstance(t, Compose) else [t])
+        self.transforms = flat
+        for slot in _SEG_SLOTS:
+            setattr(self, slot, None)
+        last = -1
+        for t in flat:
+            k = next((i for i, cls in enumerate(_SEG_ORDER) if type(t) is cls), None)
+            if k is None:
+                raise NotImplementedError('SegmentCompose: %r is not supported (supported: %s)'
+                                          % (t, ', '.join(c.__name__ for c in _SEG_ORDER)))
+            if k <= last:
+                raise NotImplementedError('SegmentCompose: %r out of order; supported is a subsequence of %s'
+                                          % (t, ' -> '.join(c.__name__ for c in _SEG_ORDER)))
+            last = k
+            setattr(self, _SEG_SLOTS[k], t)
+        if self.drop is not None and self.drop.feature_name != 'rgb':
+            raise NotImplementedError('SegmentCompose: %r: only the rgb feature can be dropped' % (self.drop,))
+        self.add_rgb = self.add_norm = False
+        if self.add is not None:
+            a = self.add
+            for name in a.feat_names:
+                if name not in ('pos', 'rgb', 'norm'):
+                    raise NotImplementedError('SegmentCompose: %r: feature %r (only pos, rgb and norm are supported)' % (a, name))
+            added = [n for n, on in zip(a.feat_names, a.list_add_to_x) if on]
+            if added not in (['pos'], ['pos', 'rgb'], ['pos', 'norm']):
+                raise NotImplementedError('SegmentCompose: %r: x must be [pos], [pos, rgb] or [pos, norm], got %s' % (a, added))
+            if any(d for n, d in zip(a.feat_names, a.delete_feats) if n == 'pos'):
+                raise NotImplementedError('SegmentCompose: %r: pos cannot be deleted' % (a,))
+            self.add_rgb, self.add_norm = added == ['pos', 'rgb'], added == ['pos', 'norm']
+        if generator is None:
+            from .data import _private_generator
+            generator = _private_generator()
+        self.seed = int(torch.randint(0, 2 ** 62, (1,), generator=generator, dtype=torch.int64, device=generator.device).item())
+        self._counter = None
+        self._counter_value = 0
+        self._out_ptr = {}                     # (S, device) -> arange(S + 1) * num
+
+    def __repr__(self):
+        return 'SegmentCompose(%s)' % ', '.join(repr(t) for t in self.transforms)
+
+    def _spec(self):
+        from ._lib import AugmentSegmentsSpec
+        d, s = Compose._spec(self), AugmentSegmentsSpec()
+        for name, _ in d._fields_:
+            setattr(s, name, getattr(d, name))
+        s.center = 1 if (self.center is not None or self.normalize is not None) else 0      # NormalizeScale centres first
+        s.normalize = 0 if self.normalize is None else 1
+        s.x_norm = 1 if self.add_norm else 0
+        return s
+
+    def _has_point_step(self):
+        return any(getattr(self, slot) is not None for slot in _SEG_SLOTS[1:])
+
+    # ---- device
+    def apply_segments(self, pos, norm, x, ptr, seed, counter, params_out=None, stats_out=None, params_in=None, noise_in=None):
+        """The chain without FixedPoints on the S clouds of ptr [S + 1] (int64 device tensor), in place: pos [N, 3], norm [N, 3] or
+        None, x [N, C] or None (C = 3 [pos]; C = 6 [pos, rgb], or [pos, norm] when AddFeatsByKeys names 'norm'), contiguous float32
+        device tensors.  `counter`: one-element int64 device tensor the kernel reads (not advanced here).  params_out [S, 8] and
+        stats_out [S, 4] (cx, cy, cz, k) record what was applied; params_in [S, 8] / noise_in [N, 3] replace the draws (tests).
+        One launch, no workspace, no host synchronisation: capturable."""
+        from . import _lib
+        from .graph import ptr as p_, require_gpu, stream_ptr
+        if pos.dim() != 2 or pos.shape[-1] != 3:
+            raise ValueError('SegmentCompose.apply_segments: pos must be [N, 3], got %s' % (tuple(pos.shape),))
+        require_gpu(pos)
+        N = pos.shape[0]
+        S = ptr.numel() - 1
+        C = 0 if x is None else x.shape[-1]
+
+        def ok(t, shape):
+            return (t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape))
+        if not ok(pos, (N, 3)) or not ok(norm, (N, 3)) or not ok(x, (N, C)) or not ok(params_out, (S, 8)) \
+                or not ok(stats_out, (S, 4)) or not ok(params_in, (S, 8)) or not ok(noise_in, (N, 3)):
+            raise ValueError('SegmentCompose.apply_segments: pos / norm / noise [N, 3], x [N, C], params [S, 8], stats [S, 4] must be '
+                             'contiguous float32 device tensors')
+        if not (ptr.is_cuda and ptr.dtype == torch.int64 and ptr.is_contiguous() and ptr.dim() == 1 and S >= 0):
+            raise ValueError('SegmentCompose.apply_segments: ptr must be a contiguous int64 device tensor [S + 1]')
+        if not (counter.is_cuda and counter.dtype == torch.int64):
+            raise ValueError('SegmentCompose.apply_segments: counter must be an int64 device tensor')
+        _lib.call('crfconv_augment_segments', p_(pos), p_(norm), p_(x), N, C, p_(ptr), S, ctypes.byref(self._spec()),
+                  int(seed) & _M64, p_(counter), p_(params_in), p_(noise_in), p_(params_out), p_(stats_out), stream_ptr())
+        return pos, norm, x
+
+    def pick(self, ptr, out_ptr, n_rows, n_picks, seed, counter):
+        """crfconv_fixed_points: index [n_picks] int64 GLOBAL rows for the clouds of ptr and the slots of out_ptr (device int64
+        [S + 1]); host twin ``FixedPoints.draws``.  One launch, nothing read back."""
+        from . import _lib
+        from .graph import ptr as p_, stream_ptr
+        index = torch.empty(int(n_picks), dtype=torch.int64, device=ptr.device)
+        _lib.call('crfconv_fixed_points', p_(ptr), p_(out_ptr), ptr.numel() - 1, int(n_rows), int(n_picks), self.fixed.mode,
+                  int(seed) & _M64, p_(counter), p_(index), stream_ptr())
+        return index
+
+    def __call__(self, data, params_out=None, stats_out=None):
+        """A ragged ``Data``: pos [N, 3], optional norm / rgb [N, 3] and y [N], and ptr [S + 1] (or a SORTED batch [N], which costs
+        one host read for S).  Returned transformed: without FixedPoints in place, as the reference's transforms do; with it,
+        pos, norm, rgb, x and y (those present) are gathered by the picks, data.ptr / data.batch are rebuilt and every other attribute
+        (category, ..) is left as it is; a batch without rows is refused.  With ptr given and FixedPoints absent or in
+        the replace / allow_duplicates mode nothing is read back and the call can be captured; replace=False,
+        allow_duplicates=False sizes its output by min(num, n): it takes the cloud sizes from data.sizes (host) when present,
+        else makes ONE host read of ptr."""
+        from . import _lib
+        from .data import pick_rows
+        from .graph import ptr as p_, require_gpu, stream_ptr, to_device
+        pos = data.pos
+        require_gpu(pos)
+        if pos.dim() != 2 or pos.shape[-1] != 3:
+            raise ValueError('SegmentCompose: data.pos must be [N, 3], got %s' % (tuple(pos.shape),))
+        if pos.dtype != torch.float32 or not pos.is_contiguous():
+            pos = data.pos = pos.float().contiguous()
+        if self.add_rgb and getattr(data, 'rgb', None) is None:
+            raise ValueError('SegmentCompose: %r needs data.rgb' % (self.add,))
+        if self.add_norm and getattr(data, 'norm', None) is None:
+            raise ValueError('SegmentCompose: %r needs data.norm' % (self.add,))
+        if self.add is not None and getattr(data, 'x', None) is not None:
+            raise NotImplementedError('SegmentCompose: %r onto an existing data.x is not supported' % (self.add,))
+        N, dev = pos.shape[0], pos.device
+        seg = getattr(data, 'ptr', None)
+        if seg is None:
+            batch = getattr(data, 'batch', None)
+            if batch is None:
+                raise ValueError('SegmentCompose: data needs ptr [S + 1] or a sorted batch [N]')
+            S = int(batch[-1].item()) + 1 if N else 0                                        # (the host read of the batch form)
+            seg = torch.searchsorted(batch.contiguous(), torch.arange(S + 1, device=dev, dtype=batch.dtype)).to(torch.int64)
+        seg = seg.to(torch.int64).contiguous()
+        S = seg.numel() - 1
+        counter = self._device_counter(dev)
+        _lib.call('crfconv_add_i64', p_(counter), 1, 1, stream_ptr())
+        if self.fixed is not None:
+            if N == 0:
+                raise ValueError('SegmentCompose: %r on a batch without rows' % (self.fixed,))
+            num = self.fixed.num
+            if self.fixed.mode == 1:
+                sizes = getattr(data, 'sizes', None)
+                if sizes is None:
+                    sizes = (seg[1:] - seg[:-1]).cpu()                                        # the ONE documented host read
+                counts = self.fixed.counts(np.asarray(sizes, dtype=np.int64))
+                out_host = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+                M = int(out_host[-1])
+                out_ptr = to_device(torch.from_numpy(out_host), dev)
+                batch = torch.repeat_interleave(torch.arange(S, device=dev), to_device(torch.from_numpy(counts), dev), output_size=M)
+            else:
+                M = S * num
+                out_ptr = self._out_ptr.get((S, dev))
+                if out_ptr is None:
+                    out_ptr = self._out_ptr[(S, dev)] = torch.arange(S + 1, device=dev, dtype=torch.int64) * num
+                batch = torch.arange(S, device=dev).view(S, 1).expand(S, num).reshape(-1)
+            index = self.pick(seg, out_ptr, N, M, self.seed, counter)
+            names = [k for k in _ROW_KEYS if torch.is_tensor(getattr(data, k, None))]
+            for k in names:
+                if getattr(data, k).shape[0] != N:
+                    raise ValueError('SegmentCompose: data.%s has %d rows, data.pos %d' % (k, getattr(data, k).shape[0], N))
+            # one launch for all row attributes (B = 1: the picks are global rows)
+            moved = pick_rows([getattr(data, k)[None] for k in names], index[None], per_cloud=True)
+            for k, m in zip(names, moved):
+                setattr(data, k, m[0])
+            data.ptr, data.batch = out_ptr.clone(), batch         # (a copy: the caller may edit it, the cached one serves later calls)
+            pos, seg, N = data.pos, out_ptr, M
+        elif getattr(data, 'ptr', None) is None:
+            data.ptr = seg
+        norm, rgb = getattr(data, 'norm', None), getattr(data, 'rgb', None)
+        if norm is not None and (norm.dtype != torch.float32 or not norm.is_contiguous()):
+            norm = data.norm = norm.float().contiguous()
+        x = None
+        if self.add_norm:
+            x = torch.empty((N, 6), dtype=torch.float32, device=dev)
+        elif self.add_rgb or (self.drop is not None and rgb is not None):
+            x = torch.cat([pos, rgb.to(torch.float32)], -1).contiguous()
+        elif self.add is not None:
+            x = torch.empty_like(pos)
+        if self._has_point_step():
+            self.apply_segments(pos, norm, x, seg, self.seed, counter, params_out=params_out, stats_out=stats_out)
+        if x is not None and x.shape[-1] == 6 and not self.add_norm:
+            data.rgb = x[:, 3:] if self.add is None else x[:, 3:].clone()      # (after DropFeature; x keeps its own copy)
+        if self.add is not None:
+            data.x = x if (self.add_rgb or self.add_norm) else x[:, :3].contiguous()
+            for name, delete in zip(self.add.feat_names, self.add.delete_feats):
+                if delete and name in data.__dict__:
+                    delattr(data, name)
+        return data

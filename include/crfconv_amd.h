@@ -1143,6 +1143,10 @@ int crfconv_vote_update_batch(const crf_vote_desc* clouds, int n_clouds, const f
 int crfconv_vote_confusion(const float* test_probs, int64_t n_cloud, int C, const int64_t* proj_idx, const int64_t* labels, int64_t n_rows,
                            int64_t label_shift, int64_t* hist, int32_t* bad_count, crf_stream_t stream);
 
+/* The transforms for ragged batches (csrc/augment_segments.hip: crfconv_augment_segments, crfconv_fixed_points) are declared in a
+ * header of their own, in the same dialect, and are part of this interface: */
+#include "crfconv_amd_segments.h"
+
 #ifdef __cplusplus
 }
 #endif
