@@ -2,8 +2,7 @@
 
 include/crfconv_amd.h is the single declaration of the C ABI: SIGNATURES and one ctypes.Structure class per record type
 (crf_reduce_job -> ReduceJob, crf_pc_dump_job -> PcDumpJob, ..) are read from it when this module is imported.  A new entry
-point or job record is added to the header and to csrc/ only.  The headers it includes (include/crfconv_amd_<unit>.h) are read the
-same way into INCLUDED_SIGNATURES / INCLUDED_RECORDS.
+point or job record is added to the header and to csrc/ only.
 
 The library is the product: there is no Python / PyTorch fallback.  If it is missing or a call
 fails, an exception is raised -- never a silent slow path.
@@ -93,22 +92,6 @@ def _read_header():
         return parse_header(f.read())
 
 
-def _read_included():
-    """(functions, records) of the headers include/crfconv_amd.h includes by `#include "crfconv_amd_<unit>.h"` (a unit's entries in a file
-    of their own), read by the same parser; a name declared twice raises."""
-    functions, records = {}, {}
-    with open(HEADER_PATH) as f:
-        names = re.findall(r'^[ \t]*#[ \t]*include[ \t]+"(crfconv_amd_\w+\.h)"', f.read(), flags=re.M)
-    for name in names:
-        with open(os.path.join(os.path.dirname(HEADER_PATH), name)) as f:
-            fn, rec = parse_header(f.read())
-        if (set(fn) & (set(functions) | set(SIGNATURES))) or (set(rec) & (set(records) | set(_records))):
-            raise CrfConvError('include/%s declares a name a second time' % name)
-        functions.update(fn)
-        records.update(rec)
-    return functions, records
-
-
 def record_class_name(c_name):
     """crf_fold1_bwd_job -> Fold1BwdJob."""
     return ''.join(w[:1].upper() + w[1:] for w in c_name[len('crf_'):].split('_'))
@@ -120,12 +103,6 @@ RECORDS = {c_name: type(record_class_name(c_name), (ctypes.Structure,),
                         {'_fields_': fields, '__doc__': '%s of include/crfconv_amd.h.' % c_name})
            for c_name, fields in _records.items()}
 globals().update((cls.__name__, cls) for cls in RECORDS.values())
-# the same two tables for the headers the main one includes (SIGNATURES / RECORDS stay the main header's own text)
-INCLUDED_SIGNATURES, _included_records = _read_included()
-INCLUDED_RECORDS = {c_name: type(record_class_name(c_name), (ctypes.Structure,),
-                                 {'_fields_': fields, '__doc__': '%s of include/crfconv_amd.h (an included header).' % c_name})
-                    for c_name, fields in _included_records.items()}
-globals().update((cls.__name__, cls) for cls in INCLUDED_RECORDS.values())
 
 _lib = None
 
@@ -139,7 +116,7 @@ def load():
                 '%s not found: build it with `make -C crfconv_amd/csrc` (or __graft_entry__.build()). '
                 'crfconv_amd has no CPU / PyTorch fallback.' % LIB_PATH)
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(INCLUDED_SIGNATURES.items()):
+        for name, (res, args) in SIGNATURES.items():
             fn = getattr(lib, name)      # AttributeError here == header and library out of sync
             fn.restype = res
             fn.argtypes = args

@@ -124,11 +124,8 @@ __global__ __launch_bounds__(AUG_NT) void aug_apply_kernel(float* __restrict__ p
     }
     const float cm0 = sp.flip_axes != 0 ? s_cmax[0] : 0.f, cm1 = sp.flip_axes != 0 ? s_cmax[1] : 0.f,
                 cm2 = sp.flip_axes != 0 ? s_cmax[2] : 0.f;
-    if (params_out != nullptr && blockIdx.x == 0 && threadIdx.x == 0) {
-        float* o = params_out + (size_t)b * 8;
-        o[0] = P.c; o[1] = P.s; o[2] = P.sc0; o[3] = P.sc1; o[4] = P.sc2; o[5] = (float)P.flip; o[6] = (float)P.keep;
-        o[7] = (P.flip & 1) ? cm0 : ((P.flip & 2) ? cm1 : ((P.flip & 4) ? cm2 : 0.f));
-    }
+    if (params_out != nullptr && blockIdx.x == 0 && threadIdx.x == 0)
+        aug_write_params(params_out + (size_t)b * 8, P, cm0, cm1, cm2, false);
     if (n <= 0) return;
     if (sp.noise) {
         if (noise_in == nullptr) {
@@ -141,14 +138,7 @@ __global__ __launch_bounds__(AUG_NT) void aug_apply_kernel(float* __restrict__ p
     for (int j = 0; j < AUG_PPT; ++j) {
         float px = v[3 * j], py = v[3 * j + 1], pz = v[3 * j + 2];
         aug_rotate_scale(sp, P, px, py, pz);
-        if (P.flip & 1) px = sub_rn(cm0, px);
-        if (P.flip & 2) py = sub_rn(cm1, py);
-        if (P.flip & 4) pz = sub_rn(cm2, pz);
-        if (sp.noise) {
-            px = aug_add_noise(px, nz[3 * j], sp.clip);
-            py = aug_add_noise(py, nz[3 * j + 1], sp.clip);
-            pz = aug_add_noise(pz, nz[3 * j + 2], sp.clip);
-        }
+        aug_flip_noise(sp, P, cm0, cm1, cm2, nz + 3 * j, px, py, pz);
         v[3 * j] = px; v[3 * j + 1] = py; v[3 * j + 2] = pz;
     }
     if (full) {
@@ -210,17 +200,7 @@ extern "C" int crfconv_augment(float* pos, float* x, int64_t B, int64_t N, int C
                 (long long)B, (long long)N);
     CRF_REQUIRE(x == nullptr || C == 3 || C == 6, CRF_ERR_ARG, "x has C=%d channels (3 or 6: [pos] or [pos, rgb])", C);
     const crf_augment_spec sp = *spec;
-    CRF_REQUIRE(sp.rotate_axis >= -1 && sp.rotate_axis <= 2, CRF_ERR_ARG, "rotate_axis=%d outside {-1, 0, 1, 2}", sp.rotate_axis);
-    CRF_REQUIRE(std::isfinite(sp.deg_lo) && std::isfinite(sp.deg_hi) && sp.deg_lo <= sp.deg_hi, CRF_ERR_ARG,
-                "rotation range [%g, %g]", (double)sp.deg_lo, (double)sp.deg_hi);
-    CRF_REQUIRE(std::isfinite(sp.scale_lo) && std::isfinite(sp.scale_span) && sp.scale_span >= 0.f, CRF_ERR_ARG,
-                "scale range lo=%g span=%g", (double)sp.scale_lo, (double)sp.scale_span);
-    CRF_REQUIRE(sp.flip_axes >= 0 && sp.flip_axes <= 7, CRF_ERR_ARG, "flip_axes=%d outside [0, 7]", sp.flip_axes);
-    CRF_REQUIRE((sp.scale == 0 || sp.scale == 1) && (sp.noise == 0 || sp.noise == 1) && (sp.drop == 0 || sp.drop == 1), CRF_ERR_ARG,
-                "scale / noise / drop flags must be 0 or 1");
-    CRF_REQUIRE(sp.sigma >= 0.f && sp.clip >= 0.f && std::isfinite(sp.sigma) && std::isfinite(sp.clip), CRF_ERR_ARG,
-                "noise sigma=%g clip=%g", (double)sp.sigma, (double)sp.clip);
-    CRF_REQUIRE(sp.drop_p >= 0.f && sp.drop_p <= 1.f, CRF_ERR_ARG, "drop probability %g outside [0, 1]", (double)sp.drop_p);
+    if (int rc = aug_check_spec(sp)) return rc;
     const int64_t nblk = cdiv(N, AUG_PPB);
     if (sp.flip_axes != 0)
         CRF_REQUIRE(workspace && workspace_bytes >= crfconv_augment_workspace(B, N) && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0,

@@ -1,7 +1,8 @@
-// The draws and the per-point steps shared by the two augmentation units: augment.hip (dense crops [B, N, 3]) and
-// augment_segments.hip (a ragged batch pos [N, 3] + ptr [S + 1]).  Both units call the SAME device functions, so cloud b of a ragged
-// batch applies what Compose.draws(seed, counter, S) predicts for row b of a dense one, one singly rounded operation at a time.
-// `Spec` is crf_augment_spec or crf_augment_segments_spec: the fields read here carry the same names in both records.
+// What the two augmentation units share: augment.hip (dense crops [B, N, 3]) and augment_segments.hip (a ragged batch pos [N, 3] +
+// ptr [S + 1]).  The host check of the spec fields both records carry (aug_check_spec), the per-cloud draws, the per-point steps
+// (rotate and scale; flip, then clamped noise) and the params_out row.  Both units call the SAME device functions, so cloud b of a
+// ragged batch applies what Compose.draws(seed, counter, S) predicts for row b of a dense one, one singly rounded operation at a time.
+// `Spec` is crf_augment_spec or crf_augment_segments_spec (include/crfconv_amd.h): the fields read here carry the same names in both.
 #pragma once
 #include <cmath>
 
@@ -21,6 +22,23 @@ __device__ __forceinline__ unsigned long long aug_hash(unsigned long long seed, 
     return z ^ (z >> 31);
 }
 __device__ __forceinline__ float aug_u24(unsigned long long h) { return (float)(unsigned)(h >> 40) * 5.9604644775390625e-8f; }   // [0, 1)
+
+// The fields of crf_augment_spec, which crf_augment_segments_spec carries too: CRF_OK, or CRF_ERR_ARG with the message set.
+template <class Spec>
+inline int aug_check_spec(const Spec& sp) {
+    CRF_REQUIRE(sp.rotate_axis >= -1 && sp.rotate_axis <= 2, CRF_ERR_ARG, "rotate_axis=%d outside {-1, 0, 1, 2}", sp.rotate_axis);
+    CRF_REQUIRE(std::isfinite(sp.deg_lo) && std::isfinite(sp.deg_hi) && sp.deg_lo <= sp.deg_hi, CRF_ERR_ARG,
+                "rotation range [%g, %g]", (double)sp.deg_lo, (double)sp.deg_hi);
+    CRF_REQUIRE(std::isfinite(sp.scale_lo) && std::isfinite(sp.scale_span) && sp.scale_span >= 0.f, CRF_ERR_ARG,
+                "scale range lo=%g span=%g", (double)sp.scale_lo, (double)sp.scale_span);
+    CRF_REQUIRE(sp.flip_axes >= 0 && sp.flip_axes <= 7, CRF_ERR_ARG, "flip_axes=%d outside [0, 7]", sp.flip_axes);
+    CRF_REQUIRE((sp.scale == 0 || sp.scale == 1) && (sp.noise == 0 || sp.noise == 1) && (sp.drop == 0 || sp.drop == 1), CRF_ERR_ARG,
+                "scale / noise / drop flags must be 0 or 1");
+    CRF_REQUIRE(sp.sigma >= 0.f && sp.clip >= 0.f && std::isfinite(sp.sigma) && std::isfinite(sp.clip), CRF_ERR_ARG,
+                "noise sigma=%g clip=%g", (double)sp.sigma, (double)sp.clip);
+    CRF_REQUIRE(sp.drop_p >= 0.f && sp.drop_p <= 1.f, CRF_ERR_ARG, "drop probability %g outside [0, 1]", (double)sp.drop_p);
+    return CRF_OK;
+}
 
 struct AugParams {
     float c, s, sc0, sc1, sc2;
@@ -93,5 +111,28 @@ __device__ __forceinline__ float aug_noise_draw(float sigma, unsigned long long 
 
 // pos + clamp(noise, -clip, clip)
 __device__ __forceinline__ float aug_add_noise(float p, float nz, float clip) { return add_rn(p, fminf(fmaxf(nz, -clip), clip)); }
+
+// One rotated and scaled point: a flipped axis i becomes cm_i - p_i (cm_i = the cloud's max of that coordinate), then the clamped
+// noise nz[0 .. 3) per axis (read only when sp.noise is set).
+template <class Spec>
+__device__ __forceinline__ void aug_flip_noise(const Spec& sp, const AugParams& P, float cm0, float cm1, float cm2, const float* nz,
+                                               float& x, float& y, float& z) {
+    if (P.flip & 1) x = sub_rn(cm0, x);
+    if (P.flip & 2) y = sub_rn(cm1, y);
+    if (P.flip & 4) z = sub_rn(cm2, z);
+    if (sp.noise) {
+        x = aug_add_noise(x, nz[0], sp.clip);
+        y = aug_add_noise(y, nz[1], sp.clip);
+        z = aug_add_noise(z, nz[2], sp.clip);
+    }
+}
+
+// params_out row o [8] <- (cos, sin, sx, sy, sz, flip mask, keep, c_max) as applied; c_max: the cloud's maximum cm_i of the lowest
+// flipped axis, 0 without a flip or for a cloud without points (`empty`).  The selection stands here, after the stores, and not at the
+// call: handed the finished c_max, aug_segments_kernel allocates 97 VGPRs (4 waves per SIMD) instead of 96 (5).
+__device__ __forceinline__ void aug_write_params(float* o, const AugParams& P, float cm0, float cm1, float cm2, bool empty) {
+    o[0] = P.c; o[1] = P.s; o[2] = P.sc0; o[3] = P.sc1; o[4] = P.sc2; o[5] = (float)P.flip; o[6] = (float)P.keep;
+    o[7] = empty ? 0.f : ((P.flip & 1) ? cm0 : ((P.flip & 2) ? cm1 : ((P.flip & 4) ? cm2 : 0.f)));
+}
 
 }  // namespace crf

@@ -207,11 +207,7 @@ __global__ __launch_bounds__(SEG_NT) void aug_segments_kernel(float* __restrict_
         seg_block_max3(cm0, cm1, cm2, s_red);
     }
     if (tid == 0) {
-        if (params_out != nullptr) {
-            float* o = params_out + (size_t)b * 8;
-            o[0] = P.c; o[1] = P.s; o[2] = P.sc0; o[3] = P.sc1; o[4] = P.sc2; o[5] = (float)P.flip; o[6] = (float)P.keep;
-            o[7] = n == 0 ? 0.f : ((P.flip & 1) ? cm0 : ((P.flip & 2) ? cm1 : ((P.flip & 4) ? cm2 : 0.f)));
-        }
+        if (params_out != nullptr) aug_write_params(params_out + (size_t)b * 8, P, cm0, cm1, cm2, n == 0);
         if (stats_out != nullptr) {
             float* o = stats_out + (size_t)b * 4;
             o[0] = c0; o[1] = c1; o[2] = c2; o[3] = k;
@@ -239,14 +235,7 @@ __global__ __launch_bounds__(SEG_NT) void aug_segments_kernel(float* __restrict_
         for (int j = 0; j < SEG_PPT; ++j) {
             float px = v[3 * j], py = v[3 * j + 1], pz = v[3 * j + 2];
             place(px, py, pz);
-            if (P.flip & 1) px = sub_rn(cm0, px);
-            if (P.flip & 2) py = sub_rn(cm1, py);
-            if (P.flip & 4) pz = sub_rn(cm2, pz);
-            if (sp.noise) {
-                px = aug_add_noise(px, nz[3 * j], sp.clip);
-                py = aug_add_noise(py, nz[3 * j + 1], sp.clip);
-                pz = aug_add_noise(pz, nz[3 * j + 2], sp.clip);
-            }
+            aug_flip_noise(sp, P, cm0, cm1, cm2, nz + 3 * j, px, py, pz);
             v[3 * j] = px; v[3 * j + 1] = py; v[3 * j + 2] = pz;
             if (norm != nullptr) {
                 float ax = nm[3 * j], ay = nm[3 * j + 1], az = nm[3 * j + 2];
@@ -434,17 +423,7 @@ extern "C" int crfconv_augment_segments(float* pos, float* norm, float* x, int64
     CRF_REQUIRE((sp.center == 0 || sp.center == 1) && (sp.normalize == 0 || sp.normalize == 1) && (sp.x_norm == 0 || sp.x_norm == 1),
                 CRF_ERR_ARG, "center / normalize / x_norm flags must be 0 or 1");
     CRF_REQUIRE(!sp.x_norm || (x != nullptr && C == 6 && norm != nullptr), CRF_ERR_ARG, "the [pos, norm] layout needs x with C = 6 and norm");
-    CRF_REQUIRE(sp.rotate_axis >= -1 && sp.rotate_axis <= 2, CRF_ERR_ARG, "rotate_axis=%d outside {-1, 0, 1, 2}", sp.rotate_axis);
-    CRF_REQUIRE(std::isfinite(sp.deg_lo) && std::isfinite(sp.deg_hi) && sp.deg_lo <= sp.deg_hi, CRF_ERR_ARG,
-                "rotation range [%g, %g]", (double)sp.deg_lo, (double)sp.deg_hi);
-    CRF_REQUIRE(std::isfinite(sp.scale_lo) && std::isfinite(sp.scale_span) && sp.scale_span >= 0.f, CRF_ERR_ARG,
-                "scale range lo=%g span=%g", (double)sp.scale_lo, (double)sp.scale_span);
-    CRF_REQUIRE(sp.flip_axes >= 0 && sp.flip_axes <= 7, CRF_ERR_ARG, "flip_axes=%d outside [0, 7]", sp.flip_axes);
-    CRF_REQUIRE((sp.scale == 0 || sp.scale == 1) && (sp.noise == 0 || sp.noise == 1) && (sp.drop == 0 || sp.drop == 1), CRF_ERR_ARG,
-                "scale / noise / drop flags must be 0 or 1");
-    CRF_REQUIRE(sp.sigma >= 0.f && sp.clip >= 0.f && std::isfinite(sp.sigma) && std::isfinite(sp.clip), CRF_ERR_ARG,
-                "noise sigma=%g clip=%g", (double)sp.sigma, (double)sp.clip);
-    CRF_REQUIRE(sp.drop_p >= 0.f && sp.drop_p <= 1.f, CRF_ERR_ARG, "drop probability %g outside [0, 1]", (double)sp.drop_p);
+    if (int rc = aug_check_spec(sp)) return rc;
     auto al4 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; };
     CRF_REQUIRE(al4(pos) && al4(norm) && al4(x) && al4(noise_in), CRF_ERR_ARG, "arrays must be 4-byte aligned");
     if (S == 0) return CRF_OK;

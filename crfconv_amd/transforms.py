@@ -30,11 +30,12 @@ _M64 = 0xFFFFFFFFFFFFFFFF
 
 
 class _Transform:
-    """A lone transform applies as a Compose of one."""
+    """A lone transform applies as a chain of one: a Compose, or a SegmentCompose for a ragged-batch transform."""
+    _ragged = False
 
     def __call__(self, data):
         if getattr(self, '_compose', None) is None:
-            self._compose = Compose([self])
+            self._compose = (SegmentCompose if self._ragged else Compose)([self])
         return self._compose(data)
 
 
@@ -144,40 +145,62 @@ def _u24(seed, counter, clouds, slot):
     return ((h >> np.uint64(40)).astype(np.float64) * 2.0 ** -24).astype(np.float32)
 
 
+def _listed(names, last):
+    """['a', 'b', 'c'], 'or' -> 'a, b or c'."""
+    return names[0] if len(names) == 1 else '%s %s %s' % (', '.join(names[:-1]), last, names[-1])
+
+
+def _f32_device(t, shape):
+    """None, or a contiguous float32 device tensor of that shape."""
+    return t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape)
+
+
 class Compose:
     """The chain, validated and lowered to one crfconv_augment call.  `generator`: the seed is ONE draw on it at construction (on
     data._private_generator() when None: the global generator never advances); a device counter advances per call.
     ``state_dict()`` / ``load_state_dict()`` carry seed and counter."""
 
+    # what a chain class supplies: the transforms it takes, in their order, and the attribute each lands in; the features
+    # AddFeatsByKeys may name and the x it may build; how the messages call the chain and its pos
+    _order = _ORDER
+    _slots = ('rotate', 'scale', 'symmetry', 'noise', 'drop', 'add')
+    _feats = ('pos', 'rgb')
+    _layouts = (['pos'], ['pos', 'rgb'])
+    _name, _pos_shape = 'Compose', '[k, 3]'
+
     def __init__(self, transforms, generator=None):
+        name = self._name
         flat = []
         for t in transforms:
             flat.extend(t.transforms if isinstance(t, Compose) else [t])
         self.transforms = flat
-        self.rotate = self.scale = self.symmetry = self.noise = self.drop = self.add = None
+        for slot in self._slots:
+            setattr(self, slot, None)
         last = -1
         for t in flat:
-            k = next((i for i, cls in enumerate(_ORDER) if type(t) is cls), None)
+            k = next((i for i, cls in enumerate(self._order) if type(t) is cls), None)
             if k is None:
-                raise NotImplementedError('Compose: %r is not supported (supported: %s)' % (t, ', '.join(c.__name__ for c in _ORDER)))
+                raise NotImplementedError('%s: %r is not supported (supported: %s)' % (name, t, ', '.join(c.__name__ for c in self._order)))
             if k <= last:
-                raise NotImplementedError('Compose: %r out of order; supported is a subsequence of %s' % (t, ' -> '.join(c.__name__ for c in _ORDER)))
+                raise NotImplementedError('%s: %r out of order; supported is a subsequence of %s'
+                                          % (name, t, ' -> '.join(c.__name__ for c in self._order)))
             last = k
-            setattr(self, ('rotate', 'scale', 'symmetry', 'noise', 'drop', 'add')[k], t)
+            setattr(self, self._slots[k], t)
         if self.drop is not None and self.drop.feature_name != 'rgb':
-            raise NotImplementedError('Compose: %r: only the rgb feature can be dropped' % (self.drop,))
-        self.add_rgb = False
+            raise NotImplementedError('%s: %r: only the rgb feature can be dropped' % (name, self.drop))
+        added = None
         if self.add is not None:
             a = self.add
-            for name in a.feat_names:
-                if name not in ('pos', 'rgb'):
-                    raise NotImplementedError('Compose: %r: feature %r (only pos and rgb are supported)' % (a, name))
+            for feat in a.feat_names:
+                if feat not in self._feats:
+                    raise NotImplementedError('%s: %r: feature %r (only %s are supported)' % (name, a, feat, _listed(self._feats, 'and')))
             added = [n for n, on in zip(a.feat_names, a.list_add_to_x) if on]
-            if added not in (['pos'], ['pos', 'rgb']):
-                raise NotImplementedError('Compose: %r: x must be [pos] or [pos, rgb], got %s' % (a, added))
+            if added not in self._layouts:
+                raise NotImplementedError('%s: %r: x must be %s, got %s'
+                                          % (name, a, _listed(['[%s]' % ', '.join(lay) for lay in self._layouts], 'or'), added))
             if any(d for n, d in zip(a.feat_names, a.delete_feats) if n == 'pos'):
-                raise NotImplementedError('Compose: %r: pos cannot be deleted' % (a,))
-            self.add_rgb = added == ['pos', 'rgb']
+                raise NotImplementedError('%s: %r: pos cannot be deleted' % (name, a))
+        self.add_rgb, self.add_norm = added == ['pos', 'rgb'], added == ['pos', 'norm']
         if generator is None:
             from .data import _private_generator
             generator = _private_generator()
@@ -186,12 +209,11 @@ class Compose:
         self._counter_value = 0
 
     def __repr__(self):
-        return 'Compose(%s)' % ', '.join(repr(t) for t in self.transforms)
+        return '%s(%s)' % (self._name, ', '.join(repr(t) for t in self.transforms))
 
     # ---- the kernel's view of the chain
-    def _spec(self):
-        from ._lib import AugmentSpec
-        s = AugmentSpec()
+    def _fill_spec(self, s):
+        """The fields crf_augment_spec and crf_augment_segments_spec share, written into the record `s`."""
         s.rotate_axis = -1 if self.rotate is None else self.rotate.axis
         s.deg_lo, s.deg_hi = (0.0, 0.0) if self.rotate is None else self.rotate.degrees
         s.scale = 0 if self.scale is None else 1
@@ -203,6 +225,10 @@ class Compose:
         s.drop = 0 if self.drop is None else 1
         s.drop_p = 0.0 if self.drop is None else self.drop.drop_proba
         return s
+
+    def _spec(self):
+        from ._lib import AugmentSpec
+        return self._fill_spec(AugmentSpec())
 
     def _scale_range(self):
         if self.scale is None:
@@ -249,8 +275,7 @@ class Compose:
         from . import _lib
         from .graph import ptr, stream_ptr
 
-        def ok(t, shape):
-            return (t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape))
+        ok = _f32_device
         if pos.dim() != 3 or pos.shape[-1] != 3:
             raise ValueError('Compose.apply_batch: pos must be [B, N, 3], got %s' % (tuple(pos.shape),))
         B, N, _ = pos.shape
@@ -269,47 +294,67 @@ class Compose:
                   ptr(params_in), ptr(noise_in), ptr(params_out), ptr(ws), nbytes, stream_ptr())
         return pos, x
 
+    # ---- one call on a Data: the steps the two chains share
     def _device_counter(self, device):
         if self._counter is None or self._counter.device != device:
             value = self._counter_value if self._counter is None else int(self._counter.item())
             self._counter = torch.full((1,), value, dtype=torch.int64, device=device)
         return self._counter
 
-    def __call__(self, data, params_out=None):
-        """One crop (``Data`` with pos [k, 3] and rgb [k, 3] on the device), augmented in place and returned, as the reference's
-        transforms do; with AddFeatsByKeys, data.x = [pos, rgb] [k, C] and the deleted features are gone."""
+    def _advance(self, device):
+        """The device counter, one step further: the word this call's draws read."""
         from . import _lib
-        from .graph import ptr, require_gpu, stream_ptr
-        if getattr(data, 'norm', None) is not None:
-            raise NotImplementedError('Compose: data.norm is not supported (the transforms would rotate it too)')
+        from .graph import ptr, stream_ptr
+        counter = self._device_counter(device)
+        _lib.call('crfconv_add_i64', ptr(counter), 1, 1, stream_ptr())
+        return counter
+
+    def _checked_pos(self, data):
+        """data.pos as a contiguous float32 device tensor (written back when converted), and what AddFeatsByKeys needs of the data."""
+        from .graph import require_gpu
         pos = data.pos
         require_gpu(pos)
         if pos.dim() != 2 or pos.shape[-1] != 3:
-            raise ValueError('Compose: data.pos must be [k, 3], got %s' % (tuple(pos.shape),))
+            raise ValueError('%s: data.pos must be %s, got %s' % (self._name, self._pos_shape, tuple(pos.shape)))
         if pos.dtype != torch.float32 or not pos.is_contiguous():
             pos = data.pos = pos.float().contiguous()
-        rgb = getattr(data, 'rgb', None)
-        if self.add_rgb and rgb is None:
-            raise ValueError('Compose: %r needs data.rgb' % (self.add,))
+        for feat, needed in (('rgb', self.add_rgb), ('norm', self.add_norm)):
+            if needed and getattr(data, feat, None) is None:
+                raise ValueError('%s: %r needs data.%s' % (self._name, self.add, feat))
         if self.add is not None and getattr(data, 'x', None) is not None:
-            raise NotImplementedError('Compose: %r onto an existing data.x is not supported' % (self.add,))
-        x = None
+            raise NotImplementedError('%s: %r onto an existing data.x is not supported' % (self._name, self.add))
+        return pos
+
+    def _stage_x(self, pos, rgb):
+        """The x the kernel fills: [pos, rgb] holds the rgb it may zero, [pos, norm] and [pos] are written whole; None when no step needs one."""
+        if self.add_norm:
+            return torch.empty((pos.shape[0], 6), dtype=torch.float32, device=pos.device)
         if self.add_rgb or (self.drop is not None and rgb is not None):
-            x = torch.cat([pos, rgb.to(torch.float32)], -1).contiguous()
-        elif self.add is not None:
-            x = torch.empty_like(pos)
-        counter = self._device_counter(pos.device)
-        _lib.call('crfconv_add_i64', ptr(counter), 1, 1, stream_ptr())
-        self.apply_batch(pos[None], None if x is None else x[None], self.seed, counter,
-                         params_out=None if params_out is None else params_out.view(1, 8))
-        if x is not None and x.shape[-1] == 6:
+            return torch.cat([pos, rgb.to(torch.float32)], -1).contiguous()
+        return None if self.add is None else torch.empty_like(pos)
+
+    def _finish(self, data, x):
+        """data.rgb after DropFeature, data.x, and the features AddFeatsByKeys deletes."""
+        if x is not None and x.shape[-1] == 6 and not self.add_norm:
             data.rgb = x[:, 3:] if self.add is None else x[:, 3:].clone()      # (after DropFeature; x keeps its own copy)
         if self.add is not None:
-            data.x = x if self.add_rgb else x[:, :3].contiguous()
+            data.x = x if (self.add_rgb or self.add_norm) else x[:, :3].contiguous()
             for name, delete in zip(self.add.feat_names, self.add.delete_feats):
                 if delete and name in data.__dict__:
                     delattr(data, name)
         return data
+
+    def __call__(self, data, params_out=None):
+        """One crop (``Data`` with pos [k, 3] and rgb [k, 3] on the device), augmented in place and returned, as the reference's
+        transforms do; with AddFeatsByKeys, data.x = [pos, rgb] [k, C] and the deleted features are gone."""
+        if getattr(data, 'norm', None) is not None:
+            raise NotImplementedError('Compose: data.norm is not supported (the transforms would rotate it too)')
+        pos = self._checked_pos(data)
+        x = self._stage_x(pos, getattr(data, 'rgb', None))
+        counter = self._advance(pos.device)
+        self.apply_batch(pos[None], None if x is None else x[None], self.seed, counter,
+                         params_out=None if params_out is None else params_out.view(1, 8))
+        return self._finish(data, x)
 
     def state_dict(self):
         return {'seed': int(self.seed), 'counter': int(self._counter.item()) if self._counter is not None else self._counter_value}
@@ -325,13 +370,8 @@ class Compose:
 _FXP_DOMAIN = 0x8CB92BA72F3D8DD7          # csrc/augment_segments.hip: FXP_DOMAIN
 
 
-class _SegmentTransform:
-    """A lone ragged-batch transform applies as a SegmentCompose of one."""
-
-    def __call__(self, data):
-        if getattr(self, '_compose', None) is None:
-            self._compose = SegmentCompose([self])
-        return self._compose(data)
+class _SegmentTransform(_Transform):
+    _ragged = True
 
 
 class Center(_SegmentTransform):
@@ -401,9 +441,7 @@ class FixedPoints(_SegmentTransform):
         return {'index': index, 'out_ptr': out_ptr}
 
 
-_SEG_ORDER = (FixedPoints, Center, NormalizeScale) + _ORDER
 _ROW_KEYS = ('pos', 'norm', 'rgb', 'x', 'y')           # the per-row attributes FixedPoints gathers; anything else on the data stays as it is
-_SEG_SLOTS = ('fixed', 'center', 'normalize', 'rotate', 'scale', 'symmetry', 'noise', 'drop', 'add')
 
 
 class SegmentCompose(Compose):
@@ -421,61 +459,26 @@ class SegmentCompose(Compose):
     Seed, device counter, ``state_dict()`` / ``load_state_dict()`` as on ``Compose``; one counter step per call serves the picks and
     the augmentation (two hash domains)."""
 
-    def __init__(self, transforms, generator=None):
-        flat = []
-        for t in transforms:
-            flat.extend(t.transforms if isinstance(t, Compose) else [t])
-        self.transforms = flat
-        for slot in _SEG_SLOTS:
-            setattr(self, slot, None)
-        last = -1
-        for t in flat:
-            k = next((i for i, cls in enumerate(_SEG_ORDER) if type(t) is cls), None)
-            if k is None:
-                raise NotImplementedError('SegmentCompose: %r is not supported (supported: %s)'
-                                          % (t, ', '.join(c.__name__ for c in _SEG_ORDER)))
-            if k <= last:
-                raise NotImplementedError('SegmentCompose: %r out of order; supported is a subsequence of %s'
-                                          % (t, ' -> '.join(c.__name__ for c in _SEG_ORDER)))
-            last = k
-            setattr(self, _SEG_SLOTS[k], t)
-        if self.drop is not None and self.drop.feature_name != 'rgb':
-            raise NotImplementedError('SegmentCompose: %r: only the rgb feature can be dropped' % (self.drop,))
-        self.add_rgb = self.add_norm = False
-        if self.add is not None:
-            a = self.add
-            for name in a.feat_names:
-                if name not in ('pos', 'rgb', 'norm'):
-                    raise NotImplementedError('SegmentCompose: %r: feature %r (only pos, rgb and norm are supported)' % (a, name))
-            added = [n for n, on in zip(a.feat_names, a.list_add_to_x) if on]
-            if added not in (['pos'], ['pos', 'rgb'], ['pos', 'norm']):
-                raise NotImplementedError('SegmentCompose: %r: x must be [pos], [pos, rgb] or [pos, norm], got %s' % (a, added))
-            if any(d for n, d in zip(a.feat_names, a.delete_feats) if n == 'pos'):
-                raise NotImplementedError('SegmentCompose: %r: pos cannot be deleted' % (a,))
-            self.add_rgb, self.add_norm = added == ['pos', 'rgb'], added == ['pos', 'norm']
-        if generator is None:
-            from .data import _private_generator
-            generator = _private_generator()
-        self.seed = int(torch.randint(0, 2 ** 62, (1,), generator=generator, dtype=torch.int64, device=generator.device).item())
-        self._counter = None
-        self._counter_value = 0
-        self._out_ptr = {}                     # (S, device) -> arange(S + 1) * num
+    _order = (FixedPoints, Center, NormalizeScale) + _ORDER
+    _slots = ('fixed', 'center', 'normalize') + Compose._slots
+    _feats = ('pos', 'rgb', 'norm')
+    _layouts = (['pos'], ['pos', 'rgb'], ['pos', 'norm'])
+    _name, _pos_shape = 'SegmentCompose', '[N, 3]'
 
-    def __repr__(self):
-        return 'SegmentCompose(%s)' % ', '.join(repr(t) for t in self.transforms)
+    def __init__(self, transforms, generator=None):
+        super().__init__(transforms, generator)
+        self._out_ptr = {}                     # (S, device) -> arange(S + 1) * num
 
     def _spec(self):
         from ._lib import AugmentSegmentsSpec
-        d, s = Compose._spec(self), AugmentSegmentsSpec()
-        for name, _ in d._fields_:
-            setattr(s, name, getattr(d, name))
+        s = self._fill_spec(AugmentSegmentsSpec())
         s.center = 1 if (self.center is not None or self.normalize is not None) else 0      # NormalizeScale centres first
         s.normalize = 0 if self.normalize is None else 1
         s.x_norm = 1 if self.add_norm else 0
         return s
 
     def _has_point_step(self):
-        return any(getattr(self, slot) is not None for slot in _SEG_SLOTS[1:])
+        return any(getattr(self, slot) is not None for slot in self._slots[1:])
 
     # ---- device
     def apply_segments(self, pos, norm, x, ptr, seed, counter, params_out=None, stats_out=None, params_in=None, noise_in=None):
@@ -492,9 +495,7 @@ class SegmentCompose(Compose):
         N = pos.shape[0]
         S = ptr.numel() - 1
         C = 0 if x is None else x.shape[-1]
-
-        def ok(t, shape):
-            return (t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape))
+        ok = _f32_device
         if not ok(pos, (N, 3)) or not ok(norm, (N, 3)) or not ok(x, (N, C)) or not ok(params_out, (S, 8)) \
                 or not ok(stats_out, (S, 4)) or not ok(params_in, (S, 8)) or not ok(noise_in, (N, 3)):
             raise ValueError('SegmentCompose.apply_segments: pos / norm / noise [N, 3], x [N, C], params [S, 8], stats [S, 4] must be '
@@ -525,21 +526,9 @@ class SegmentCompose(Compose):
         the replace / allow_duplicates mode nothing is read back and the call can be captured; replace=False,
         allow_duplicates=False sizes its output by min(num, n): it takes the cloud sizes from data.sizes (host) when present,
         else makes ONE host read of ptr."""
-        from . import _lib
         from .data import pick_rows
-        from .graph import ptr as p_, require_gpu, stream_ptr, to_device
-        pos = data.pos
-        require_gpu(pos)
-        if pos.dim() != 2 or pos.shape[-1] != 3:
-            raise ValueError('SegmentCompose: data.pos must be [N, 3], got %s' % (tuple(pos.shape),))
-        if pos.dtype != torch.float32 or not pos.is_contiguous():
-            pos = data.pos = pos.float().contiguous()
-        if self.add_rgb and getattr(data, 'rgb', None) is None:
-            raise ValueError('SegmentCompose: %r needs data.rgb' % (self.add,))
-        if self.add_norm and getattr(data, 'norm', None) is None:
-            raise ValueError('SegmentCompose: %r needs data.norm' % (self.add,))
-        if self.add is not None and getattr(data, 'x', None) is not None:
-            raise NotImplementedError('SegmentCompose: %r onto an existing data.x is not supported' % (self.add,))
+        from .graph import to_device
+        pos = self._checked_pos(data)
         N, dev = pos.shape[0], pos.device
         seg = getattr(data, 'ptr', None)
         if seg is None:
@@ -550,8 +539,7 @@ class SegmentCompose(Compose):
             seg = torch.searchsorted(batch.contiguous(), torch.arange(S + 1, device=dev, dtype=batch.dtype)).to(torch.int64)
         seg = seg.to(torch.int64).contiguous()
         S = seg.numel() - 1
-        counter = self._device_counter(dev)
-        _lib.call('crfconv_add_i64', p_(counter), 1, 1, stream_ptr())
+        counter = self._advance(dev)
         if self.fixed is not None:
             if N == 0:
                 raise ValueError('SegmentCompose: %r on a batch without rows' % (self.fixed,))
@@ -581,26 +569,13 @@ class SegmentCompose(Compose):
             for k, m in zip(names, moved):
                 setattr(data, k, m[0])
             data.ptr, data.batch = out_ptr.clone(), batch         # (a copy: the caller may edit it, the cached one serves later calls)
-            pos, seg, N = data.pos, out_ptr, M
+            pos, seg = data.pos, out_ptr
         elif getattr(data, 'ptr', None) is None:
             data.ptr = seg
         norm, rgb = getattr(data, 'norm', None), getattr(data, 'rgb', None)
         if norm is not None and (norm.dtype != torch.float32 or not norm.is_contiguous()):
             norm = data.norm = norm.float().contiguous()
-        x = None
-        if self.add_norm:
-            x = torch.empty((N, 6), dtype=torch.float32, device=dev)
-        elif self.add_rgb or (self.drop is not None and rgb is not None):
-            x = torch.cat([pos, rgb.to(torch.float32)], -1).contiguous()
-        elif self.add is not None:
-            x = torch.empty_like(pos)
+        x = self._stage_x(pos, rgb)
         if self._has_point_step():
             self.apply_segments(pos, norm, x, seg, self.seed, counter, params_out=params_out, stats_out=stats_out)
-        if x is not None and x.shape[-1] == 6 and not self.add_norm:
-            data.rgb = x[:, 3:] if self.add is None else x[:, 3:].clone()      # (after DropFeature; x keeps its own copy)
-        if self.add is not None:
-            data.x = x if (self.add_rgb or self.add_norm) else x[:, :3].contiguous()
-            for name, delete in zip(self.add.feat_names, self.add.delete_feats):
-                if delete and name in data.__dict__:
-                    delattr(data, name)
-        return data
+        return self._finish(data, x)

@@ -1,12 +1,16 @@
 """-m gpu: the ragged-batch transforms on the device (csrc/augment_segments.hip: crfconv_augment_segments, crfconv_fixed_points)
 against the numpy float64 restatement of tests/segment_transforms_restatement.py and the exact host twins of the draws
 (transforms.Compose.draws, transforms.FixedPoints.draws), their capture in one graph, and a ShapeNet-Part style training step."""
+import ctypes
+import re
+
 import numpy as np
 import pytest
 import torch
 
 import segment_transforms_restatement as R
 from gpu_util import DEV, t
+from crfconv_amd import _lib
 from crfconv_amd import transforms as T
 from crfconv_amd.data import Data
 
@@ -426,3 +430,31 @@ def test_shapenet_part_training_step():
     assert torch.isfinite(loss)
     for name, p in net.named_parameters():
         assert p.grad is not None and torch.isfinite(p.grad).all(), name
+
+
+@pytest.mark.parametrize('field,value,fragment', [
+    ('rotate_axis', 3, 'rotate_axis=3 outside'),
+    ('deg_lo', 200.0, 'rotation range'),                                           # above deg_hi = 180
+    ('scale_span', -0.125, 'scale range'),
+    ('flip_axes', 8, 'flip_axes=8 outside'),
+    ('scale', 2, 'flags must be 0 or 1'), ('noise', 2, 'flags must be 0 or 1'), ('drop', 2, 'flags must be 0 or 1'),
+    ('sigma', -1.0, 'noise sigma='),
+    ('drop_p', 1.5, 'drop probability'),
+])
+def test_both_entries_refuse_a_bad_spec_value(field, value, fragment):
+    """The spec fields the dense and the ragged record share are checked by one function (csrc/augment_common.hpp: aug_check_spec):
+    each bad value is refused by crfconv_augment and by crfconv_augment_segments in the same words, before anything is launched."""
+    from crfconv_amd.graph import ptr, stream_ptr
+    steps = [T.RandomRotate(180, axis=2), T.RandomScaleAnisotropic([0.8, 1.2]), T.RandomSymmetry([True, False, False]),
+             T.RandomNoise(sigma=0.01, clip=0.05), T.DropFeature(0.2)]
+    pos, counter, seg = torch.ones((4, 3), device=DEV), counter0(), t(np.array([0, 4], np.int64))
+    dense = T.Compose(steps, generator=torch.Generator().manual_seed(1))._spec()
+    ragged = T.SegmentCompose(steps, generator=torch.Generator().manual_seed(1))._spec()
+    setattr(dense, field, value)
+    setattr(ragged, field, value)
+    with pytest.raises(_lib.CrfConvError, match=re.escape(fragment)):              # B = 1, N = 4, no x
+        _lib.call('crfconv_augment', ptr(pos), None, 1, 4, 0, ctypes.byref(dense), 1, ptr(counter), None, None, None, None, 0, stream_ptr())
+    with pytest.raises(_lib.CrfConvError, match=re.escape(fragment)):              # one cloud of 4 rows, no norm, no x
+        _lib.call('crfconv_augment_segments', ptr(pos), None, None, 4, 0, ptr(seg), 1, ctypes.byref(ragged), 1, ptr(counter), None, None,
+                  None, None, stream_ptr())
+    assert torch.equal(pos, torch.ones((4, 3), device=DEV))

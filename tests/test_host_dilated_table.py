@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+from abi_counts import N_FUNCTIONS, N_RECORDS
 import dilated_restatement as R
 from crfconv_amd import _lib
 
@@ -33,7 +34,7 @@ def test_header_has_the_entry_in_the_place_of_the_single_layer_matrices(header):
     assert _lib.SIGNATURES['crfconv_graph_table_dilated'] == (restype, argtypes)
     assert 'crfconv_crf_matrices' not in functions and 'crfconv_crf_matrices(' not in text
     assert 'crfconv_crf_matrices_batched' in functions and 'crfconv_crf_matrices_backward' in functions
-    assert len(functions) == 190 and len(records) == 22
+    assert len(functions) == N_FUNCTIONS and len(records) == N_RECORDS
 
 
 def test_library_exports():

@@ -5,6 +5,7 @@ import os
 
 import pytest
 
+from abi_counts import N_FUNCTIONS, N_RECORDS
 from crfconv_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,7 +28,7 @@ def test_header_has_the_entry_in_the_place_of_the_single_narrowing(header):
     assert _lib.SIGNATURES['crfconv_graph_table'] == (restype, argtypes)
     assert 'crfconv_index_narrow_sorted' not in functions and 'crfconv_index_narrow_sorted' not in text
     assert 'crfconv_index_narrow_batched' in functions and 'crf_narrow_job' in records
-    assert len(functions) == 190 and len(records) == 22
+    assert len(functions) == N_FUNCTIONS and len(records) == N_RECORDS
 
 
 def test_library_exports():

@@ -2,6 +2,7 @@
 validation of the chain, the laws of the picks' host twin, the float64 restatement the GPU tests compare against -- itself compared
 with a plain float64 torch composition --, and the header / ABI record of the new entry points.  No GPU and no library needed."""
 import ctypes
+import glob
 import os
 import subprocess
 import sys
@@ -206,12 +207,10 @@ def test_restatement_against_a_plain_torch_composition():
 
 
 def test_header_and_abi_of_the_new_record():
-    # the unit's declarations sit in include/crfconv_amd_segments.h, which crfconv_amd.h includes; _lib reads it with the same parser
-    assert list(_lib.INCLUDED_RECORDS) == ['crf_augment_segments_spec'] and _lib.INCLUDED_RECORDS['crf_augment_segments_spec'] is _lib.AugmentSegmentsSpec
-    assert sorted(_lib.INCLUDED_SIGNATURES) == ['crfconv_augment_segments', 'crfconv_fixed_points']
-    assert not set(_lib.INCLUDED_SIGNATURES) & set(_lib.SIGNATURES) and not set(_lib.INCLUDED_RECORDS) & set(_lib.RECORDS)
-    with open(_lib.HEADER_PATH) as f:
-        assert '#include "crfconv_amd_segments.h"' in f.read()
+    # the unit's declarations stand in include/crfconv_amd.h itself, the one header of the ABI, and in _lib's one pair of tables
+    assert _lib.RECORDS['crf_augment_segments_spec'] is _lib.AugmentSegmentsSpec
+    assert {'crfconv_augment_segments', 'crfconv_fixed_points'} <= set(_lib.SIGNATURES)
+    assert glob.glob(os.path.join(os.path.dirname(_lib.HEADER_PATH), 'crfconv_amd_*.h')) == []
     spec = _lib.AugmentSegmentsSpec
     names = [n for n, _ in spec._fields_]
     assert names == ['center', 'normalize', 'rotate_axis', 'deg_lo', 'deg_hi', 'scale', 'scale_lo', 'scale_span', 'flip_axes', 'noise',
@@ -221,11 +220,11 @@ def test_header_and_abi_of_the_new_record():
     assert ctypes.sizeof(spec) == 60                                  # flat, fifteen 4-byte fields, no padding
     # the dense record is a suffix-free subset: the shared device functions read the same names in both
     assert [n for n, _ in _lib.AugmentSpec._fields_] == names[2:-1]
-    res, args = _lib.INCLUDED_SIGNATURES['crfconv_augment_segments']
+    res, args = _lib.SIGNATURES['crfconv_augment_segments']
     assert res is ctypes.c_int and len(args) == 15
     assert args[:3] == [ctypes.c_void_p] * 3 and args[3] is ctypes.c_int64 and args[4] is ctypes.c_int and args[6] is ctypes.c_int64
     assert args[8] is ctypes.c_uint64 and args[-1] is ctypes.c_void_p
-    res, args = _lib.INCLUDED_SIGNATURES['crfconv_fixed_points']
+    res, args = _lib.SIGNATURES['crfconv_fixed_points']
     assert res is ctypes.c_int and args == [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                             ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     # the kernel's view of a chain
