@@ -40,8 +40,9 @@ LASTWG_FLAT_ restated beside regular expressions over the text they restate.  Ea
 test_every_form_is_reached asserts that the union of the cases reaches every (TCO, VEC4, NCH, EPI, PRO) for which lf_form is true, except
 EPI_UV, and every (tco, tci) class of mlp_plan's switch.
 
-Not here, and held today by: the coarse family mlp_small*.hip / gemm*.hip / _MLPSmall* (test_gpu_model.py, test_gpu_mask_fold.py,
-test_gpu_operand_fold.py, test_gpu_infer.py), head.hip / _HeadRecompute (test_gpu_model.py, test_gpu_mlp_nodes.py), mlp_block_pool
+Not here, and held today by: the coarse family mlp_small*.hip / gemm_stats.hip / _MLPSmall* (test_gpu_mlp_small.py, form by form against
+the same reference; its UV operand forms, the eval epilogue and the plain product: test_gpu_operand_fold.py, test_gpu_infer.py,
+test_gpu_model.py), head.hip / _HeadRecompute (test_gpu_model.py, test_gpu_mlp_nodes.py), mlp_block_pool
 (test_gpu_pool.py, test_gpu_mlp_nodes.py), the EPI_UV operand fold (test_gpu_operand_fold.py), deferred delivery (test_gpu_mlp_nodes.py,
 test_gpu_backward_tail.py), the stand-alone statistics pass of bn.hip (test_gpu_model.py, test_gpu_infer.py) and loss.hip
 (test_gpu_model.py, test_gpu_native.py).  Measured figures per site: BOUNDS and
