@@ -14,6 +14,7 @@ import re
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('CRFCONV_LIB') or os.path.join(_HERE, 'libcrfconv_amd.so')      # CRFCONV_LIB: A/B builds of scratch/
 HEADER_PATH = os.path.join(_HERE, '..', 'include', 'crfconv_amd.h')
+INTERNAL_HEADER_PATH = os.path.join(_HERE, 'csrc', 'stream_jobs.h')        # entries only this package calls: not part of the public ABI
 
 
 class CrfConvError(RuntimeError):
@@ -85,10 +86,10 @@ def parse_header(text):
     return functions, records
 
 
-def _read_header():
-    if not os.path.exists(HEADER_PATH):
-        raise CrfConvError('%s not found: it is the declaration of the C ABI that crfconv_amd reads at import.' % HEADER_PATH)
-    with open(HEADER_PATH) as f:
+def _read_header(path=HEADER_PATH):
+    if not os.path.exists(path):
+        raise CrfConvError('%s not found: it is the declaration of the C ABI that crfconv_amd reads at import.' % path)
+    with open(path) as f:
         return parse_header(f.read())
 
 
@@ -103,6 +104,14 @@ RECORDS = {c_name: type(record_class_name(c_name), (ctypes.Structure,),
                         {'_fields_': fields, '__doc__': '%s of include/crfconv_amd.h.' % c_name})
            for c_name, fields in _records.items()}
 globals().update((cls.__name__, cls) for cls in RECORDS.values())
+# the same for the package-internal entries of csrc/stream_jobs.h (LinearJob, MlpStreamBwdJob): tables of their own, the public ones stay the header's
+INTERNAL_SIGNATURES, _internal_records = _read_header(INTERNAL_HEADER_PATH)
+INTERNAL_RECORDS = {c_name: type(record_class_name(c_name), (ctypes.Structure,),
+                                 {'_fields_': fields, '__doc__': '%s of csrc/stream_jobs.h.' % c_name})
+                    for c_name, fields in _internal_records.items()}
+if set(INTERNAL_SIGNATURES) & set(SIGNATURES) or set(INTERNAL_RECORDS) & set(RECORDS):
+    raise CrfConvError('csrc/stream_jobs.h declares a name of include/crfconv_amd.h again')
+globals().update((cls.__name__, cls) for cls in INTERNAL_RECORDS.values())
 
 _lib = None
 
@@ -116,7 +125,7 @@ def load():
                 '%s not found: build it with `make -C crfconv_amd/csrc` (or __graft_entry__.build()). '
                 'crfconv_amd has no CPU / PyTorch fallback.' % LIB_PATH)
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(INTERNAL_SIGNATURES.items()):
             fn = getattr(lib, name)      # AttributeError here == header and library out of sync
             fn.restype = res
             fn.argtypes = args

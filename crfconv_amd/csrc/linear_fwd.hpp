@@ -3,6 +3,7 @@
 // product of the fused MLP backward, PRO = true).
 #pragma once
 #include "common.hpp"
+#include "stream_jobs.h"
 #include "uv_fold.hpp"
 
 #include <type_traits>
@@ -490,6 +491,31 @@ __global__ __launch_bounds__(LF_BLOCK) void linear_fwd_kernel(const float* __res
     }
 }
 
+// The same statements as a device function of the workgroup's coordinates (bx, by) in a grid of nbx row workgroups: a job's own coordinates
+// and block count in linear_fwd_jobs_kernel, whose launch is the jobs' single launches laid end to end.  linear_fwd_body.inc is a COPY of the
+// kernel's statements above with blockIdx.x / blockIdx.y / gridDim.x spelled LF_BX / LF_BY / LF_NBX (tests/test_host_stream_jobs.py holds the
+// two texts together).  The kernel does not call this function: through a call the register counts of 27 instantiations moved and two dX
+// forms lost a wavefront per SIMD (profiles/r31_stream_groups.md).
+template <int TCO, bool PRO, bool VEC4, int EPI, int NCH>
+__device__ __forceinline__ void linear_fwd_body(const float* __restrict__ X, const float* __restrict__ W,
+                                                const float* __restrict__ bias, int64_t M, int Ci, int Co,
+                                                int transpose_w, float* __restrict__ Y,
+                                                float* __restrict__ stat_partial /*[nblk][Co][4] or null*/,
+                                                const float* __restrict__ Y2, const float* __restrict__ pro, float slope,
+                                                const float* __restrict__ Xb, int xsplit, float* __restrict__ Yb, int ysplit,
+                                                const float* __restrict__ addend, const long long* __restrict__ drop_counter,
+                                                unsigned long long drop_seed, unsigned drop_threshold, float drop_scale,
+                                                const float* __restrict__ mask_ref, float mask_slope, const UvFold& uv,
+                                                const unsigned bx, const unsigned by, const unsigned nbx) {
+#define LF_BX bx
+#define LF_BY by
+#define LF_NBX nbx
+#include "linear_fwd_body.inc"
+#undef LF_BX
+#undef LF_BY
+#undef LF_NBX
+}
+
 static int lf_blocks(int64_t M) {
     constexpr int cap = 512;   // swept 128..2048 on the training step: 512 (two blocks per CU, half the statistic records of 1024) is the optimum
     int64_t nb = (M + 16 * LF_WAVES - 1) / (16 * LF_WAVES);           // 16 rows per wave and iteration; two blocks per CU keep
@@ -604,6 +630,111 @@ static int lf_launch(const LfArgs& a, int epi, crf_stream_t stream) {
         }
     }); }); }); });
     CRF_REQUIRE(launched, CRF_ERR_UNSUPPORTED, "linear_fwd_kernel has no form pro=%d epi=%d for %d -> %d", (int)PRO, epi, a.Ci, a.Co);
+    CRF_LAUNCH_CHECK();
+    return CRF_OK;
+}
+
+// ---------------------------------------------------------------------- several INDEPENDENT products per launch
+// Up to LFJ_MAX jobs whose single launches (lf_launch) are laid end to end in one grid: workgroup blk_base[j] + bx + nbx by of the launch
+// is workgroup (bx, by) of job j's own grid of nbx = lf_blocks(M_j) row workgroups, and runs the instantiation that job's launch would --
+// the same rows, summation order and statistic records.  A fine-level launch of these widths is a chain of dependent round trips on
+// <= 512 workgroups of 36-76 registers: two of them side by side cost about the longer one.  Forms: the forward's <1, false, true, EPI_NONE,
+// 1 | 2 | 4> (Co <= 16, Ci <= 64, one operand, no bias) and the dX product's <1 | 2 | 4, true, true, EPI_NONE | EPI_ADD, 1> (k <= 16).
+constexpr int LFJ_MAX = 4;                               // (= GG_MAX of gemm_tile.hpp, BA_MAX of bn_records.hip: the group nodes' size)
+struct LfJobs {                                          // (slots at or past njobs are never read)
+    const float* X[LFJ_MAX]; const float* W[LFJ_MAX]; float* Y[LFJ_MAX]; float* stat[LFJ_MAX];
+    const float* Y2[LFJ_MAX]; const float* pro[LFJ_MAX]; const float* addend[LFJ_MAX];
+    long long M[LFJ_MAX];
+    int Ci[LFJ_MAX], Co[LFJ_MAX], nbx[LFJ_MAX], form[LFJ_MAX];      // form: NCH (forward); 2 TCO + (addend != null) (dX)
+    float slope[LFJ_MAX];
+    int blk_base[LFJ_MAX + 1];
+    int njobs;
+};
+// workgroup `blk` of the jobs' grids laid end to end (blockIdx.x in linear_fwd_jobs_kernel; behind the hosted tiles in linear.hip's
+// linear_fwd_jobs_hosting_kernel)
+template <bool PRO>
+__device__ __forceinline__ void linear_fwd_jobs_block(const LfJobs& t, const unsigned blk) {
+    int j = 0;
+    while (j + 1 < t.njobs && t.blk_base[j + 1] <= (int)blk) ++j;
+    const unsigned local = blk - (unsigned)t.blk_base[j];
+    const unsigned nbx = (unsigned)uni(t.nbx[j]);
+    const unsigned bx = (unsigned)uni((int)(local % nbx)), by = (unsigned)uni((int)(local / nbx));
+    const float* X = uni(t.X[j]); const float* W = uni(t.W[j]); float* Y = uni(t.Y[j]);
+    const int64_t M = uni(t.M[j]);
+    const int Ci = uni(t.Ci[j]), Co = uni(t.Co[j]), form = uni(t.form[j]);
+    if constexpr (!PRO) {
+        float* stat = uni(t.stat[j]);
+#define LFJ_FWD(NCH) linear_fwd_body<1, false, true, EPI_NONE, NCH>(X, W, nullptr, M, Ci, Co, 0, Y, stat, nullptr, nullptr, 1.f, nullptr, 0, nullptr, 0, \
+                                                                    nullptr, nullptr, 0ull, 0u, 1.f, nullptr, 1.f, UvFold(), bx, by, nbx)
+        if (form == 1) LFJ_FWD(1);
+        else if (form == 2) LFJ_FWD(2);
+        else LFJ_FWD(4);
+#undef LFJ_FWD
+    } else {
+        const float* Y2 = uni(t.Y2[j]); const float* pro = uni(t.pro[j]); const float* addend = uni(t.addend[j]);
+        const float slope = uni(t.slope[j]);
+#define LFJ_DX(TCO, EPI) linear_fwd_body<TCO, true, true, EPI, 1>(X, W, nullptr, M, Ci, Co, 1, Y, nullptr, Y2, pro, slope, nullptr, 0, nullptr, 0, addend, \
+                                                                  nullptr, 0ull, 0u, 1.f, nullptr, 1.f, UvFold(), bx, by, nbx)
+        switch (form) {
+            case 2: LFJ_DX(1, EPI_NONE); break;
+            case 3: LFJ_DX(1, EPI_ADD); break;
+            case 4: LFJ_DX(2, EPI_NONE); break;
+            case 5: LFJ_DX(2, EPI_ADD); break;
+            case 8: LFJ_DX(4, EPI_NONE); break;
+            default: LFJ_DX(4, EPI_ADD); break;
+        }
+#undef LFJ_DX
+    }
+}
+template <bool PRO>
+__global__ __launch_bounds__(LF_BLOCK) void linear_fwd_jobs_kernel(const LfJobs t) {
+    linear_fwd_jobs_block<PRO>(t, blockIdx.x);
+}
+
+// Whether linear_fwd_jobs_kernel<PRO> has the form lf_launch<PRO> would pick for this job (a: the arguments of its single launch)
+template <bool PRO>
+static bool lf_job_ok(const LfArgs& a, int epi) {
+    if (a.M < 1 || a.Ci < 1 || a.Co < 1 || (a.Ci % 4) != 0 || (a.Co % 4) != 0) return false;
+    if (a.bias != nullptr || a.Xb != nullptr || a.Yb != nullptr || a.mask_ref != nullptr) return false;
+    if (lf_lds_bytes(a.Ci, a.Co, PRO) > 64 * 1024) return false;
+    const int tco = lf_tco(a.Ci, a.Co, PRO), nch = lf_hoist_chunks(a.Ci, true);
+    if (PRO) return a.transpose_w != 0 && nch == 1 && (epi == EPI_NONE || epi == EPI_ADD);
+    return a.transpose_w == 0 && epi == EPI_NONE && tco == 1 && a.Co <= 16 && (nch == 1 || nch == 2 || nch == 4);
+}
+
+// The job table of one launch: per job the plan of lf_launch (row workgroups, column slabs, instantiation); dynamic LDS is the largest of
+// the jobs' sizes (the body lays its slabs out from its own widths).  epi[j]: EPI_NONE, or EPI_ADD with a[j].addend.
+template <bool PRO>
+static int lf_jobs_plan(const LfArgs* a, const int* epi, int njobs, LfJobs& t, int64_t& blocks, size_t& lds) {
+    CRF_REQUIRE(a && njobs >= 1 && njobs <= LFJ_MAX, CRF_ERR_ARG, "1 .. %d jobs (got %d)", LFJ_MAX, njobs);
+    t = LfJobs{};
+    blocks = 0;
+    lds = 0;
+    for (int j = 0; j < njobs; ++j) {
+        const LfArgs& b = a[j];
+        CRF_REQUIRE(lf_job_ok<PRO>(b, epi[j]), CRF_ERR_UNSUPPORTED, "job %d: linear_fwd_jobs_kernel has no form pro=%d epi=%d for %lld x %d -> %d", j,
+                    (int)PRO, epi[j], (long long)b.M, b.Ci, b.Co);
+        const int tiles = (b.Co + 15) / 16, tco = lf_tco(b.Ci, b.Co, PRO);
+        t.X[j] = b.X; t.W[j] = b.W; t.Y[j] = b.Y; t.stat[j] = b.stat_partial; t.Y2[j] = b.Y2; t.pro[j] = b.pro;
+        t.addend[j] = epi[j] == EPI_ADD ? b.addend : nullptr;
+        t.M[j] = (long long)b.M; t.Ci[j] = b.Ci; t.Co[j] = b.Co; t.nbx[j] = lf_blocks(b.M); t.slope[j] = b.slope;
+        t.form[j] = PRO ? 2 * tco + (epi[j] == EPI_ADD ? 1 : 0) : lf_hoist_chunks(b.Ci, true);
+        t.blk_base[j] = (int)blocks;
+        blocks += (int64_t)t.nbx[j] * ((tiles + tco - 1) / tco);
+        const size_t need = lf_lds_bytes_at(b.Ci, tco, PRO);
+        if (need > lds) lds = need;
+    }
+    for (int j = njobs; j <= LFJ_MAX; ++j) t.blk_base[j] = (int)blocks;
+    t.njobs = njobs;
+    return CRF_OK;
+}
+template <bool PRO>
+static int lf_launch_jobs(const LfArgs* a, const int* epi, int njobs, crf_stream_t stream) {
+    LfJobs t;
+    int64_t blocks;
+    size_t lds;
+    if (int rc = lf_jobs_plan<PRO>(a, epi, njobs, t, blocks, lds)) return rc;
+    hipLaunchKernelGGL((linear_fwd_jobs_kernel<PRO>), dim3((unsigned)blocks), dim3(LF_BLOCK), lds, as_stream(stream), t);
     CRF_LAUNCH_CHECK();
     return CRF_OK;
 }

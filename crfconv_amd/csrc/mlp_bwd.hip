@@ -2,6 +2,8 @@
 // stands above mlp_channel_part): the streaming pass mlp_bwd_p1_kernel, its finalize, the batched end-of-pass dW launches
 // (mlp_dw_jobs_kernel, and the form that carries the CRF matrices' backward slabs of crf_matrices_body.hpp), and the dX product,
 // which is linear_fwd_kernel<.., PRO = true> of linear_fwd.hpp -- this unit instantiates those forms.
+// The narrow blocks of a fine-level CRF layer also run as JOBS -- up to four independent blocks per launch, each job its own single launch's
+// workgroups laid end to end (mlp_bwd_p1_jobs_kernel here, linear_fwd_jobs_kernel<true> of linear_fwd.hpp; crfconv_mlp_backward_jobs).
 #include "common.hpp"
 #include "gridsync.hpp"
 #include "wgrad_body.hpp"
@@ -200,6 +202,68 @@ __global__ __launch_bounds__(WG_BLOCK) void mlp_bwd_p1_kernel(const float* __res
     double* s_tot = s_buf + 4 * WG_BLOCK;
     sum_partial_rows_f64<WG_BLOCK>(pgr, (int)gridDim.x, 2 * Co, s_buf, s_tot);
     if ((int)threadIdx.x < Co) mlp_channel_part(threadIdx.x, s_tot[threadIdx.x], s_tot[Co + threadIdx.x], coef, M, Co, dgamma, dbeta, bcoef);
+}
+
+// The same statements as a device function of the workgroup's coordinates (bx, by, bz) in a grid of (nbx, nby, nbz), on LDS that the
+// caller owns: a job's own coordinates in mlp_bwd_p1_jobs_kernel.  mlp_bwd_p1_body.inc is a COPY of the kernel's statements above with the
+// coordinates spelled P1_BX / P1_BY / P1_BZ / P1_NBX, without the LDS declarations, and with the last workgroup counted among the JOB's
+// workgroups (tests/test_host_stream_jobs.py holds the two texts together).  The kernel does not call this function: through a call its
+// register counts move.  s_own: 5 WG_BLOCK doubles for the last workgroup's sums where TCO TCI < 3 (else they go inside s_red); it may lie
+// inside the caller's larger reduction buffer -- everybody has left that by then.
+template <int TCO, int TCI>
+__device__ __forceinline__ void mlp_bwd_p1_body(const float* __restrict__ GA, const float* __restrict__ Y, const float* __restrict__ X,
+                                                const float* __restrict__ X2, int split, const float* __restrict__ coef, float slope, int64_t M,
+                                                int Co, int Ci, int rows_per_block, float* __restrict__ PA, float* __restrict__ PB,
+                                                float* __restrict__ PG, float* __restrict__ PX, unsigned* __restrict__ ticket,
+                                                float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ bcoef,
+                                                const unsigned bx, const unsigned by, const unsigned bz, const unsigned nbx, const unsigned nby,
+                                                const unsigned nbz, float (&s_red)[WG_WAVES][TCO * TCI * 256],
+                                                float (&s_v)[WG_WAVES][(2 * TCO + TCI) * 16], double* s_own, int& s_flag) {
+#define P1_BX bx
+#define P1_BY by
+#define P1_BZ bz
+#define P1_NBX nbx
+#include "mlp_bwd_p1_body.inc"
+#undef P1_BX
+#undef P1_BY
+#undef P1_BZ
+#undef P1_NBX
+}
+
+// The pass of up to LFJ_MAX INDEPENDENT blocks in one launch: the jobs' own grids laid end to end (job j's workgroup (bx, by, bz) is
+// workgroup blk_base[j] + bx + nbx (by + nby bz)), each with its own workspace, its own block of LW_TICKET_WORDS ticket words and its own
+// last workgroup, which counts among the job's nbx nby nbz workgroups (last_workgroup_of).  Narrow outputs only: TCO = 1 (Co <= 16).
+struct MlpP1Jobs {                                       // (slots at or past njobs are never read)
+    const float* GA[LFJ_MAX]; const float* Y[LFJ_MAX]; const float* X[LFJ_MAX]; const float* coef[LFJ_MAX];
+    float* PA[LFJ_MAX]; float* PB[LFJ_MAX]; float* PG[LFJ_MAX]; float* PX[LFJ_MAX];
+    float* dgamma[LFJ_MAX]; float* dbeta[LFJ_MAX]; float* bcoef[LFJ_MAX];
+    long long M[LFJ_MAX];
+    int Co[LFJ_MAX], Ci[LFJ_MAX], rows_per_block[LFJ_MAX], nbx[LFJ_MAX], nbz[LFJ_MAX], tci[LFJ_MAX];
+    float slope[LFJ_MAX];
+    int blk_base[LFJ_MAX + 1];
+    int njobs;
+};
+__global__ __launch_bounds__(WG_BLOCK) void mlp_bwd_p1_jobs_kernel(const MlpP1Jobs t, unsigned* __restrict__ tickets) {
+    int j = 0;
+    while (j + 1 < t.njobs && t.blk_base[j + 1] <= (int)blockIdx.x) ++j;
+    const unsigned local = blockIdx.x - (unsigned)t.blk_base[j];
+    const unsigned nbx = (unsigned)uni(t.nbx[j]), nbz = (unsigned)uni(t.nbz[j]);
+    const unsigned bx = (unsigned)uni((int)(local % nbx)), bz = (unsigned)uni((int)(local / nbx));      // nby = 1: one 16-channel output slab
+    // one allocation for the widest form; the narrower forms' sums for the last workgroup go inside it as the wide form's do
+    __shared__ __attribute__((aligned(16))) float s_red[WG_WAVES * 4 * 256];
+    __shared__ float s_v[WG_WAVES * (2 + 4) * 16];
+    __shared__ int s_flag;
+    static_assert(sizeof(s_red) >= sizeof(double) * 5 * WG_BLOCK, "the last workgroup's sums fit the reduction buffer");
+    unsigned* ticket = uni(tickets) + j * LW_TICKET_WORDS;
+#define P1J(TCI) mlp_bwd_p1_body<1, TCI>(uni(t.GA[j]), uni(t.Y[j]), uni(t.X[j]), nullptr, 0, uni(t.coef[j]), uni(t.slope[j]), (int64_t)uni(t.M[j]), uni(t.Co[j]), \
+                                        uni(t.Ci[j]), uni(t.rows_per_block[j]), uni(t.PA[j]), uni(t.PB[j]), uni(t.PG[j]), uni(t.PX[j]), ticket, uni(t.dgamma[j]), \
+                                        uni(t.dbeta[j]), uni(t.bcoef[j]), bx, 0u, bz, nbx, 1u, nbz, *reinterpret_cast<float (*)[WG_WAVES][TCI * 256]>(s_red), \
+                                        *reinterpret_cast<float (*)[WG_WAVES][(2 + TCI) * 16]>(s_v), reinterpret_cast<double*>(s_red), s_flag)
+    const int tci = uni(t.tci[j]);
+    if (tci == 1) P1J(1);
+    else if (tci == 2) P1J(2);
+    else P1J(4);
+#undef P1J
 }
 
 // dW slots [64 block, 64 block + 64) of one MLP block's backward from its partial slabs (see mlp_bwd_finalize_kernel): shared by
@@ -508,6 +572,69 @@ extern "C" int crfconv_mlp_backward_cat(const float* gA, const float* Y, const f
                 CRF_ERR_ARG, "two-operand form: split=%d Ci=%d must be multiples of 4, dXa / dXb both or neither", split, Ci);
     return mlp_backward_impl(gA, Y, Xa, Xb, split, W, coef, slope, M, Ci, Co, dXa, dXb, dW, dgamma, dbeta, workspace,
                              workspace_bytes, ticket, stream);
+}
+
+// crfconv_mlp_backward_add for up to 4 INDEPENDENT blocks in TWO launches in all: pass 1 of every job (mlp_bwd_p1_jobs_kernel), then
+// every wanted dX product (linear_fwd_jobs_kernel<true>) -- per job the workgroups, summation orders, workspace slabs and results of its
+// own call.  Narrow blocks: Co in {4, 8, 16} (one output slab in pass 1, one k chunk in dX, the channel part by the last workgroup).
+extern "C" int crfconv_mlp_backward_p1_jobs_supported(int64_t M, int Ci, int Co) {
+    if (crfconv_mlp_backward_supported(M, Ci, Co) != 1) return 0;
+    const crf::MlpPlan p = crf::mlp_plan(M, Co, Ci);
+    return (p.tco == 1 && p.gy == 1 && 2 * Co <= crf::WG_BLOCK && crf::WG_BLOCK % (Co / 2) == 0 &&
+            (int64_t)p.nblk * 2 * Co * 4 < ((int64_t)1 << 31)) ? 1 : 0;
+}
+extern "C" int crfconv_mlp_backward_dx_jobs_supported(int64_t M, int Ci, int Co) {
+    crf::LfArgs a;
+    a.M = M; a.Ci = Co; a.Co = Ci; a.transpose_w = 1;
+    return crf::lf_job_ok<true>(a, crf::EPI_NONE) ? 1 : 0;
+}
+
+extern "C" int crfconv_mlp_backward_jobs(const crf_mlp_stream_bwd_job* jobs, int njobs, unsigned* tickets, crf_stream_t stream) {
+    CRF_REQUIRE(jobs && tickets && njobs >= 1 && njobs <= crf::LFJ_MAX, CRF_ERR_ARG, "1 .. %d jobs (got %d) and their ticket words", crf::LFJ_MAX, njobs);
+    hipStream_t st = crf::as_stream(stream);
+    crf::MlpP1Jobs t{};
+    crf::LfArgs dx[crf::LFJ_MAX];
+    int epi[crf::LFJ_MAX], ndx = 0;
+    int64_t blocks = 0;
+    for (int j = 0; j < njobs; ++j) {
+        const crf_mlp_stream_bwd_job& b = jobs[j];
+        CRF_REQUIRE(b.gA && b.Y && b.X && b.W && b.coef && b.dgamma && b.dbeta && b.workspace, CRF_ERR_ARG, "job %d: null pointer", j);
+        CRF_REQUIRE(b.dX != nullptr || b.dX_add == nullptr, CRF_ERR_ARG, "job %d: dX_add without dX", j);
+        CRF_REQUIRE(crfconv_mlp_backward_p1_jobs_supported(b.M, b.Ci, b.Co) == 1 && crfconv_mlp_backward_dx_jobs_supported(b.M, b.Ci, b.Co) == 1,
+                    CRF_ERR_UNSUPPORTED, "job %d: shape M=%lld Ci=%d Co=%d is not a narrow row-streaming block", j, (long long)b.M, b.Ci, b.Co);
+        CRF_REQUIRE(b.workspace_bytes >= crfconv_mlp_backward_workspace(b.M, b.Ci, b.Co), CRF_ERR_WORKSPACE, "job %d: workspace too small", j);
+        char* base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(b.workspace) + 255) & ~(uintptr_t)255);
+        size_t off[5];
+        crf::mlp_ws_layout(b.M, b.Co, b.Ci, off);
+        const crf::MlpPlan p = crf::mlp_plan(b.M, b.Co, b.Ci);
+        t.GA[j] = b.gA; t.Y[j] = b.Y; t.X[j] = b.X; t.coef[j] = b.coef;
+        t.PA[j] = reinterpret_cast<float*>(base + off[0]); t.PB[j] = reinterpret_cast<float*>(base + off[1]);
+        t.PG[j] = reinterpret_cast<float*>(base + off[2]); t.PX[j] = reinterpret_cast<float*>(base + off[3]);
+        t.bcoef[j] = reinterpret_cast<float*>(base + off[4]);
+        t.dgamma[j] = b.dgamma; t.dbeta[j] = b.dbeta; t.M[j] = (long long)b.M; t.Co[j] = b.Co; t.Ci[j] = b.Ci;
+        t.rows_per_block[j] = p.rows_per_block; t.nbx[j] = p.nblk; t.nbz[j] = p.gz; t.tci[j] = p.tci; t.slope[j] = b.slope;
+        t.blk_base[j] = (int)blocks;
+        blocks += (int64_t)p.nblk * p.gz;
+        if (b.dX != nullptr) {
+            crf::LfArgs& a = dx[ndx];
+            a.X = b.gA; a.W = b.W; a.M = b.M; a.Ci = b.Co; a.Co = b.Ci; a.transpose_w = 1; a.Y = b.dX;
+            a.Y2 = b.Y; a.pro = t.bcoef[j]; a.slope = b.slope; a.addend = b.dX_add;
+            epi[ndx++] = b.dX_add != nullptr ? crf::EPI_ADD : crf::EPI_NONE;
+        }
+    }
+    for (int j = njobs; j <= crf::LFJ_MAX; ++j) t.blk_base[j] = (int)blocks;
+    t.njobs = njobs;
+    hipLaunchKernelGGL(crf::mlp_bwd_p1_jobs_kernel, dim3((unsigned)blocks), dim3(crf::WG_BLOCK), 0, st, t, tickets);
+    CRF_LAUNCH_CHECK();
+    for (int j = 0; j < njobs; ++j) {              // a weight gradient wanted now (not deferred to crfconv_mlp_dw_jobs): that job's dW workgroups
+        const crf_mlp_stream_bwd_job& b = jobs[j];
+        if (b.dW == nullptr) continue;
+        const int nw = (int)crf::cdiv((int64_t)b.Co * b.Ci, 64);
+        hipLaunchKernelGGL(crf::mlp_bwd_finalize_kernel, dim3((unsigned)nw), dim3(crf::MF_BLOCK), 0, st, t.PA[j], t.PB[j], t.PG[j], t.PX[j], t.nbx[j], b.coef,
+                           b.M, b.Co, b.Ci, nw, b.dW, b.dgamma, b.dbeta, t.bcoef[j]);
+        CRF_LAUNCH_CHECK();
+    }
+    return ndx > 0 ? crf::lf_launch_jobs<true>(dx, epi, ndx, stream) : CRF_OK;
 }
 
 // dW of any number of MLP blocks whose crfconv_mlp_backward(_add / _cat) call was given dW = NULL, from the workspaces those

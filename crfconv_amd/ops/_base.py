@@ -85,6 +85,17 @@ def _mlp_ticket(device):
     return ptr(_ticket(device))
 
 
+_STREAM_TICKETS = {}
+STREAM_GROUP_MAX = 4           # jobs of one crfconv_mlp_backward_jobs call (GG_MAX / LFJ_MAX of csrc/)
+
+
+def _stream_tickets(device):
+    """One block of ticket words per job of a row-streaming group's backward (crfconv_mlp_backward_jobs: every job has its own last
+    workgroup), zero and left zero, per (device, stream)."""
+    return _stream_buf(_STREAM_TICKETS, device,
+                       lambda: torch.zeros(STREAM_GROUP_MAX * (_lib.load().crfconv_ticket_bytes() // 4), dtype=torch.int32, device=device))
+
+
 _sync_ws = {}
 
 
@@ -189,6 +200,9 @@ class _State:
     small_bwd_one_launch = __import__('os').environ.get('CRFCONV_SMALL_BWD_TWO_LAUNCHES') is None
     # the backward of the CRF layers' matrices as riders of the MLP blocks' end-of-pass weight-gradient launch (defer._flush_mlp_dw)
     dw_hosts_mats = __import__('os').environ.get('CRFCONV_NO_TAIL_RIDERS') is None
+    # independent narrow row-streaming MLP blocks of a fine-level CRF layer as one node of two launches each way (ops.mlp._MLPStreamGroup);
+    # CRFCONV_NO_STREAM_GROUPS=1: one node per block again, the launch sequence from before the groups (A/B runs of bench.py)
+    no_stream_groups = __import__('os').environ.get('CRFCONV_NO_STREAM_GROUPS') is not None
     # the d = 128 PointConv layers' parameter pass on the matrix pipe beside d = 32 / 64 (csrc/pointconv_wide_params.hip: a pair of wavefronts per
     # point); CRFCONV_NO_WIDE128=1: the dump + GEMM + a1 passes for them again (A/B runs of bench.py)
     no_wide128 = __import__('os').environ.get('CRFCONV_NO_WIDE128') is not None

@@ -6,7 +6,7 @@ import torch
 
 from .. import _lib
 from ..graph import ptr, require_gpu, stream_ptr
-from ._base import _f32c, _mlp_ticket, _ticket, gridsync_ws, state
+from ._base import _f32c, _mlp_ticket, _stream_tickets, _ticket, gridsync_ws, state
 
 # ------------------------------------------------------------------------------ Linear -> BatchNorm -> LeakyReLU as one op
 
@@ -739,21 +739,171 @@ class _MLPSmallGroup(torch.autograd.Function):
         return tuple(rets)
 
 
+class _MLPStreamGroup(torch.autograd.Function):
+    """_MLPSmallGroup for the narrow blocks of the FINE levels (each _MLPBlock's arithmetic, bit for bit): n independent row-streaming
+    blocks as one node -- forward ONE product launch with every block's statistic records (crfconv_linear_forward_jobs) and ONE
+    coefficient + apply launch (crfconv_bn_apply_from_records_jobs), backward TWO launches for all blocks (crfconv_mlp_backward_jobs:
+    pass 1 of every block, then every dX product).  At these widths (<= 16 outputs) a launch is a few hundred workgroups waiting on
+    memory round trips, not bytes: unary_nn[i] / pairwise_nn[i] of the finest CRF layer run side by side for about the longer one's time.
+    Per block: (x, W, gamma, beta, run_mean, run_var, momentum, eps, slope, fork); a block with fork returns (out, x_alias).
+    tiled (one flag per block; the MIXED pair of the level-1 CRF layer): that block lies below the switch-over and is _MLPSmall's
+    launch-separated arithmetic (_small_fwd's tiled product with statistic records) -- its product rides the same forward launch as the
+    first workgroups (crf_linear_job.tiled), and the backward of such a group runs the members' own paths one after the other
+    (_small_bwd, _stream_bwd)."""
+
+    NARG = 10
+    calls = 0                                          # forwards run through the node (tests: the grouped path was really taken)
+
+    @staticmethod
+    def forward(ctx, tiled, *args):
+        n = len(args) // _MLPStreamGroup.NARG
+        jobs = [args[i * _MLPStreamGroup.NARG:(i + 1) * _MLPStreamGroup.NARG] for i in range(n)]
+        lib = _lib.load()
+        st = stream_ptr()
+        keep, outs, prm, slopes, forks, tmp = [], [], [], [], [], []
+        lf = (_lib.LinearJob * n)()
+        ba = (_lib.BnApplyJob * n)()
+        order = sorted(range(n), key=lambda i: not tiled[i])      # the tiled jobs first in the product's job array
+        for i, (x_in, W, gamma, beta, rm, rv, mom, eps, slope, fork) in enumerate(jobs):
+            x, Wc = x_in.contiguous(), W.contiguous()
+            m, ci = x.shape
+            co = Wc.shape[0]
+            dev = x.device
+            y = torch.empty((m, co), dtype=torch.float32, device=dev)
+            out = torch.empty_like(y)
+            coef = torch.empty(4 * co, dtype=torch.float32, device=dev)
+            nrec = lib.crfconv_gemm_stat_records(m) if tiled[i] else lib.crfconv_linear_forward_stat_records(m)
+            rec = torch.empty((nrec, 4, co), dtype=torch.float32, device=dev)
+            g, b = _f32c(gamma), _f32c(beta)
+            lf[order.index(i)] = _lib.LinearJob(x.data_ptr(), Wc.data_ptr(), m, ci, co, y.data_ptr(), rec.data_ptr(), 1 if tiled[i] else 0)
+            ba[i] = _lib.BnApplyJob(rec.data_ptr(), nrec, y.data_ptr(), m, co, g.data_ptr(), b.data_ptr(),
+                                    None if rm is None else rm.data_ptr(), None if rv is None else rv.data_ptr(), float(mom), float(eps),
+                                    None, float(slope), coef.data_ptr(), out.data_ptr())
+            keep += [x, Wc, y, coef]
+            prm.append((W, gamma, beta))
+            slopes.append(float(slope))
+            forks.append(bool(fork))
+            outs.append(out)
+            if fork:
+                outs.append(x_in)
+            tmp.append((rec, g, b))                    # alive until the launches below are queued
+        _lib.call('crfconv_linear_forward_jobs', lf, n, st)
+        _lib.call('crfconv_bn_apply_from_records_jobs', ba, n, st)
+        del tmp
+        _MLPStreamGroup.calls += 1
+        ctx.n, ctx.prm, ctx.slopes, ctx.forks, ctx.tiled = n, prm, slopes, forks, tuple(bool(t) for t in tiled)
+        ctx.save_for_backward(*keep)
+        ctx.set_materialize_grads(False)
+        return tuple(outs)
+
+    @staticmethod
+    def _backward_one_by_one(ctx, grads):
+        """A mixed group: every member's own backward path, in member order -- _MLPSmall's for a tiled member, _MLPBlock's for the others."""
+        saved = ctx.saved_tensors
+        rets, gi = [None], 0
+        for i in range(ctx.n):
+            x, W, y, coef = saved[4 * i:4 * i + 4]
+            gA = grads[gi]
+            gi += 1
+            g_alias = None
+            if ctx.forks[i]:
+                g_alias = grads[gi]
+                gi += 1
+            gA = torch.zeros_like(y) if gA is None else gA.contiguous()
+            want_dx = ctx.needs_input_grad[1 + i * _MLPStreamGroup.NARG]
+            Wp, gp, bp = ctx.prm[i]
+            if ctx.tiled[i]:
+                outs = [_param_out(q, (W.shape[0],), x.device) for q in (gp, bp)]
+                gY, dX = _small_bwd(gA, y, coef, W, None if g_alias is None else g_alias.reshape(x.shape), ctx.slopes[i], outs[0][0], outs[1][0],
+                                    want_dx)
+                dW = _weight_grad(gY, x, (Wp, None), False)[0]
+                part = (dX, dW, _param_ret(gp, outs[0][0], outs[0][1]), _param_ret(bp, outs[1][0], outs[1][1]))
+            else:
+                part = _stream_bwd(ctx.prm[i], x, W, y, coef, gA, ctx.slopes[i], want_dx, True, g_alias)
+            rets += [*part, None, None, None, None, None, None]
+        return tuple(rets)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        if any(ctx.tiled):
+            return _MLPStreamGroup._backward_one_by_one(ctx, grads)
+        n = ctx.n
+        saved = ctx.saved_tensors
+        lib = _lib.load()
+        per, gi = [], 0
+        jobs = (_lib.MlpStreamBwdJob * n)()
+        for i in range(n):
+            x, W, y, coef = saved[4 * i:4 * i + 4]
+            m, ci = x.shape
+            co = W.shape[0]
+            dev = x.device
+            gA = grads[gi]
+            gi += 1
+            g_alias = None
+            if ctx.forks[i]:
+                g_alias = grads[gi]
+                gi += 1
+            gA = torch.zeros_like(y) if gA is None else gA.contiguous()
+            want_dx = ctx.needs_input_grad[1 + i * _MLPStreamGroup.NARG]
+            outs, dfr = _mlp_param_outs(ctx.prm[i], W, dev)       # as _stream_bwd: (dW, dgamma, dbeta) targets, dW left to the end of the pass
+            nbytes = lib.crfconv_mlp_backward_workspace(m, ci, co)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            dX = torch.empty_like(x) if want_dx else None
+            add = _f32c(g_alias).reshape(m, ci) if (g_alias is not None and want_dx) else None
+            jobs[i] = _lib.MlpStreamBwdJob(gA.data_ptr(), y.data_ptr(), x.data_ptr(), W.data_ptr(), coef.data_ptr(), ctx.slopes[i], m, ci, co,
+                                           None if add is None else add.data_ptr(), None if dX is None else dX.data_ptr(),
+                                           None if dfr else outs[0][0].data_ptr(), outs[1][0].data_ptr(), outs[2][0].data_ptr(),
+                                           ws.data_ptr(), nbytes)
+            per.append((dX, outs, dfr, ws, m, ci, co, coef, gA, add))      # (gA and add stay alive until the launches are queued)
+        _lib.call('crfconv_mlp_backward_jobs', jobs, n, ptr(_stream_tickets(saved[0].device)), stream_ptr())
+        rets = [None]
+        for i, (dX, outs, dfr, ws, m, ci, co, coef, _, _) in enumerate(per):
+            rets += [dX, *_mlp_param_rets(ctx.prm[i], outs, dfr, ws, m, ci, co, coef), None, None, None, None, None, None]
+        return tuple(rets)
+
+
+def _stream_group_ok(lib, m, ci, co):
+    """A training-mode row-streaming block (mlp_block_ok's conditions) of a shape all three job launches take."""
+    return (not _mlp_small_ok(m, ci, co) and _mfma_ok(m, ci, co) and co % 4 == 0 and lib.crfconv_mlp_backward_supported(m, ci, co) == 1
+            and lib.crfconv_linear_forward_jobs_supported(m, ci, co) == 1 and lib.crfconv_mlp_backward_p1_jobs_supported(m, ci, co) == 1
+            and lib.crfconv_mlp_backward_dx_jobs_supported(m, ci, co) == 1)
+
+
+def _stream_group_tiled_ok(lib, m, ci, co):
+    """A coarse-level block whose forward _small_fwd runs launch-separated (tiled product with statistic records, then the apply): past the
+    one-launch kernel's limit, in the tile class the row-streaming job launch can carry, with _MLPSmall's backward."""
+    return (_mlp_small_ok(m, ci, co) and not (not state.small_mlp_disabled and lib.crfconv_mlp_small_supported(m, ci, co) == 1)
+            and lib.crfconv_mlp_small_backward_supported(m, ci, co) == 1 and lib.crfconv_linear_forward_jobs_tiled_supported(m, ci, co) == 1)
+
+
 def mlp_group(blocks, shared=False, input_mask=None):
     """[(x [.., Ci], W, bn, slope, fork)] -> per block its output (or (out, x_alias) with fork), all blocks in ONE node -- or None when
-    the group form does not apply to every block (training-mode coarse-level blocks: _mlp_small_ok rows, affine float32 BatchNorm with
-    running statistics, widths the two-launch backward takes).  shared: blocks 0 and 1 read the same tensor.  input_mask (shared): the
+    no group form applies to every block: training-mode coarse-level blocks (_mlp_small_ok rows, affine float32 BatchNorm with
+    running statistics, widths the two-launch backward takes: _MLPSmallGroup), or -- not shared -- narrow row-streaming blocks of the fine
+    levels (_stream_group_ok: _MLPStreamGroup), among them up to two blocks of the level just below the switch-over
+    (_stream_group_tiled_ok: the mixed pair).  shared: blocks 0 and 1 read the same tensor.  input_mask (shared): the
     JoinMask of the join that produced that tensor, given by a caller who knows that its every other use goes through block 0's alias."""
     if not (2 <= len(blocks) <= 4):
         return None
     lib = _lib.load()
     args, shapes = [], []
+    dims = []
     for x, W, bn, slope, fork in blocks:
         ci, co = x.shape[-1], W.shape[0]
         m = x.numel() // max(ci, 1)
         if not (x.is_cuda and x.dtype == torch.float32 and W.dtype == torch.float32 and bn.affine and bn.running_mean is not None
-                and m >= 1 and _mlp_small_ok(m, ci, co) and ci % 4 == 0 and co % 4 == 0
-                and lib.crfconv_mlp_small_backward_supported(m, ci, co) == 1):
+                and m >= 1 and ci % 4 == 0 and co % 4 == 0):
+            return None
+        dims.append((m, ci, co))
+    small = all(_mlp_small_ok(*d) and lib.crfconv_mlp_small_backward_supported(*d) == 1 for d in dims)
+    tiled = ()
+    if not small:
+        if shared or state.no_stream_groups:
+            return None
+        if len({id(b[2]) for b in blocks}) != len(blocks) or len({id(b[1]) for b in blocks}) != len(blocks):
+            return None                                # not independent: the jobs of one launch would update one BatchNorm's running statistics
+        tiled = tuple(_stream_group_tiled_ok(lib, *d) for d in dims)
+        if sum(tiled) > 2 or all(tiled) or not all(t or _stream_group_ok(lib, *d) for t, d in zip(tiled, dims)):
             return None
     if shared and (state.no_fork or blocks[0][0] is not blocks[1][0]):
         return None                                    # (tests: the un-forked graph runs the blocks one by one)
@@ -764,7 +914,7 @@ def mlp_group(blocks, shared=False, input_mask=None):
         args += [xa, W, *_bn_args(bn), float(slope), use_fork]
         shapes.append((x.shape, W.shape[0], fork, use_fork))
     fold = input_mask if (shared and len(blocks) == 2 and args[9]) else None      # block 0 forks: its alias carries the other uses
-    res = list(_MLPSmallGroup.apply(bool(shared), fold, *args))
+    res = list(_MLPSmallGroup.apply(bool(shared), fold, *args) if small else _MLPStreamGroup.apply(tiled, *args))
     out = []
     for (xs, co, fork, use_fork), (x, _, _, _, _) in zip(shapes, blocks):
         o = res.pop(0).reshape(xs[:-1] + (co,))
