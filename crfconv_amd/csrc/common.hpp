@@ -29,6 +29,7 @@ __device__ __forceinline__ long long uni(long long v) {
 
 
 constexpr int WAVE = 64;  // gfx950 wavefront
+using f32x4 = __attribute__((ext_vector_type(4))) float;     // the accumulator of one 16x16 fp32 MFMA tile
 
 // ----------------------------------------------------------------------------- errors
 void set_error(const char* fmt, ...);

@@ -33,8 +33,6 @@
 
 namespace crf {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
 constexpr int HD_BLOCK = 256, HD_WAVES = HD_BLOCK / WAVE;
 constexpr int HD_CO = 128, HD_T = HD_CO / 16;       // hidden width (4 C) and its 16-channel tiles
 constexpr int HD_C2P = 16;                         // classes, padded to one tile

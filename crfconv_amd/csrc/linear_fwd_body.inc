@@ -1,6 +1,13 @@
-// A copy of the statements of linear_fwd_kernel (linear_fwd.hpp) for linear_fwd_body, the device function that linear_fwd_jobs_kernel calls:
-// blockIdx.x, blockIdx.y and gridDim.x are spelled LF_BX, LF_BY and LF_NBX (the job's own coordinates and block count); nothing else differs.
-// A change to the kernel's statements is made in both places (tests/test_host_stream_jobs.py compares them).
+// The statements of the row-streaming product, included by linear_fwd_kernel and by linear_fwd_body (linear_fwd.hpp), the device function that
+// linear_fwd_jobs_kernel calls.  The two include this text and neither calls the other: through a call the single kernels' registers move
+// (profiles/r31_stream_groups.md).  The includer provides
+//   the template parameters TCO, PRO, VEC4, EPI, NCH;
+//   the parameters X, W, bias, M, Ci, Co, transpose_w, Y, stat_partial, Y2, pro, slope, Xb, xsplit, Yb, ysplit, addend, drop_counter,
+//     drop_seed, drop_threshold, drop_scale, mask_ref, mask_slope, uv  (linear_fwd_kernel's list);
+//   sW, the launch's dynamic LDS as a float array: [16*TCO][Cip] (+ [5][Cik] prologue coefficients) (+ the output staging tiles);
+//   the macros LF_BX, LF_BY (the workgroup's row and column-slab coordinates) and LF_NBX (the row workgroups of its grid): the launch's
+//     own in the kernel, the job's in the body function.  The text never reads the launch's coordinates itself.
+// The tunables and the rule PF<NCH> (the next row group's fragments in flight too) are linear_fwd.hpp's, beside the planning helpers.
     static_assert(EPI != EPI_ADD_MASK || (PRO && VEC4), "the masked epilogue is the aligned dX product's");
     static_assert(EPI != EPI_UV || (!PRO && VEC4 && NCH == 1), "the combine prologue is the narrow aligned forward's");
     static_assert(EPI != EPI_BN_ACT || !PRO, "the BatchNorm epilogue is the forward product's");
@@ -15,7 +22,6 @@
     // Xb / xsplit: the operand is the column concatenation [X | Xb] split at column xsplit (the fusion layers' torch.cat,
     // never materialised); Yb / ysplit: the output columns >= ysplit go to Yb [M, Co - ysplit] (dX of such a layer).
     // Both splits are multiples of 4.
-    extern __shared__ float sW[];                 // [16*TCO][Cip] (+ [5][Cik] prologue coefficients)
     const int Cip = ((Ci + 15) / 16) * 16 + 4;
     const int Cik = ((Ci + 15) / 16) * 16;
     float* sPro = sW + 16 * TCO * Cip;
@@ -169,9 +175,8 @@
     // write-heavy shapes run at the ~2.7 TB/s HBM WRITE rate -- 163840 x 8 -> 32 moves 21 MB out in 13 us -- not at a
     // per-wavefront latency limit.)
     constexpr int NCA = NCH > 0 ? NCH : 1;
-    constexpr bool PF = NCH > 0 && NCH <= LF_PF_MAX_;                 // next group's fragments in flight too
     const int64_t row_stride = (int64_t)LF_NBX * (LF_BLOCK / WAVE) * 16;
-    [[maybe_unused]] float4 fa[NCA], fb[TWO ? NCA : 1], na[PF ? NCA : 1], nb[(PF && TWO) ? NCA : 1];
+    [[maybe_unused]] float4 fa[NCA], fb[TWO ? NCA : 1], na[PF<NCH> ? NCA : 1], nb[(PF<NCH> && TWO) ? NCA : 1];
     [[maybe_unused]] auto load_group = [&](int64_t rw0, float4 (&xa)[NCA], float4 (&xb)[TWO ? NCA : 1]) {
         const int64_t rq = rw0 + rr;
         const bool ok = rw0 < M && rq < M;
@@ -183,7 +188,7 @@
             if constexpr (TWO) xb[c] = t1;
         }
     };
-    if constexpr (PF) load_group(((int64_t)LF_BX * (LF_BLOCK / WAVE) + wave) * 16, fa, fb);
+    if constexpr (PF<NCH>) load_group(((int64_t)LF_BX * (LF_BLOCK / WAVE) + wave) * 16, fa, fb);
     for (int64_t row0 = ((int64_t)LF_BX * (LF_BLOCK / WAVE) + wave) * 16; row0 < M; row0 += row_stride) {
         const int64_t r = row0 + rr;
         const bool rv = r < M;
@@ -191,7 +196,7 @@
 #pragma unroll
         for (int t = 0; t < TCO; ++t) acc[t] = f32x4{bsel[t][0], bsel[t][1], bsel[t][2], bsel[t][3]};
         if constexpr (NCH > 0) {
-            if constexpr (PF) {
+            if constexpr (PF<NCH>) {
                 if constexpr (TWO) load_group(row0 + row_stride, na, nb);
                 else load_group(row0 + row_stride, na, fb);
             } else {
@@ -212,7 +217,7 @@
                     acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv.w, xv.w, acc[t], 0, 0, 0);
                 }
             }
-            if constexpr (PF) {
+            if constexpr (PF<NCH>) {
 #pragma unroll
                 for (int c = 0; c < NCH; ++c) {
                     fa[c] = na[c];

@@ -40,6 +40,11 @@ __device__ __forceinline__ void mlp_channel_part(int c, double s1, double s2, co
     bcoef[4 * Co + c] = (float)(-a * c2 + a * c3 * rs * mu);
 }
 
+// Where the last workgroup of the pass keeps its 5 WG_BLOCK doubles (10 KB) of channel sums: inside s_red, the cross-wave reduction buffer
+// of TCO TCI 4 KB (everybody has left it by then), when that is large enough; else in an array of their own (s_own).
+template <int TCO, int TCI>
+constexpr bool P1_ALIAS = TCO * TCI >= 3;
+
 template <int TCO, int TCI>
 __global__ __launch_bounds__(WG_BLOCK) void mlp_bwd_p1_kernel(const float* __restrict__ GA, const float* __restrict__ Y,
                                                               const float* __restrict__ X,
@@ -53,163 +58,29 @@ __global__ __launch_bounds__(WG_BLOCK) void mlp_bwd_p1_kernel(const float* __res
                                                               unsigned* __restrict__ ticket /*null: mlp_bwd_finalize_kernel does the channel part*/,
                                                               float* __restrict__ dgamma, float* __restrict__ dbeta,
                                                               float* __restrict__ bcoef) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int co_base = blockIdx.y * 16 * TCO, ci_base = blockIdx.z * 16 * TCI;
-    const int kk = lane >> 4, cc = lane & 15;
-    f32x4 accA[TCO][TCI], accB[TCO][TCI];
-#pragma unroll
-    for (int a = 0; a < TCO; ++a)
-#pragma unroll
-        for (int b = 0; b < TCI; ++b) { accA[a][b] = f32x4{0.f, 0.f, 0.f, 0.f}; accB[a][b] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-    float ca[TCO], cb[TCO], cm[TCO], cr[TCO], sg[TCO], sgy[TCO], sx[TCI];
-#pragma unroll
-    for (int a = 0; a < TCO; ++a) {
-        const int co = co_base + 16 * a + cc;
-        const bool ok = co < Co;
-        ca[a] = ok ? coef[co] : 0.f;
-        cb[a] = ok ? coef[Co + co] : 0.f;
-        cm[a] = ok ? coef[2 * Co + co] : 0.f;
-        cr[a] = ok ? coef[3 * Co + co] : 0.f;
-        sg[a] = 0.f;
-        sgy[a] = 0.f;
-    }
-#pragma unroll
-    for (int b = 0; b < TCI; ++b) sx[b] = 0.f;
-
-    const int64_t row_begin = (int64_t)blockIdx.x * rows_per_block;
-    const int64_t row_end = row_begin + rows_per_block < M ? row_begin + rows_per_block : M;
-#ifndef P1_PREFETCH_
-#define P1_PREFETCH_ 0
-#endif
-    struct Frag { float gv[4][TCO], yv[4][TCO], bv[4][TCI]; };
-    auto load = [&](int64_t r0, Frag& f) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int64_t r = r0 + 4 * u + kk;
-            const bool rv = r < row_end;
-#pragma unroll
-            for (int a = 0; a < TCO; ++a) {
-                const int co = co_base + 16 * a + cc;
-                const bool ok = rv && co < Co;
-                f.gv[u][a] = ok ? GA[r * Co + co] : 0.f;
-                f.yv[u][a] = ok ? Y[r * Co + co] : cm[a];          // yh = 0 on padding
-            }
-#pragma unroll
-            for (int b = 0; b < TCI; ++b) {
-                const int ci = ci_base + 16 * b + cc;
-                float xv = 0.f;
-                if (rv && ci < Ci) xv = (X2 == nullptr || ci < split) ? X[r * (X2 ? split : Ci) + ci] : X2[r * (Ci - split) + (ci - split)];
-                f.bv[u][b] = xv;
-            }
-        }
-    };
-    auto compute = [&](const Frag& f) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-#pragma unroll
-            for (int b = 0; b < TCI; ++b) sx[b] += f.bv[u][b];
-#pragma unroll
-            for (int a = 0; a < TCO; ++a) {
-                const float g1 = f.gv[u][a] * (fmaf(ca[a], f.yv[u][a], cb[a]) > 0.f ? 1.f : slope);
-                const float yh = (f.yv[u][a] - cm[a]) * cr[a];
-                sg[a] += g1;
-                sgy[a] = fmaf(g1, yh, sgy[a]);
-#pragma unroll
-                for (int b = 0; b < TCI; ++b) {
-                    accA[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(g1, f.bv[u][b], accA[a][b], 0, 0, 0);
-                    accB[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(yh, f.bv[u][b], accB[a][b], 0, 0, 0);
-                }
-            }
-        }
-    };
-    if constexpr (P1_PREFETCH_ != 0) {
-        // the next 16-row group's fragments are requested before this group's products (rows past the slice load nothing)
-        Frag cur, nxt;
-        load(row_begin + 16 * wave, cur);
-        for (int64_t r0 = row_begin + 16 * wave; r0 < row_end; r0 += 16 * WG_WAVES) {
-            load(r0 + 16 * WG_WAVES, nxt);
-            compute(cur);
-            cur = nxt;
-        }
-    } else {
-        for (int64_t r0 = row_begin + 16 * wave; r0 < row_end; r0 += 16 * WG_WAVES) {
-            Frag f;
-            load(r0, f);
-            compute(f);
-        }
-    }
-    // C/D layout of 16x16x4: col = lane & 15 (j = ci), row = 4 * (lane >> 4) + reg (i = co)
     __shared__ __attribute__((aligned(16))) float s_red[WG_WAVES][TCO * TCI * 256];
     __shared__ float s_v[WG_WAVES][(2 * TCO + TCI) * 16];
-    const int64_t pb = (int64_t)blockIdx.x;
-    for (int pass = 0; pass < 2; ++pass) {
-        if (pass) __syncthreads();
-#pragma unroll
-        for (int a = 0; a < TCO; ++a)
-#pragma unroll
-            for (int b = 0; b < TCI; ++b)
-#pragma unroll
-                for (int g = 0; g < 4; ++g)
-                    s_red[wave][(a * TCI + b) * 256 + (4 * kk + g) * 16 + cc] = pass ? accB[a][b][g] : accA[a][b][g];
-        if (pass == 0) {
-            // per-channel sums: lanes with the same cc over the 4 k-groups
-#pragma unroll
-            for (int a = 0; a < TCO; ++a) {
-                float t1 = sg[a], t2 = sgy[a];
-                t1 += __shfl_xor(t1, 16, WAVE); t1 += __shfl_xor(t1, 32, WAVE);
-                t2 += __shfl_xor(t2, 16, WAVE); t2 += __shfl_xor(t2, 32, WAVE);
-                if (kk == 0) { s_v[wave][a * 16 + cc] = t1; s_v[wave][(TCO + a) * 16 + cc] = t2; }
-            }
-#pragma unroll
-            for (int b = 0; b < TCI; ++b) {
-                float t1 = sx[b];
-                t1 += __shfl_xor(t1, 16, WAVE); t1 += __shfl_xor(t1, 32, WAVE);
-                if (kk == 0) s_v[wave][(2 * TCO + b) * 16 + cc] = t1;
-            }
-        }
-        __syncthreads();
-        float* dst = pass ? PB : PA;
-        for (int t = threadIdx.x; t < TCO * TCI * 256; t += WG_BLOCK) {
-            float v = 0.f;
-#pragma unroll
-            for (int w = 0; w < WG_WAVES; ++w) v += s_red[w][t];
-            const int tile = t >> 8, a = tile / TCI, b = tile % TCI, i = (t >> 4) & 15, j = t & 15;
-            const int co = co_base + 16 * a + i, ci = ci_base + 16 * b + j;
-            if (co < Co && ci < Ci) dst[(pb * Co + co) * Ci + ci] = v;
-        }
-    }
-    const __amdgpu_buffer_rsrc_t pgr = make_rsrc(PG, (int)gridDim.x * 2 * Co * 4);
-    for (int t = threadIdx.x; t < (2 * TCO + TCI) * 16; t += WG_BLOCK) {
-        float v = 0.f;
-#pragma unroll
-        for (int w = 0; w < WG_WAVES; ++w) v += s_v[w][t];
-        const int grp = t >> 4, c16 = t & 15;
-        if (grp < 2 * TCO) {                                   // sum g1 | sum g1 yh: slabs of ci-slab 0 only
-            const int which = grp / TCO, co = co_base + 16 * (grp % TCO) + c16;
-            if (blockIdx.z == 0 && co < Co) st1_sc1(pgr, (((int)pb * 2 + which) * Co + co) * 4, v);   // write-through: summed in this launch
-        } else {                                               // column sums of X: slabs of co-slab 0 only
-            const int ci = ci_base + 16 * (grp - 2 * TCO) + c16;
-            if (blockIdx.y == 0 && ci < Ci) PX[pb * Ci + ci] = v;
-        }
-    }
-    // The channel part of the finalize (dgamma, dbeta, the coefficients of gY for the dX pass) by the LAST workgroup of this launch
-    // to finish (gridsync.hpp): the launch between the two passes of the block's backward disappears.  2 Co <= WG_BLOCK slots.
-    constexpr bool ALIAS = TCO * TCI >= 3;                     // the 10 KB of sums inside s_red (everybody has left it by then)
-    __shared__ double s_own[ALIAS ? 1 : 5 * WG_BLOCK];
+    __shared__ double s_own[P1_ALIAS<TCO, TCI> ? 1 : 5 * WG_BLOCK];
     __shared__ int s_flag;
-    if (ticket == nullptr || !last_workgroup(ticket, gridDim.x * gridDim.y * gridDim.z, &s_flag)) return;
-    double* s_buf = ALIAS ? reinterpret_cast<double*>(&s_red[0][0]) : s_own;
-    double* s_tot = s_buf + 4 * WG_BLOCK;
-    sum_partial_rows_f64<WG_BLOCK>(pgr, (int)gridDim.x, 2 * Co, s_buf, s_tot);
-    if ((int)threadIdx.x < Co) mlp_channel_part(threadIdx.x, s_tot[threadIdx.x], s_tot[Co + threadIdx.x], coef, M, Co, dgamma, dbeta, bcoef);
+#define P1_BX blockIdx.x
+#define P1_BY blockIdx.y
+#define P1_BZ blockIdx.z
+#define P1_NBX gridDim.x
+#define P1_LAST last_workgroup(ticket, gridDim.x * gridDim.y * gridDim.z, &s_flag)
+#include "mlp_bwd_p1_body.inc"
+#undef P1_BX
+#undef P1_BY
+#undef P1_BZ
+#undef P1_NBX
+#undef P1_LAST
 }
 
-// The same statements as a device function of the workgroup's coordinates (bx, by, bz) in a grid of (nbx, nby, nbz), on LDS that the
-// caller owns: a job's own coordinates in mlp_bwd_p1_jobs_kernel.  mlp_bwd_p1_body.inc is a COPY of the kernel's statements above with the
-// coordinates spelled P1_BX / P1_BY / P1_BZ / P1_NBX, without the LDS declarations, and with the last workgroup counted among the JOB's
-// workgroups (tests/test_host_stream_jobs.py holds the two texts together).  The kernel does not call this function: through a call its
-// register counts move.  s_own: 5 WG_BLOCK doubles for the last workgroup's sums where TCO TCI < 3 (else they go inside s_red); it may lie
-// inside the caller's larger reduction buffer -- everybody has left that by then.
+// The same statements (mlp_bwd_p1_body.inc, the one home of them) as a device function of the workgroup's coordinates (bx, by, bz) in a grid
+// of (nbx, nby, nbz), on LDS that the caller owns: a job's own coordinates in mlp_bwd_p1_jobs_kernel, and the last workgroup counted among
+// the JOB's workgroups.  The kernel and this function both INCLUDE the text; neither calls the other: through a call the kernel's register
+// counts move (profiles/r31_stream_groups.md), while the included text compiles to the code the kernel's own statements did
+// (profiles/r32_shared_body.md).  s_own: 5 WG_BLOCK doubles for the last workgroup's sums where they do not go inside s_red (P1_ALIAS); it
+// may lie inside the caller's larger reduction buffer -- everybody has left that by then.
 template <int TCO, int TCI>
 __device__ __forceinline__ void mlp_bwd_p1_body(const float* __restrict__ GA, const float* __restrict__ Y, const float* __restrict__ X,
                                                 const float* __restrict__ X2, int split, const float* __restrict__ coef, float slope, int64_t M,
@@ -223,11 +94,13 @@ __device__ __forceinline__ void mlp_bwd_p1_body(const float* __restrict__ GA, co
 #define P1_BY by
 #define P1_BZ bz
 #define P1_NBX nbx
+#define P1_LAST last_workgroup_of(ticket, nbx * nby * nbz, &s_flag, bx + nbx * (by + nby * bz))
 #include "mlp_bwd_p1_body.inc"
 #undef P1_BX
 #undef P1_BY
 #undef P1_BZ
 #undef P1_NBX
+#undef P1_LAST
 }
 
 // The pass of up to LFJ_MAX INDEPENDENT blocks in one launch: the jobs' own grids laid end to end (job j's workgroup (bx, by, bz) is

@@ -1,7 +1,14 @@
-// A copy of the statements of mlp_bwd_p1_kernel (mlp_bwd.hip) for mlp_bwd_p1_body, the device function that mlp_bwd_p1_jobs_kernel calls:
-// blockIdx.x / .y / .z and gridDim.x are spelled P1_BX, P1_BY, P1_BZ and P1_NBX (the job's own), the LDS (s_red, s_v, s_own, s_flag) and the
-// grid extents nby, nbz come from the enclosing function, and the last workgroup counts among the JOB's workgroups (last_workgroup_of).
-// A change to the kernel's statements is made in both places (tests/test_host_stream_jobs.py compares them).
+// The statements of pass 1 of the fused MLP backward, included by mlp_bwd_p1_kernel and by mlp_bwd_p1_body (mlp_bwd.hip), the device function
+// that mlp_bwd_p1_jobs_kernel calls.  The two include this text and neither calls the other: through a call the single kernel's registers
+// move (profiles/r31_stream_groups.md).  The includer provides
+//   the template parameters TCO, TCI;
+//   the parameters GA, Y, X, X2, split, coef, slope, M, Co, Ci, rows_per_block, PA, PB, PG, PX, ticket, dgamma, dbeta, bcoef
+//     (mlp_bwd_p1_kernel's list);
+//   the LDS: s_red [WG_WAVES][TCO TCI 256] floats, 16-byte aligned; s_v [WG_WAVES][(2 TCO + TCI) 16] floats; s_own, 5 WG_BLOCK doubles
+//     (read only where !P1_ALIAS<TCO, TCI>); s_flag, one int;
+//   the macros P1_BX, P1_BY, P1_BZ (the workgroup's coordinates), P1_NBX (the row slices of its grid) and P1_LAST (whether this workgroup is
+//     the last of its grid to arrive at `ticket`): the launch's own in the kernel, the job's in the body function.  The text never reads the
+//     launch's coordinates itself.
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int co_base = P1_BY * 16 * TCO, ci_base = P1_BZ * 16 * TCI;
     const int kk = lane >> 4, cc = lane & 15;
@@ -141,9 +148,8 @@
     }
     // The channel part of the finalize (dgamma, dbeta, the coefficients of gY for the dX pass) by the LAST workgroup of this launch
     // to finish (gridsync.hpp): the launch between the two passes of the block's backward disappears.  2 Co <= WG_BLOCK slots.
-    constexpr bool ALIAS = TCO * TCI >= 3;                     // the 10 KB of sums inside s_red (everybody has left it by then)
-    if (ticket == nullptr || !last_workgroup_of(ticket, P1_NBX * nby * nbz, &s_flag, P1_BX + P1_NBX * (P1_BY + nby * P1_BZ))) return;
-    double* s_buf = ALIAS ? reinterpret_cast<double*>(&s_red[0][0]) : s_own;
+    if (ticket == nullptr || !P1_LAST) return;
+    double* s_buf = P1_ALIAS<TCO, TCI> ? reinterpret_cast<double*>(&s_red[0][0]) : s_own;   // the 10 KB of sums inside s_red where they fit
     double* s_tot = s_buf + 4 * WG_BLOCK;
     sum_partial_rows_f64<WG_BLOCK>(pgr, (int)P1_NBX, 2 * Co, s_buf, s_tot);
     if ((int)threadIdx.x < Co) mlp_channel_part(threadIdx.x, s_tot[threadIdx.x], s_tot[Co + threadIdx.x], coef, M, Co, dgamma, dbeta, bcoef);

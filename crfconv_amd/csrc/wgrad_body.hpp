@@ -5,8 +5,6 @@
 
 namespace crf {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
 constexpr int WG_BLOCK = 256;
 constexpr int WG_WAVES = WG_BLOCK / WAVE;
 #ifndef WG_RED_BUFS_

@@ -1,7 +1,7 @@
-"""The job forms of the row-streaming kernels run a COPY of the single kernels' statements (csrc/linear_fwd_body.inc,
-mlp_bwd_p1_body.inc: the single kernels keep their own text so that their code stays what it was).  The copies must be the kernels'
-statements with only the workgroup coordinates respelled -- and, for the backward pass, the LDS declarations left to the caller and the last
-workgroup counted among the job's workgroups.  No GPU."""
+"""The single kernels and the job forms of the row-streaming kernels include ONE text of statements each (csrc/linear_fwd_body.inc,
+mlp_bwd_p1_body.inc).  What a job may never do is read the launch's own coordinates or own LDS: the text reaches both only through what
+its includer provides -- the coordinate macros, and for the backward pass the last-workgroup test -- and the single kernels provide the
+launch's.  No GPU."""
 import os
 import re
 
@@ -13,45 +13,54 @@ def _read(name):
         return f.read()
 
 
-def _kernel_statements(text, head, end):
-    """The statements between the `) {` that closes the parameter list starting at `head` and the kernel's closing brace in front of `end`."""
+# included text: (the file that includes it, the single kernel's head, the body function's head, what the kernel's macros must say)
+BODIES = {
+    'linear_fwd_body.inc': ('linear_fwd.hpp', '__global__ __launch_bounds__(LF_BLOCK) void linear_fwd_kernel(',
+                            '__device__ __forceinline__ void linear_fwd_body(',
+                            {'LF_BX': 'blockIdx.x', 'LF_BY': 'blockIdx.y', 'LF_NBX': 'gridDim.x'}),
+    'mlp_bwd_p1_body.inc': ('mlp_bwd.hip', '__global__ __launch_bounds__(WG_BLOCK) void mlp_bwd_p1_kernel(',
+                            '__device__ __forceinline__ void mlp_bwd_p1_body(',
+                            {'P1_BX': 'blockIdx.x', 'P1_BY': 'blockIdx.y', 'P1_BZ': 'blockIdx.z', 'P1_NBX': 'gridDim.x',
+                             'P1_LAST': 'last_workgroup(ticket, gridDim.x * gridDim.y * gridDim.z, &s_flag)'}),
+}
+
+
+def _function(text, head):
+    """The definition that starts at `head` (which must occur once), up to the closing brace at the start of a line."""
+    assert text.count(head) == 1, head
     a = text.index(head)
-    a = text.index(') {\n', a) + 4
-    body = text[a:text.index(end, a)].rstrip()
-    assert body.endswith('}')
-    return body[:-1]
+    return text[a:text.index('\n}\n', a)]
 
 
-def _copy_statements(text):
-    """An included file without its leading comment lines."""
-    lines = text.split('\n')
-    while lines and lines[0].startswith('//'):
-        lines.pop(0)
-    return '\n'.join(lines)
+def test_the_shared_statements_never_read_the_launch():
+    """A job's workgroup is not the launch's: the included text names neither the launch's coordinates nor LDS of its own."""
+    for inc in BODIES:
+        assert not re.search(r'blockIdx|gridDim|__shared__', _read(inc)), inc
 
 
-def test_linear_fwd_body_is_the_kernels_statements():
-    src = _kernel_statements(_read('linear_fwd.hpp'), '__global__ __launch_bounds__(LF_BLOCK) void linear_fwd_kernel(', '// The same statements as a device function')
-    for a, b in (('blockIdx.x', 'LF_BX'), ('blockIdx.y', 'LF_BY'), ('gridDim.x', 'LF_NBX')):
-        src = src.replace(a, b)
-    assert not re.search(r'blockIdx|gridDim', src)
-    assert src == _copy_statements(_read('linear_fwd_body.inc'))
+def test_each_text_is_included_by_its_kernel_and_its_body_function():
+    for inc, (host, kernel, body, _) in BODIES.items():
+        line = '#include "%s"' % inc
+        counts = {name: _read(name).count(line) for name in sorted(os.listdir(CSRC)) if name.endswith(('.hip', '.hpp', '.h', '.inc'))}
+        assert {n: c for n, c in counts.items() if c} == {host: 2}, (inc, counts)
+        text = _read(host)
+        assert _function(text, kernel).count(line) == 1 and _function(text, body).count(line) == 1, inc
 
 
-def test_mlp_bwd_p1_body_is_the_kernels_statements():
-    src = _kernel_statements(_read('mlp_bwd.hip'), '__global__ __launch_bounds__(WG_BLOCK) void mlp_bwd_p1_kernel(', '// The same statements as a device function')
-    for drop in ('    __shared__ __attribute__((aligned(16))) float s_red[WG_WAVES][TCO * TCI * 256];\n',
-                 '    __shared__ float s_v[WG_WAVES][(2 * TCO + TCI) * 16];\n',
-                 '    __shared__ double s_own[ALIAS ? 1 : 5 * WG_BLOCK];\n', '    __shared__ int s_flag;\n'):
-        assert src.count(drop) == 1
-        src = src.replace(drop, '')
-    last = 'last_workgroup(ticket, gridDim.x * gridDim.y * gridDim.z, &s_flag)'
-    assert src.count(last) == 1
-    src = src.replace(last, 'last_workgroup_of(ticket, P1_NBX * nby * nbz, &s_flag, P1_BX + P1_NBX * (P1_BY + nby * P1_BZ))')
-    for a, b in (('blockIdx.x', 'P1_BX'), ('blockIdx.y', 'P1_BY'), ('blockIdx.z', 'P1_BZ'), ('gridDim.x', 'P1_NBX')):
-        src = src.replace(a, b)
-    assert not re.search(r'blockIdx|gridDim|__shared__', src)
-    assert src == _copy_statements(_read('mlp_bwd_p1_body.inc'))
+def test_the_kernels_provide_the_launchs_own_coordinates():
+    """The single kernel's macros are the launch's coordinates and the whole-grid last-workgroup test; the body function defines the same
+    names from its arguments, and neither lets a macro outlive the include."""
+    for inc, (host, kernel, body, want) in BODIES.items():
+        text = _read(host)
+        for head in (kernel, body):
+            fn = _function(text, head)
+            defines = dict(re.findall(r'^#define (\w+) (.*)$', fn, re.M))
+            assert set(defines) == set(want), (inc, head, defines)
+            assert sorted(re.findall(r'^#undef (\w+)$', fn, re.M)) == sorted(want), (inc, head)
+            if head == kernel:
+                assert defines == want, (inc, defines)
+            else:
+                assert not re.search(r'blockIdx|gridDim', fn), (inc, head)
 
 
 def test_internal_job_records_match_the_compiler(tmp_path):
