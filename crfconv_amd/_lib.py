@@ -3,6 +3,8 @@
 include/crfconv_amd.h is the single declaration of the C ABI: SIGNATURES and one ctypes.Structure class per record type
 (crf_reduce_job -> ReduceJob, crf_pc_dump_job -> PcDumpJob, ..) are read from it when this module is imported.  A new entry
 point or job record is added to the header and to csrc/ only.
+include/crfconv_blocks.h, the sliding block split, is a second public header read the same way (BLOCKS_SIGNATURES, BLOCKS_RECORDS), and
+csrc/stream_jobs.h holds the entries only this package calls (INTERNAL_*): tables of their own, so the first header's stay its own.
 
 The library is the product: there is no Python / PyTorch fallback.  If it is missing or a call
 fails, an exception is raised -- never a silent slow path.
@@ -15,6 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('CRFCONV_LIB') or os.path.join(_HERE, 'libcrfconv_amd.so')      # CRFCONV_LIB: A/B builds of scratch/
 HEADER_PATH = os.path.join(_HERE, '..', 'include', 'crfconv_amd.h')
 INTERNAL_HEADER_PATH = os.path.join(_HERE, 'csrc', 'stream_jobs.h')        # entries only this package calls: not part of the public ABI
+BLOCKS_HEADER_PATH = os.path.join(_HERE, '..', 'include', 'crfconv_blocks.h')      # public: the entries behind crfconv_amd.blocks
 
 
 class CrfConvError(RuntimeError):
@@ -98,20 +101,23 @@ def record_class_name(c_name):
     return ''.join(w[:1].upper() + w[1:] for w in c_name[len('crf_'):].split('_'))
 
 
-# name -> (restype, argtypes), and C record name -> its ctypes.Structure class (also a module attribute under its CamelCase name)
-SIGNATURES, _records = _read_header()
-RECORDS = {c_name: type(record_class_name(c_name), (ctypes.Structure,),
-                        {'_fields_': fields, '__doc__': '%s of include/crfconv_amd.h.' % c_name})
-           for c_name, fields in _records.items()}
-globals().update((cls.__name__, cls) for cls in RECORDS.values())
-# the same for the package-internal entries of csrc/stream_jobs.h (LinearJob, MlpStreamBwdJob): tables of their own, the public ones stay the header's
-INTERNAL_SIGNATURES, _internal_records = _read_header(INTERNAL_HEADER_PATH)
-INTERNAL_RECORDS = {c_name: type(record_class_name(c_name), (ctypes.Structure,),
-                                 {'_fields_': fields, '__doc__': '%s of csrc/stream_jobs.h.' % c_name})
-                    for c_name, fields in _internal_records.items()}
-if set(INTERNAL_SIGNATURES) & set(SIGNATURES) or set(INTERNAL_RECORDS) & set(RECORDS):
-    raise CrfConvError('csrc/stream_jobs.h declares a name of include/crfconv_amd.h again')
-globals().update((cls.__name__, cls) for cls in INTERNAL_RECORDS.values())
+def _tables(path, where, taken=()):
+    """(signatures, record classes) of one header: name -> (restype, argtypes), and C record name -> its ctypes.Structure class (also a
+    module attribute under its CamelCase name).  A name that a table in `taken` holds already is refused."""
+    signatures, fields = _read_header(path)
+    records = {c_name: type(record_class_name(c_name), (ctypes.Structure,), {'_fields_': f, '__doc__': '%s of %s.' % (c_name, where)})
+               for c_name, f in fields.items()}
+    if any((set(signatures) | set(records)) & set(t) for t in taken):
+        raise CrfConvError('%s declares a name of another header again' % where)
+    globals().update((cls.__name__, cls) for cls in records.values())
+    return signatures, records
+
+
+SIGNATURES, RECORDS = _tables(HEADER_PATH, 'include/crfconv_amd.h')
+# the package-internal entries of csrc/stream_jobs.h (LinearJob, MlpStreamBwdJob) and the block split's public header: tables of their own
+INTERNAL_SIGNATURES, INTERNAL_RECORDS = _tables(INTERNAL_HEADER_PATH, 'csrc/stream_jobs.h', (SIGNATURES, RECORDS))
+BLOCKS_SIGNATURES, BLOCKS_RECORDS = _tables(BLOCKS_HEADER_PATH, 'include/crfconv_blocks.h',
+                                            (SIGNATURES, RECORDS, INTERNAL_SIGNATURES, INTERNAL_RECORDS))
 
 _lib = None
 
@@ -125,7 +131,7 @@ def load():
                 '%s not found: build it with `make -C crfconv_amd/csrc` (or __graft_entry__.build()). '
                 'crfconv_amd has no CPU / PyTorch fallback.' % LIB_PATH)
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(INTERNAL_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(INTERNAL_SIGNATURES.items()) + list(BLOCKS_SIGNATURES.items()):
             fn = getattr(lib, name)      # AttributeError here == header and library out of sync
             fn.restype = res
             fn.argtypes = args
