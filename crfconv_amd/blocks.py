@@ -12,6 +12,16 @@ sparse networks take --, bit for bit the blocks of the reference's NumPy loop an
     data = split.as_data(x, split.take(labels))
 
 There is one host read (the block and row totals, which size the outputs) and no Python loop over blocks or scenes.
+
+The networks return one row of scores per block ROW; ``BlockVotes`` (csrc/block_votes.hip) brings them back to the points of the scenes --
+a point lies in up to 64 blocks -- by a sum in a fixed order over the point's rows: the same bits in every run, no float atomics:
+
+    votes = blocks.BlockVotes(split, num_classes, core='prefer', exp=True)      # exp: the networks return log_softmax
+    for b0 in range(0, split.n_blocks, 32):                                     # the network over chunks of blocks
+        data, row_offset = split.select(b0, min(b0 + 32, split.n_blocks), x)
+        votes.update(net(data).detach(), row_offset)                            # ONE launch, no host read
+    scores, pred = votes.result('mean')                                         # pred = -1 where no kept block covers the point
+    hist = votes.confusion(labels)                                              # int64 [C, C]: feeds runningScore / iou_from_confusions
 """
 import ctypes
 import math
@@ -35,6 +45,9 @@ CELL_CAP = 1 << 16            # grid cells the first attempt has room for; a lar
 _LIMIT = 1 << 31
 
 _STATUS_BAD_PTR, _STATUS_CELL_CAP, _STATUS_OVERFLOW = 1, 2, 4
+CORE_MODES = {'all': 0, 'only': 1, 'prefer': 2}
+REDUCE_FORMS = {'sum': 0, 'mean': 1}
+MAX_CLASSES = 64              # classes BlockVotes takes: a workgroup holds whole points
 
 
 def memberships_bound(block_size, stride, padding):
@@ -53,6 +66,7 @@ class BlockSplit:
         self.scene, self.cell, self.pos_min, self.limit = scene, cell, pos_min, limit
         self.n_blocks, self.n_rows = scene.shape[0], rows.shape[0]
         self._pos_block = None
+        self._reverse = self._rev_packed = self._ptr_host = None
 
     def take(self, t):
         """t[rows]: a per-point tensor (labels, colours) gathered to the rows of the blocks."""
@@ -93,6 +107,130 @@ class BlockSplit:
             raise ValueError('BlockSplit.as_data: x and y must have one row per block row (%d)' % self.n_rows)
         pos_block = self._pos_block if self._pos_block is not None else self.features('room')[0]
         return Data(pos=pos_block, x=x, y=y, batch=self.batch, ptr=self.ptr, mask=self.mask, indices=self.indices)
+
+    def select(self, b0, b1, x, y=None):
+        """(``Data`` of blocks b0 .. b1, row_offset): pos, x, y, mask and indices sliced to the rows of those blocks, batch - b0 and ptr
+        rebased to start at 0 -- one chunk of the split for the network -- and the first row of the chunk, what ``BlockVotes.update``
+        takes beside the chunk's scores.  The row ranges come from a host copy of ptr, read once and kept."""
+        if x.shape[0] != self.n_rows or (y is not None and y.shape[0] != self.n_rows):
+            raise ValueError('BlockSplit.select: x and y must have one row per block row (%d)' % self.n_rows)
+        b0, b1 = int(b0), int(b1)
+        if not 0 <= b0 <= b1 <= self.n_blocks:
+            raise ValueError('BlockSplit.select: blocks %d .. %d outside 0 .. %d' % (b0, b1, self.n_blocks))
+        if self._ptr_host is None:
+            self._ptr_host = self.ptr.tolist()             # the one host read of select, at its first call
+        pos_block = self._pos_block if self._pos_block is not None else self.features('room')[0]
+        r0, r1 = self._ptr_host[b0], self._ptr_host[b1]
+        rows = slice(r0, r1)
+        return Data(pos=pos_block[rows], x=x[rows], y=None if y is None else y[rows], batch=self.batch[rows] - b0,
+                    ptr=self.ptr[b0:b1 + 1] - r0, mask=self.mask[rows], indices=self.indices[rows]), r0
+
+    def _reverse_packed(self):
+        """(rev_ptr, the list entries as the library wrote them: the row in bits 0..30, the core flag in bit 31), built once."""
+        from .graph import ptr as p_, stream_ptr
+        if self._rev_packed is None:
+            N, R, dev = self._pos.shape[0], self.n_rows, self._pos.device
+            if N == 0 or R == 0:
+                self._rev_packed = (_zeros(N + 1, torch.int64, dev), torch.empty(0, dtype=torch.int32, device=dev))
+            else:
+                rev_ptr = torch.empty(N + 1, dtype=torch.int64, device=dev)
+                packed = torch.empty(R, dtype=torch.int32, device=dev)
+                nbytes = _lib.call('crfconv_block_reverse_workspace', N, R)
+                ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+                _lib.call('crfconv_block_reverse', p_(self.rows), R, N, p_(self.mask), p_(ws), nbytes, p_(rev_ptr), p_(packed), stream_ptr())
+                self._rev_packed = (rev_ptr, packed)
+        return self._rev_packed
+
+    def reverse(self):
+        """(rev_ptr [N + 1] int64, rev_rows [R] int32): rev_rows[rev_ptr[p] : rev_ptr[p + 1]] are the block rows r with rows[r] == p,
+        ascending.  Built at the first call by a stable sort (no atomics: the same bits in every run) and kept on the split."""
+        if self._reverse is None:
+            rev_ptr, packed = self._reverse_packed()
+            self._reverse = (rev_ptr, packed & 0x7fffffff)
+        return self._reverse
+
+
+class BlockVotes:
+    """Scores per block row summed onto the points of the split's scenes, deterministically (csrc/block_votes.hip).
+
+    ``update(scores, row_offset)`` adds, for every point, the scores of its rows among row_offset .. row_offset + len(scores) in
+    ascending row order (float32, one add per row, then one add onto ``sums``) and the number of rows to ``count``; with exp=True the
+    terms are expf(score).  core: 'all' rows of a point, 'only' those in their block's un-padded core (mask == 1), 'prefer' the core rows
+    of a point that has one anywhere in the split and all rows of a point that has none.  sums [N, C] float32 and count [N] int32 are
+    public.  No backward."""
+
+    def __init__(self, split, num_classes, core='prefer', exp=False):
+        if not isinstance(split, BlockSplit):
+            raise ValueError('BlockVotes: split must be the BlockSplit of sliding_blocks')
+        if core not in CORE_MODES:
+            raise ValueError("BlockVotes: core must be 'all', 'only' or 'prefer', got %r" % (core,))
+        C = int(num_classes)
+        if not 1 <= C <= MAX_CLASSES:
+            raise ValueError('BlockVotes: num_classes = %d outside 1 .. %d' % (C, MAX_CLASSES))
+        self.split, self.num_classes, self.core, self.exp = split, C, core, bool(exp)
+        self._rev_ptr, self._rev_rows = split._reverse_packed()
+        self.n_points, dev = split._pos.shape[0], split._pos.device
+        self.sums = torch.zeros((self.n_points, C), dtype=torch.float32, device=dev)
+        self.count = torch.zeros(self.n_points, dtype=torch.int32, device=dev)
+        self._bad = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def reset(self):
+        self.sums.zero_()
+        self.count.zero_()
+
+    def update(self, scores, row_offset=0):
+        """scores [R', C] float32 on the device: the scores of block rows row_offset .. row_offset + R' (row_offset a host int, as
+        ``BlockSplit.select`` returns it).  ONE library call, no host read: capturable."""
+        from .graph import ptr as p_, stream_ptr
+        C, R = self.num_classes, self.split.n_rows
+        if not (torch.is_tensor(scores) and scores.dim() == 2 and scores.shape[1] == C and scores.dtype == torch.float32):
+            raise ValueError('BlockVotes.update: scores must be a float32 tensor [rows, %d]' % C)
+        if not scores.is_cuda:
+            raise ValueError('BlockVotes.update: scores must be on the device (got %s); there is no CPU path' % scores.device)
+        row_offset, n = int(row_offset), scores.shape[0]
+        if row_offset < 0 or row_offset + n > R:
+            raise ValueError('BlockVotes.update: rows %d .. %d outside the split\'s 0 .. %d' % (row_offset, row_offset + n, R))
+        if n == 0 or self.n_points == 0:
+            return
+        scores = scores.detach().contiguous()
+        _lib.call('crfconv_block_votes_update', p_(scores), n, row_offset, C, p_(self._rev_ptr), p_(self._rev_rows), R, self.n_points,
+                  CORE_MODES[self.core], 1 if self.exp else 0, p_(self.sums), p_(self.count), stream_ptr())
+        for t in (self.sums, self.count):                  # written by a library kernel
+            torch.autograd.graph.increment_version(t)
+
+    def result(self, reduce='mean', fill=-1):
+        """(scores_out [N, C] float32, pred [N] int64): sums ('sum') or sums / float32(count) ('mean'), and the first arg-max of sums.
+        A point no row was added to has a zero row and pred = fill.  One launch, no host read."""
+        from .graph import ptr as p_, stream_ptr
+        if reduce not in REDUCE_FORMS:
+            raise ValueError("BlockVotes.result: reduce must be 'mean' or 'sum', got %r" % (reduce,))
+        N, C, dev = self.n_points, self.num_classes, self.sums.device
+        out = torch.empty((N, C), dtype=torch.float32, device=dev)
+        pred = torch.empty(N, dtype=torch.int64, device=dev)
+        if N:
+            _lib.call('crfconv_block_votes_result', p_(self.sums), p_(self.count), N, C, REDUCE_FORMS[reduce], int(fill), p_(out), p_(pred),
+                      stream_ptr())
+        return out, pred
+
+    def confusion(self, labels, label_shift=0, out=None):
+        """Confusion matrix of the merged votes, device int64 [C, C] (rows = ground truth), through crfconv_vote_confusion on ``sums``: the
+        prediction of point p is the first arg-max of sums[p], its class labels[p] - label_shift; labels outside [0, C) are skipped, and
+        so are the points no row was added to (their labels are moved outside first).  Accumulates into `out` when given."""
+        from .graph import ptr as p_, require_gpu, stream_ptr
+        N, C = self.n_points, self.num_classes
+        if not (torch.is_tensor(labels) and labels.numel() == N):
+            raise ValueError('BlockVotes.confusion: one label per point (%d) is needed' % N)
+        if out is None:
+            out = torch.zeros((C, C), dtype=torch.int64, device=self.sums.device)
+        elif not (torch.is_tensor(out) and out.dtype == torch.int64 and tuple(out.shape) == (C, C) and out.is_contiguous()):
+            raise ValueError('BlockVotes.confusion(out=): a contiguous int64 [%d, %d] tensor is needed' % (C, C))
+        require_gpu(labels, out)
+        if N == 0:
+            return out
+        labels = torch.where(self.count > 0, labels.reshape(-1).long(), int(label_shift) - 1).contiguous()
+        _lib.call('crfconv_vote_confusion', p_(self.sums), N, C, None, p_(labels), N, int(label_shift), p_(out), p_(self._bad), stream_ptr())
+        torch.autograd.graph.increment_version(out)
+        return out
 
 
 def _zeros(shape, dtype, dev):
