@@ -5,7 +5,8 @@ include/crfconv_amd.h is the single declaration of the C ABI: SIGNATURES and one
 point or job record is added to the header and to csrc/ only.
 include/crfconv_blocks.h, the sliding block split, is a second public header read the same way (BLOCKS_SIGNATURES, BLOCKS_RECORDS),
 include/crfconv_block_votes.h, the merge of per-block scores onto the points, a third (VOTES_SIGNATURES, VOTES_RECORDS),
-include/crfconv_grid.h, the grid subsampling of ragged batches, a fourth (GRID_SIGNATURES, GRID_RECORDS), and
+include/crfconv_grid.h, the grid subsampling of ragged batches, a fourth (GRID_SIGNATURES, GRID_RECORDS),
+include/crfconv_parts.h, the part IoU of ragged shape batches, a fifth (PARTS_SIGNATURES, PARTS_RECORDS), and
 csrc/stream_jobs.h holds the entries only this package calls (INTERNAL_*): tables of their own, so the first header's stay its own.
 
 The library is the product: there is no Python / PyTorch fallback.  If it is missing or a call
@@ -22,6 +23,7 @@ INTERNAL_HEADER_PATH = os.path.join(_HERE, 'csrc', 'stream_jobs.h')        # ent
 BLOCKS_HEADER_PATH = os.path.join(_HERE, '..', 'include', 'crfconv_blocks.h')      # public: the entries behind crfconv_amd.blocks
 VOTES_HEADER_PATH = os.path.join(_HERE, '..', 'include', 'crfconv_block_votes.h')      # public: the entries behind blocks.BlockVotes
 GRID_HEADER_PATH = os.path.join(_HERE, '..', 'include', 'crfconv_grid.h')      # public: the entries behind crfconv_amd.grid
+PARTS_HEADER_PATH = os.path.join(_HERE, '..', 'include', 'crfconv_parts.h')      # public: the entries behind utils.PartScores
 
 
 class CrfConvError(RuntimeError):
@@ -127,6 +129,9 @@ VOTES_SIGNATURES, VOTES_RECORDS = _tables(VOTES_HEADER_PATH, 'include/crfconv_bl
 GRID_SIGNATURES, GRID_RECORDS = _tables(GRID_HEADER_PATH, 'include/crfconv_grid.h',
                                         (SIGNATURES, RECORDS, INTERNAL_SIGNATURES, INTERNAL_RECORDS, BLOCKS_SIGNATURES, BLOCKS_RECORDS,
                                          VOTES_SIGNATURES, VOTES_RECORDS))
+PARTS_SIGNATURES, PARTS_RECORDS = _tables(PARTS_HEADER_PATH, 'include/crfconv_parts.h',
+                                          (SIGNATURES, RECORDS, INTERNAL_SIGNATURES, INTERNAL_RECORDS, BLOCKS_SIGNATURES, BLOCKS_RECORDS,
+                                           VOTES_SIGNATURES, VOTES_RECORDS, GRID_SIGNATURES, GRID_RECORDS))
 
 _lib = None
 
@@ -141,7 +146,7 @@ def load():
                 'crfconv_amd has no CPU / PyTorch fallback.' % LIB_PATH)
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(INTERNAL_SIGNATURES.items()) + list(BLOCKS_SIGNATURES.items())
-                                  + list(VOTES_SIGNATURES.items()) + list(GRID_SIGNATURES.items())):
+                                  + list(VOTES_SIGNATURES.items()) + list(GRID_SIGNATURES.items()) + list(PARTS_SIGNATURES.items())):
             fn = getattr(lib, name)      # AttributeError here == header and library out of sync
             fn.restype = res
             fn.argtypes = args
